@@ -68,6 +68,8 @@ FLOAT_MODES = {"strict": 0, "fast": 1, "relaxed": 2}
 CPU_PASSES = 11         # ~10 s of host work on the GPU box's 32 cores (0.9-1.0 s per 4096^2 pass)
 PREHEAT_MIN_STEPS = 50  # untimed passes before the timed region, warm-up included (clock settling)
 MAX_MARKED_STEPS = 200  # per-stage markers are kept for the last steps only (the handle ring holds 4096)
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: a larger plane is written as a fixed, seeded sample of its rows
+DUMP_SEED = 20240917
 
 
 def parse():
@@ -114,7 +116,28 @@ def parse():
                     help="nz_ctx_set_float_mode of the timed steps: strict (the reference's operation sequence, bit-equal to the "
                          "oracle: the headline), fast (fBm tail and tap sums FMA-contracted, every stage within 1e-5 of strict), "
                          "relaxed (fast + the flow iterations).  The other modes are timed beside the headline in `float_modes`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the height plane the last timed step left (what a caller of the timed "
+                         "path receives) as DIR/height.npy (float32, rows x cols) and the global index of each of its rows as "
+                         "DIR/height_rows.npy (float64); a plane over %d MiB is written as a fixed, seeded sample of its rows"
+                         % (DUMP_MAX_BYTES >> 20))
     return ap.parse_args()
+
+
+def dump_rows(grid_rows, cols):
+    """The global rows --dump-outputs writes for a grid_rows x cols plane: all of them, or a fixed, seeded sample (sorted) that
+    fits DUMP_MAX_BYTES.  The same arguments give the same rows on every run and every build."""
+    import numpy as np
+    k = min(grid_rows, max(1, DUMP_MAX_BYTES // (cols * 4)))
+    if k == grid_rows:
+        return np.arange(grid_rows)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(grid_rows, k, replace=False))
+
+
+def write_dump(np, out_dir, rows, height):
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "height.npy"), np.ascontiguousarray(height, dtype=np.float32))
+    np.save(os.path.join(out_dir, "height_rows.npy"), np.asarray(rows, dtype=np.float64))
 
 
 # ---- counter summaries ---------------------------------------------------------------------------------------------
@@ -519,6 +542,8 @@ def self_launch(argv, gpus):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.impl == "python" and (args.gpus > 1 or args.sharded or args.as_rank is not None):
+        raise SystemExit("--dump-outputs: the sharded runs dump the native schedule's planes only (--impl native)")
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.self_launch):
         self_launch(sys.argv[1:], args.gpus)
     import numpy as np
@@ -724,6 +749,33 @@ def main():
         host_t.append(time.perf_counter())
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        # outside the timed region: the plane the last timed step left, before anything else runs on it
+        if not sharded:
+            rows = dump_rows(res, res)
+            last = np.empty(cells, np.float32)
+            nj._native.check(nj._native.lib.nz_tile_download(ctx._h, gd.data.ptr, last.ctypes.data, cells, 0, None),
+                             "download")
+            fence()
+            write_dump(np, args.dump_outputs, rows, last.reshape(res, res)[rows])
+        else:
+            # every rank's share of the sampled rows, gathered on rank 0 in global row order
+            rows = dump_rows(plan.grows, plan.cols)
+            mine = []
+            for i in range(grid.local_stripes):
+                g0, got = grid.owned_rows(i)
+                sel = rows[(rows >= g0) & (rows < g0 + got.shape[0])]
+                mine.append((sel, got[sel - g0]))
+            parts = [None] * world
+            if world > 1:
+                dist.all_gather_object(parts, mine)
+            else:
+                parts = [mine]
+            if rank == 0:
+                got_rows = np.concatenate([r for part in parts for r, _ in part])
+                height = np.concatenate([h for part in parts for _, h in part], axis=0)
+                order = np.argsort(got_rows, kind="stable")
+                write_dump(np, args.dump_outputs, got_rows[order], height[order])
     # (the collector stays off for the informational measurements below, which collect by hand before their own warm-ups)
     if os.environ.get("NZ_BENCH_HOST_TIMES"):
         iv = [(host_t[k + 1] - host_t[k]) * 1e3 for k in range(len(host_t) - 1)]

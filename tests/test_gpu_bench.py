@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -166,3 +167,23 @@ def test_bench_gpus_2_without_a_launcher():
     assert c["backend"] == "nccl" and c["world"] == 2 and c["halo"] == "exchange" and c["exchange_ms_per_step"] > 0.0
     assert set(d["grid_2048"]) >= {"recompute", "exchange", "exchange_interior_first", "exchange_border_first", "exchange_once"}
     assert c["impl"].startswith("native") and c["bytes_sent_per_step"] > 0
+
+
+def test_dump_outputs_are_the_last_timed_plane(oracle, tmp_path):
+    # --dump-outputs DIR: the plane the last timed step left, as a caller of the timed path receives it, against the oracle
+    want = oracle.pipeline(512, 512, oracle.SIMPLEX, 0.4, 1.0, 2.0, 0.0, 13, 0, 0, 1700, oracle.GAUSS5_S1, 17, 5, 0.0, 0.005, 5)
+    tile = tmp_path / "tile"
+    d = _run("--steps", "3", "--warmup", "1", "--res", "512", "--grid", "0", "--no-extras", "--no-cpu-baseline",
+             "--dump-outputs", str(tile))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    h, rows = np.load(tile / "height.npy"), np.load(tile / "height_rows.npy")
+    assert h.dtype == np.float32 and h.shape == (512, 512) and rows.dtype == np.float64
+    assert np.array_equal(rows, np.arange(512)) and np.array_equal(h, want)
+    # the sharded schedule (one-rank rehearsal, closed-form ghost rows): the rows the rank owns, global row numbers
+    want = oracle.pipeline(1024, 1024, oracle.SIMPLEX, 0.4, 1.0, 2.0, 0.0, 13, 0, 0, 1700, oracle.GAUSS5_S1, 17, 5, 0.0, 0.005, 5)
+    stripe = tmp_path / "stripe"
+    d = _run("--steps", "2", "--warmup", "1", "--as-rank", "1", "4", "--stripe-rows", "256", "--cols", "1024", "--grid", "0",
+             "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(stripe))
+    assert d["steps"] == 2
+    h, rows = np.load(stripe / "height.npy"), np.load(stripe / "height_rows.npy")
+    assert np.array_equal(rows, np.arange(256, 512)) and np.array_equal(h, want[256:512])
