@@ -219,7 +219,7 @@ namespace xshazwar.noize.hip {
         void CompleteActive() {
             try {
                 pipelineHandle.Complete();
-            } catch (NoizeException e) when (e.status == Native.NZ_ERR_RETRY && stage_instances[0].GetType() == typeof(NoiseStage)
+            } catch (NoizeException e) when (e.status == Native.NZ_ERR_RETRY && stage_instances[0] is NoiseStage  // (ShapedNoiseStage too)
                                              && RetryIsLocal()) {
                 foreach (PipelineStage stage in stage_instances) stage.OnStageComplete();
                 pipelineRunning = false;

@@ -1,6 +1,7 @@
 // Stages.cs -- the stage classes of the hot path with the reference's fields and Schedule bodies; where the reference
 // calls a static Burst-job delegate, these call the C ABI (one extern "C" entry per delegate, include/noize_hip.h).
 //   NoiseStage            Noise/NoiseStage.cs:13-61
+//   ShapedNoiseStage      new-framework: NoiseStage with an octave shape (billow, ridged multifractal)
 //   KernelFilterStage     Filter/KernelFilterStage.cs:13-51
 //   StageGaussianBlur     Filter/Kernel/Blur/StageGaussianBlur.cs:14-53
 //   StageSmoothBlur       Filter/Kernel/Blur/StageSmoothBlur.cs:14-52
@@ -16,6 +17,7 @@ using System;
 namespace xshazwar.noize.hip {
 
     public enum FractalNoise { Sin, Perlin, PeriodicPerlin, Simplex, RotatedSimplex, Cellular, DomainRotatedPerlin, DomainRotatedSimplex }  // NoiseStage.cs:15-24
+    public enum FractalShape { Fbm, Billow, Ridged }                                                                                     // enum nz_fractal_shape
     public enum KernelFilterType { Gauss9_S1, Gauss7_S1, Gauss5_S1, Gauss3_S1, Gauss9_S2, Gauss7_S2, Gauss5_S2, Gauss3_S2, Smooth3,
                                    Sobel3Horizontal, Sobel3Vertical, Sobel3_2D, Prewitt3Horizontal, Prewitt3Vertical }                  // KernelJob.cs:79-94
     public enum GaussSigma { s0d50, s1d00, s1d50, s2d00, s2d50, s3d00, s3d50, s4d00, s4d50, s5d00, s5d50, s6d00, s6d50, s7d00, s7d50, s8d00 } // BlurKernels.cs:8-25
@@ -57,6 +59,29 @@ namespace xshazwar.noize.hip {
             // jobs[(int) noiseType](d.data, d.resolution, hurst, startingAmplitude, stepdown, detuneRate, octaves, d.xpos, d.zpos, noiseSize, dependency)
             Native.Check(Native.nz_fractal(ctx.Handle, (int) noiseType, d.data.Ptr, d.resolution, hurst, startingAmplitude, stepdown,
                                            detuneRate, octaves, d.xpos, d.zpos, noiseSize, dependency.id, out ulong h), "nz_fractal");
+            jobHandle = Done(h);
+        }
+    }
+
+    // NoiseStage with an octave shape; Fbm gives the bits of NoiseStage.  BasePipeline.StockListParams compares the exact type,
+    // so a shaped stage never runs there as plain fBm.
+    public class ShapedNoiseStage : NoiseStage {
+        public FractalShape shape = FractalShape.Ridged;
+        public float ridgeOffset = 1f, ridgeGain = 2f;
+        public ShapedNoiseStage(GpuContext ctx) : base(ctx) {}
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_fractal_shaped_batch(ctx.Handle, (int) noiseType, b.data.Ptr, b.resolution, b.count, b.positions.Ptr,
+                                                            hurst, startingAmplitude, stepdown, detuneRate, octaves, noiseSize, (int) shape,
+                                                            ridgeOffset, ridgeGain, dependency.id, out ulong hb), "nz_fractal_shaped_batch");
+                jobHandle = Done(hb);
+                return;
+            }
+            Native.Check(Native.nz_fractal_shaped(ctx.Handle, (int) noiseType, d.data.Ptr, d.resolution, hurst, startingAmplitude, stepdown,
+                                                  detuneRate, octaves, d.xpos, d.zpos, noiseSize, (int) shape, ridgeOffset, ridgeGain,
+                                                  dependency.id, out ulong h), "nz_fractal_shaped");
             jobHandle = Done(h);
         }
     }

@@ -51,6 +51,13 @@ enum nz_noise_type {
     NZ_NOISE_DOMAIN_ROTATED_SIMPLEX
 };
 
+/* octave shape of nz_fractal_shaped* (new-framework feature; v = the basis value the fBm sums, in [0, 1]):
+ *   FBM     t += a * v                                   (what nz_fractal computes)
+ *   BILLOW  t += a * |2v - 1|
+ *   RIDGED  r = (ridgeOffset - |2v - 1|)^2 * w;  t += a * r;  w = clamp(r * ridgeGain, 0, 1)   (w = 1 before octave 0)
+ * the result is t / CalcFractalNormValue in every shape */
+enum nz_fractal_shape { NZ_SHAPE_FBM = 0, NZ_SHAPE_BILLOW = 1, NZ_SHAPE_RIDGED = 2 };
+
 /* KernelFilterType, Filter/Kernel/KernelJob.cs:79-94 */
 enum nz_kernel_filter_type {
     NZ_GAUSS9_S1 = 0, NZ_GAUSS7_S1, NZ_GAUSS5_S1, NZ_GAUSS3_S1,
@@ -169,6 +176,18 @@ int32_t nz_fractal(nz_ctx *ctx, int32_t noiseType, float *src, int32_t resolutio
 int32_t nz_fractal_stripe(nz_ctx *ctx, int32_t noiseType, float *buf, const nz_stripe *st, float hurst,
                           float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
                           int32_t xpos, int32_t zpos, int32_t noiseSize, nz_handle dep, nz_handle *out);
+
+/* nz_fractal / nz_fractal_stripe with an octave shape (enum nz_fractal_shape; ridgeOffset / ridgeGain are read by
+ * NZ_SHAPE_RIDGED only, 1 and 2 are the usual values).  A shape outside the enum is NZ_ERR_INVALID and writes nothing;
+ * NZ_SHAPE_FBM returns the bits of nz_fractal in every float mode. */
+int32_t nz_fractal_shaped(nz_ctx *ctx, int32_t noiseType, float *src, int32_t resolution, float hurst,
+                          float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                          int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                          float ridgeGain, nz_handle dep, nz_handle *out);
+int32_t nz_fractal_shaped_stripe(nz_ctx *ctx, int32_t noiseType, float *buf, const nz_stripe *st, float hurst,
+                                 float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                                 int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                                 float ridgeGain, nz_handle dep, nz_handle *out);
 
 /* ---- separable kernel filters ------------------------------------------------------------- */
 /* SeperableKernelFilterDelegate, Filter/Kernel/KernelJob.cs:308-314 (one X+Z application) */
@@ -298,6 +317,10 @@ int32_t nz_flow_fused_stripe(nz_ctx *ctx, const float *height, const float *cons
 int32_t nz_fractal_batch(nz_ctx *ctx, int32_t noiseType, float *data, int32_t resolution, int32_t count,
                          const int32_t *positions, float hurst, float startingAmplitude, float stepdown,
                          float detuneRate, int32_t octaves, int32_t noiseSize, nz_handle dep, nz_handle *out);
+int32_t nz_fractal_shaped_batch(nz_ctx *ctx, int32_t noiseType, float *data, int32_t resolution, int32_t count,
+                                const int32_t *positions, float hurst, float startingAmplitude, float stepdown,
+                                float detuneRate, int32_t octaves, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                                float ridgeGain, nz_handle dep, nz_handle *out);
 int32_t nz_kernel_filter_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t filter, int32_t iterations,
                                      int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
 int32_t nz_gauss_blur_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t width, int32_t sigma,

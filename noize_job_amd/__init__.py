@@ -7,10 +7,10 @@ it is missing: there is no CPU or PyTorch fallback in the product path.
 from . import _native
 from ._native import NoizeError, Stripe
 from .runtime import Context, DeviceTile, JobHandle
-from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DownsampleData, ErosionStage, FlowMapStage, FractalNoise, GaussSigma,
+from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DownsampleData, ErosionStage, FlowMapStage, FractalNoise, FractalShape, GaussSigma,
                        GeneratorData, GeneratorDataBatch, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
-                       ReducePipeline, ReduceStage, Upstream,
+                       ReducePipeline, ReduceStage, ShapedNoiseStage, Upstream,
                        ReductionType, StageGaussianBlur, StageThermalErosion,
                        StageIO, StageSmoothBlur)
 

@@ -519,7 +519,7 @@ __device__ __forceinline__ float snoise2_tab_fast(float vx, float vy, const int 
 }
 
 // batched launch: grid blockIdx.y of the batch has its own world position and output plane
-__device__ __forceinline__ void fractal_batch_enter(nz_fractal_params &p, float *__restrict__ &dst) {
+__device__ __forceinline__ void fractal_batch_enter(nz_fractal_kparams &p, float *__restrict__ &dst) {
     if (p.positions) {
         p.posx = (float)p.positions[2 * blockIdx.y];
         p.posz = (float)p.positions[2 * blockIdx.y + 1];
@@ -527,12 +527,38 @@ __device__ __forceinline__ void fractal_batch_enter(nz_fractal_params &p, float 
     dst += blockIdx.y * p.bstride;
 }
 
+// ---- octave shapes (nz_fractal_shaped, enum nz_fractal_shape) ----------------------------------------------------------
+// Every octave loop below hands its basis value v to octave_add<SHAPE>.  SHAPE is a template argument of each kernel, so
+// the shape-0 instantiations compile to the fBm sum they always were (`w` is dead there and disappears).  Billow and ridged
+// fold e = |2v - 1| (2v is exact, so twice_minus_one is the separate multiply and add bit for bit); ridged carries one
+// weight register per cell, 1 before octave 0.  fminf / fmaxf are the C functions (a NaN operand yields the other one).
+template <int SHAPE>
+__device__ __forceinline__ void shape_fold(float &t, float &w, float a, float e, const nz_ridge_params &rp) {
+    if constexpr (SHAPE == NZ_SHAPE_BILLOW) {
+        t += a * e;
+    } else if constexpr (SHAPE == NZ_SHAPE_RIDGED) {
+        float r = rp.offset - e;
+        r = r * r;
+        r = r * w;
+        t += a * r;
+        w = fminf(fmaxf(r * rp.gain, 0.0f), 1.0f);
+    }
+}
+template <int SHAPE>
+__device__ __forceinline__ void octave_add(float &t, float &w, float a, float v, const nz_ridge_params &rp) {
+    if constexpr (SHAPE == NZ_SHAPE_FBM) {
+        t += a * v;
+    } else {
+        shape_fold<SHAPE>(t, w, a, fabsf(twice_minus_one(v)), rp);
+    }
+}
 
-template <int VEC, bool FAST>
+
+template <int VEC, bool FAST, int SHAPE>
 __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restrict__ dst, int rows, int cols, int pitch,
-                                                                 int blocks_per_row, nz_fractal_params p,
+                                                                 int blocks_per_row, nz_fractal_kparams p,
                                                                  const int *__restrict__ t1g,
-                                                                 const float4 *__restrict__ t2g) {
+                                                                 const float4 *__restrict__ t2g, nz_ridge_params rp) {
     __shared__ int s_t1[NZ_T1_N];
     __shared__ float4 s_t2[FAST ? 1 : NZ_T2_N];
     __shared__ float2 s_t2f[FAST ? NZ_T2_N : 1];  // tolerance mode: {a0, h} * norm, 8-byte entries (T1 staged as 8 * permute)
@@ -558,14 +584,25 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
     int zend = min(rows, (by + 1) * p.rows_per_wg);
     for (int z = by * p.rows_per_wg; z < zend; z++) {
         float zi = ((float)z + p.posz) / p.noise_size;
-        float t[VEC];
+        float t[VEC], w[VEC];
 #pragma unroll
-        for (int c = 0; c < VEC; c++) t[c] = 0.0f;
+        for (int c = 0; c < VEC; c++) t[c] = 0.0f, w[c] = 1.0f;
         float detune = 0.0f, f = 1.0f, a = p.amp;
         float reach = fabsf(zi);
 #pragma unroll
         for (int c = 0; c < VEC; c++) reach = fmaxf(reach, fabsf(xi[c]));
-        if (FAST && p.fmax * reach < NZ_TAB_LIMIT) {
+        if (FAST && SHAPE != NZ_SHAPE_FBM && p.fmax * reach < NZ_TAB_LIMIT) {
+            // tolerance mode, shaped: |2 rectify(130 n) - 1| = |130 n| up to the roundings the strict form adds
+            for (int i = 0; i < p.octaves; i++) {
+                const float zV = f * zi;
+#pragma unroll
+                for (int c = 0; c < VEC; c++)
+                    shape_fold<SHAPE>(t[c], w[c], a, fabsf(130.0f * snoise2_tab_fast(f * xi[c], zV, s_t1, s_t2f)), rp);
+                detune += p.detune_rate;
+                f *= (p.stepdown - detune);
+                a *= p.G;
+            }
+        } else if (FAST && p.fmax * reach < NZ_TAB_LIMIT) {
             float bias = 0.0f;  // the octaves' 0.5 a (wave-uniform)
             for (int i = 0; i < p.octaves; i++) {
                 const float zV = f * zi, a65 = 65.0f * a;
@@ -584,7 +621,7 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
 #pragma unroll
                 for (int c = 0; c < VEC; c++) {
                     float xV = f * xi[c];
-                    t[c] += a * rectify_half(snoise2_tab(xV, zV, s_t1, s_t2));
+                    octave_add<SHAPE>(t[c], w[c], a, rectify_half(snoise2_tab(xV, zV, s_t1, s_t2)), rp);
                 }
                 detune += p.detune_rate;
                 f *= (p.stepdown - detune);
@@ -602,11 +639,11 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
                 }
                 if (!FAST && big < NZ_TAB_LIMIT) {  // (tolerance mode: beyond the tables' range the strict direct form)
 #pragma unroll
-                    for (int c = 0; c < VEC; c++) t[c] += a * rectify_half(snoise2_tab(xV[c], zV, s_t1, s_t2));
+                    for (int c = 0; c < VEC; c++) octave_add<SHAPE>(t[c], w[c], a, rectify_half(snoise2_tab(xV[c], zV, s_t1, s_t2)), rp);
                 } else {
                     asm volatile("; direct evaluation" ::: "memory");
 #pragma unroll
-                    for (int c = 0; c < VEC; c++) t[c] += a * rectify(snoise2(xV[c], zV));
+                    for (int c = 0; c < VEC; c++) octave_add<SHAPE>(t[c], w[c], a, rectify(snoise2(xV[c], zV)), rp);
                 }
                 detune += p.detune_rate;
                 f *= (p.stepdown - detune);
@@ -703,10 +740,11 @@ __device__ __forceinline__ float cellular_rect_tab(float Px, float Py, const int
     return rectify(F1) * rectify(F2);
 }
 
-template <int BASIS, int VEC>
+template <int BASIS, int VEC, int SHAPE>
 __global__ __launch_bounds__(256) void fractal_tab2_kernel(float *__restrict__ dst, int rows, int cols, int pitch,
-                                                          int blocks_per_row, nz_fractal_params p,
-                                                          const int *__restrict__ t1g, const float2 *__restrict__ t2g) {
+                                                          int blocks_per_row, nz_fractal_kparams p,
+                                                          const int *__restrict__ t1g, const float2 *__restrict__ t2g,
+                                                          nz_ridge_params rp) {
     __shared__ int s_t1[NZ_TB1_N];
     __shared__ float2 s_t2[NZ_TB2_N];
     for (int i = threadIdx.x; i < NZ_TB1_N; i += 256) s_t1[i] = t1g[i];
@@ -723,9 +761,9 @@ __global__ __launch_bounds__(256) void fractal_tab2_kernel(float *__restrict__ d
     int zend = min(rows, (by + 1) * p.rows_per_wg);
     for (int z = by * p.rows_per_wg; z < zend; z++) {
         float zi = ((float)z + p.posz) / p.noise_size;
-        float t[VEC];
+        float t[VEC], w[VEC];
 #pragma unroll
-        for (int c = 0; c < VEC; c++) t[c] = 0.0f;
+        for (int c = 0; c < VEC; c++) t[c] = 0.0f, w[c] = 1.0f;
         float detune = 0.0f, f = 1.0f, a = p.amp;
         float reach = fabsf(zi);
 #pragma unroll
@@ -736,8 +774,9 @@ __global__ __launch_bounds__(256) void fractal_tab2_kernel(float *__restrict__ d
 #pragma unroll
                 for (int c = 0; c < VEC; c++) {
                     float xV = f * xi[c];
-                    t[c] += a * (BASIS == NZ_NOISE_PERLIN ? rectify(cnoise2_tab(xV, zV, s_t1, s_t2))
-                                                          : cellular_rect_tab(xV, zV, s_t1, s_t2));
+                    octave_add<SHAPE>(t[c], w[c], a,
+                                      BASIS == NZ_NOISE_PERLIN ? rectify(cnoise2_tab(xV, zV, s_t1, s_t2))
+                                                               : cellular_rect_tab(xV, zV, s_t1, s_t2), rp);
                 }
                 detune += p.detune_rate;
                 f *= (p.stepdown - detune);
@@ -758,7 +797,7 @@ __global__ __launch_bounds__(256) void fractal_tab2_kernel(float *__restrict__ d
                         asm volatile("; direct evaluation" ::: "memory");
                         nv = BASIS == NZ_NOISE_PERLIN ? rectify(cnoise2(xV, zV)) : cellular_rect(xV, zV);
                     }
-                    t[c] += a * nv;
+                    octave_add<SHAPE>(t[c], w[c], a, nv, rp);
                 }
                 detune += p.detune_rate;
                 f *= (p.stepdown - detune);
@@ -860,10 +899,11 @@ __device__ __forceinline__ float snoise3_tab(float vx, float vy, float vz, const
     return 42.0f * (acc[0] + acc[1] + acc[2] + acc[3]);
 }
 
-template <int BASIS, int VEC>
+template <int BASIS, int VEC, int SHAPE>
 __global__ __launch_bounds__(256) void fractal_tab3_kernel(float *__restrict__ dst, int rows, int cols, int pitch,
-                                                          int blocks_per_row, nz_fractal_params p,
-                                                          const int *__restrict__ p3g, const float4 *__restrict__ g3g) {
+                                                          int blocks_per_row, nz_fractal_kparams p,
+                                                          const int *__restrict__ p3g, const float4 *__restrict__ g3g,
+                                                          nz_ridge_params rp) {
     __shared__ int s_p[NZ_P3_N];
     __shared__ float4 s_g[NZ_G3_N];
     for (int i = threadIdx.x; i < NZ_P3_N; i += 256) s_p[i] = p3g[i];
@@ -889,6 +929,9 @@ __global__ __launch_bounds__(256) void fractal_tab3_kernel(float *__restrict__ d
         }
         // the rotation shrinks |x|, |z| (factor <= 1.16 on x + z), so the 2-D limit keeps the lattice in range
         const bool small_row = p.fmax * reach < NZ_TAB_LIMIT;
+        float w[VEC];  // (ridged)
+#pragma unroll
+        for (int c = 0; c < VEC; c++) w[c] = 1.0f;
         for (int i = 0; i < p.octaves; i++) {
             float zV = f * zi;
 #pragma unroll
@@ -904,7 +947,7 @@ __global__ __launch_bounds__(256) void fractal_tab3_kernel(float *__restrict__ d
                     asm volatile("; direct evaluation" ::: "memory");  // a real branch, never if-converted
                     nv = BASIS == NZ_NOISE_DOMAIN_ROTATED_PERLIN ? cnoise3(xr, zr, yr) : snoise3(xr, zr, yr);
                 }
-                t[c] += a * rectify(nv);
+                octave_add<SHAPE>(t[c], w[c], a, rectify(nv), rp);
             }
             detune += p.detune_rate;
             f *= (p.stepdown - detune);
@@ -919,11 +962,11 @@ __global__ __launch_bounds__(256) void fractal_tab3_kernel(float *__restrict__ d
 constexpr int FR_THREADS = 256;
 
 // FractalGenerator.NoiseValue (Fractal.cs:114-131) for VEC consecutive cells of one row.
-template <int BASIS, int VEC>
+template <int BASIS, int VEC, int SHAPE>
 __global__ __launch_bounds__(FR_THREADS) void fractal_kernel(float *__restrict__ dst, int rows, int cols,
                                                             int pitch, int blocks_per_row,
-                                                            nz_fractal_params p,
-                                                            const float2 *__restrict__ rgrad) {
+                                                            nz_fractal_kparams p,
+                                                            const float2 *__restrict__ rgrad, nz_ridge_params rp) {
     constexpr bool USES_TAB = BASIS == NZ_NOISE_PERIODIC_PERLIN || BASIS == NZ_NOISE_ROTATED_SIMPLEX;
     __shared__ float2 s_tab[USES_TAB ? NZ_PSR_T2 : 1];
     __shared__ int s_t1[USES_TAB ? NZ_PSR_T1 : 1];
@@ -952,9 +995,9 @@ __global__ __launch_bounds__(FR_THREADS) void fractal_kernel(float *__restrict__
     int zend = min(rows, (by + 1) * p.rows_per_wg);
     for (int z = by * p.rows_per_wg; z < zend; z++) {
         float zi = ((float)z + p.posz) / p.noise_size;
-        float t[VEC];
+        float t[VEC], w[VEC];
 #pragma unroll
-        for (int c = 0; c < VEC; c++) t[c] = 0.0f;
+        for (int c = 0; c < VEC; c++) t[c] = 0.0f, w[c] = 1.0f;
         float detune = 0.0f, f = 1.0f, a = p.amp;
         for (int i = 0; i < p.octaves; i++) {
             float zV = f * zi;
@@ -965,19 +1008,19 @@ __global__ __launch_bounds__(FR_THREADS) void fractal_kernel(float *__restrict__
                 const int nowrap = __builtin_amdgcn_readfirstlane((xr + zr + 3.5f < 1000.0f ? 1 : 0) | (zr + 3.0f < 100.0f ? 2 : 0));
                 if (nowrap == 3) {
 #pragma unroll
-                    for (int c = 0; c < VEC; c++) t[c] += a * rectify(psrnoise2<false, false>(f * xi[c], zV, tabs));
+                    for (int c = 0; c < VEC; c++) octave_add<SHAPE>(t[c], w[c], a, rectify(psrnoise2<false, false>(f * xi[c], zV, tabs)), rp);
                 } else if (nowrap == 1) {
 #pragma unroll
-                    for (int c = 0; c < VEC; c++) t[c] += a * rectify(psrnoise2<false, true>(f * xi[c], zV, tabs));
+                    for (int c = 0; c < VEC; c++) octave_add<SHAPE>(t[c], w[c], a, rectify(psrnoise2<false, true>(f * xi[c], zV, tabs)), rp);
                 } else {
 #pragma unroll
-                    for (int c = 0; c < VEC; c++) t[c] += a * noise_value<BASIS>(f * xi[c], zV, tabs);
+                    for (int c = 0; c < VEC; c++) octave_add<SHAPE>(t[c], w[c], a, noise_value<BASIS>(f * xi[c], zV, tabs), rp);
                 }
             } else {
 #pragma unroll
                 for (int c = 0; c < VEC; c++) {
                     float xV = f * xi[c];
-                    t[c] += a * noise_value<BASIS>(xV, zV, tabs);
+                    octave_add<SHAPE>(t[c], w[c], a, noise_value<BASIS>(xV, zV, tabs), rp);
                 }
             }
             detune += p.detune_rate;
@@ -1005,7 +1048,7 @@ __global__ __launch_bounds__(FR_THREADS) void fractal_kernel(float *__restrict__
     }
 }
 
-template <int BASIS, int VEC>
+template <int BASIS, int VEC, int SHAPE>
 int32_t launch_basis(hipStream_t s, float *dst, int rows, int cols, int pitch, const nz_fractal_params &p,
                      const float *d_rgrad, int count) {
     int per_block = FR_THREADS * VEC;
@@ -1015,29 +1058,16 @@ int32_t launch_basis(hipStream_t s, float *dst, int rows, int cols, int pitch, c
         nz_set_error("fractal grid too large");
         return NZ_ERR_INVALID;
     }
-    NZ_LAUNCH((fractal_kernel<BASIS, VEC>), dim3((unsigned)blocks, count), dim3(FR_THREADS), 0, s, dst, rows,
-                       cols, pitch, bpr, p, reinterpret_cast<const float2 *>(d_rgrad));
+    NZ_LAUNCH((fractal_kernel<BASIS, VEC, SHAPE>), dim3((unsigned)blocks, count), dim3(FR_THREADS), 0, s, dst, rows,
+                       cols, pitch, bpr, static_cast<const nz_fractal_kparams &>(p), reinterpret_cast<const float2 *>(d_rgrad), p.ridge);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
 
-}  // namespace
-
-int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
-                          const nz_fractal_params &p_in, const float *d_rgrad, const void *d_simplex, int count,
-                          size_t bstride, const int32_t *positions) {
-    if (count < 1) return NZ_OK;
-    nz_fractal_params p = p_in;
-    p.positions = positions;
-    p.bstride = count > 1 || positions ? bstride : 0;
-    // 4 rows per workgroup amortise the table staging on big grids (1 / 2 / 4 / 8 / 16 rows: 0.285 / 0.278 / 0.277 /
-    // 0.281 / 0.292 ms for the metric's 4096^2 simplex plane); a small grid gets more, shorter workgroups (the launch
-    // lasts as long as one workgroup's rows)
-    p.rows_per_wg = 4;
-    {
-        long long wg_per_row = (cols + 511) / 512;
-        while (p.rows_per_wg > 1 && wg_per_row * ((rows + p.rows_per_wg - 1) / p.rows_per_wg) * count < 2048) p.rows_per_wg >>= 1;
-    }
+// the kernel choice of nz_launch_fractal for one octave shape (p: complete, rows_per_wg set)
+template <int SHAPE>
+int32_t launch_shaped(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch, const nz_fractal_params &p,
+                      const float *d_rgrad, const void *d_simplex, int count) {
     constexpr int use_tab = 1;  // (the direct kernels below serve Sin / psrnoise and every basis beyond its tables' range)
     if (noiseType == NZ_NOISE_SIMPLEX && use_tab && d_simplex) {
 #ifndef NZ_FT_VEC
@@ -1049,11 +1079,11 @@ int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, in
         const int *t1 = reinterpret_cast<const int *>(d_simplex);
         const float4 *t2 = reinterpret_cast<const float4 *>(t1 + NZ_T1_N);
         if (nz_tls_float_mode >= NZ_FLOAT_FAST)
-            NZ_LAUNCH((fractal_simplex_tab_kernel<VEC, true>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows, cols,
-                      pitch, bpr, p, t1, t2);
+            NZ_LAUNCH((fractal_simplex_tab_kernel<VEC, true, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows, cols,
+                      pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
         else
-            NZ_LAUNCH((fractal_simplex_tab_kernel<VEC, false>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows, cols,
-                      pitch, bpr, p, t1, t2);
+            NZ_LAUNCH((fractal_simplex_tab_kernel<VEC, false, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows, cols,
+                      pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
         NZ_HIP(hipGetLastError());
         return NZ_OK;
     }
@@ -1073,14 +1103,14 @@ int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, in
             constexpr int V = NZ_TAB2_VEC_PERLIN;
             int bpr = (cols + 256 * V - 1) / (256 * V);
             long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
-            NZ_LAUNCH((fractal_tab2_kernel<NZ_NOISE_PERLIN, V>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows,
-                               cols, pitch, bpr, p, t1, t2);
+            NZ_LAUNCH((fractal_tab2_kernel<NZ_NOISE_PERLIN, V, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows,
+                               cols, pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
         } else {
             constexpr int V = NZ_TAB2_VEC_CELLULAR;
             int bpr = (cols + 256 * V - 1) / (256 * V);
             long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
-            NZ_LAUNCH((fractal_tab2_kernel<NZ_NOISE_CELLULAR, V>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst,
-                               rows, cols, pitch, bpr, p, t1, t2);
+            NZ_LAUNCH((fractal_tab2_kernel<NZ_NOISE_CELLULAR, V, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst,
+                               rows, cols, pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
         }
         NZ_HIP(hipGetLastError());
         return NZ_OK;
@@ -1098,34 +1128,67 @@ int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, in
         int bpr = (cols + 256 * V3 - 1) / (256 * V3);
         long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
         if (noiseType == NZ_NOISE_DOMAIN_ROTATED_PERLIN)
-            NZ_LAUNCH((fractal_tab3_kernel<NZ_NOISE_DOMAIN_ROTATED_PERLIN, V3>), dim3((unsigned)blocks, count), dim3(256), 0,
-                               s, dst, rows, cols, pitch, bpr, p, p3, g3);
+            NZ_LAUNCH((fractal_tab3_kernel<NZ_NOISE_DOMAIN_ROTATED_PERLIN, V3, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0,
+                               s, dst, rows, cols, pitch, bpr, static_cast<const nz_fractal_kparams &>(p), p3, g3, p.ridge);
         else
-            NZ_LAUNCH((fractal_tab3_kernel<NZ_NOISE_DOMAIN_ROTATED_SIMPLEX, V3>), dim3((unsigned)blocks, count), dim3(256), 0,
-                               s, dst, rows, cols, pitch, bpr, p, p3, g3 + NZ_G3_N);
+            NZ_LAUNCH((fractal_tab3_kernel<NZ_NOISE_DOMAIN_ROTATED_SIMPLEX, V3, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0,
+                               s, dst, rows, cols, pitch, bpr, static_cast<const nz_fractal_kparams &>(p), p3, g3 + NZ_G3_N, p.ridge);
         NZ_HIP(hipGetLastError());
         return NZ_OK;
     }
     switch (noiseType) {
-        case NZ_NOISE_SIN: return launch_basis<NZ_NOISE_SIN, 4>(s, dst, rows, cols, pitch, p, d_rgrad, count);
-        case NZ_NOISE_PERLIN: return launch_basis<NZ_NOISE_PERLIN, 2>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+        case NZ_NOISE_SIN: return launch_basis<NZ_NOISE_SIN, 4, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+        case NZ_NOISE_PERLIN: return launch_basis<NZ_NOISE_PERLIN, 2, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
 #ifndef NZ_PSR_VEC
 #define NZ_PSR_VEC 4  // cells per thread: 0.492 / 0.518 / 0.464 ms with 1 / 2 / 4 (4096^2, 13 octaves)
 #endif
         case NZ_NOISE_PERIODIC_PERLIN:
-            return launch_basis<NZ_NOISE_PERIODIC_PERLIN, NZ_PSR_VEC>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+            return launch_basis<NZ_NOISE_PERIODIC_PERLIN, NZ_PSR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
 #ifndef NZ_FR_VEC
 #define NZ_FR_VEC 2
 #endif
-        case NZ_NOISE_SIMPLEX: return launch_basis<NZ_NOISE_SIMPLEX, NZ_FR_VEC>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+        case NZ_NOISE_SIMPLEX: return launch_basis<NZ_NOISE_SIMPLEX, NZ_FR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_ROTATED_SIMPLEX:
-            return launch_basis<NZ_NOISE_ROTATED_SIMPLEX, NZ_PSR_VEC>(s, dst, rows, cols, pitch, p, d_rgrad, count);
-        case NZ_NOISE_CELLULAR: return launch_basis<NZ_NOISE_CELLULAR, 2>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+            return launch_basis<NZ_NOISE_ROTATED_SIMPLEX, NZ_PSR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+        case NZ_NOISE_CELLULAR: return launch_basis<NZ_NOISE_CELLULAR, 2, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_DOMAIN_ROTATED_PERLIN:
-            return launch_basis<NZ_NOISE_DOMAIN_ROTATED_PERLIN, 1>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+            return launch_basis<NZ_NOISE_DOMAIN_ROTATED_PERLIN, 1, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_DOMAIN_ROTATED_SIMPLEX:
-            return launch_basis<NZ_NOISE_DOMAIN_ROTATED_SIMPLEX, 1>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+            return launch_basis<NZ_NOISE_DOMAIN_ROTATED_SIMPLEX, 1, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
     }
     nz_set_error("unknown noise type %d", noiseType);
     return NZ_ERR_INVALID;
 }
+
+}  // namespace
+
+#ifdef NZ_FRACTAL_SHAPED_TU
+int32_t nz_launch_fractal_shaped(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
+                                 const nz_fractal_params &p, const float *d_rgrad, const void *d_simplex, int count) {
+    switch (p.shape) {
+        case NZ_SHAPE_BILLOW: return launch_shaped<NZ_SHAPE_BILLOW>(s, noiseType, dst, rows, cols, pitch, p, d_rgrad, d_simplex, count);
+        case NZ_SHAPE_RIDGED: return launch_shaped<NZ_SHAPE_RIDGED>(s, noiseType, dst, rows, cols, pitch, p, d_rgrad, d_simplex, count);
+    }
+    nz_set_error("unknown octave shape %d", p.shape);
+    return NZ_ERR_INVALID;
+}
+#else
+int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
+                          const nz_fractal_params &p_in, const float *d_rgrad, const void *d_simplex, int count,
+                          size_t bstride, const int32_t *positions) {
+    if (count < 1) return NZ_OK;
+    nz_fractal_params p = p_in;
+    p.positions = positions;
+    p.bstride = count > 1 || positions ? bstride : 0;
+    // 4 rows per workgroup amortise the table staging on big grids (1 / 2 / 4 / 8 / 16 rows: 0.285 / 0.278 / 0.277 /
+    // 0.281 / 0.292 ms for the metric's 4096^2 simplex plane); a small grid gets more, shorter workgroups (the launch
+    // lasts as long as one workgroup's rows)
+    p.rows_per_wg = 4;
+    {
+        long long wg_per_row = (cols + 511) / 512;
+        while (p.rows_per_wg > 1 && wg_per_row * ((rows + p.rows_per_wg - 1) / p.rows_per_wg) * count < 2048) p.rows_per_wg >>= 1;
+    }
+    if (p.shape == NZ_SHAPE_FBM) return launch_shaped<NZ_SHAPE_FBM>(s, noiseType, dst, rows, cols, pitch, p, d_rgrad, d_simplex, count);
+    return nz_launch_fractal_shaped(s, noiseType, dst, rows, cols, pitch, p, d_rgrad, d_simplex, count);
+}
+#endif

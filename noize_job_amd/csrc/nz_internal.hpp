@@ -115,7 +115,8 @@ struct nz_kernel_taps {
     int ksize;
 };
 
-struct nz_fractal_params {
+// what every fractal kernel takes by value (64 bytes: the kernel argument offsets behind it are part of the tuned code)
+struct nz_fractal_kparams {
     float posx, posz;     // (float)xpos, (float)(zpos + first row)
     float noise_size;     // (float)NoiseSize
     float G;              // exp2f(-hurst), host libm
@@ -128,6 +129,14 @@ struct nz_fractal_params {
     const int32_t *positions = nullptr;
     size_t bstride = 0;
     int rows_per_wg = 8;  // rows one workgroup walks through (8 amortises the table staging; fewer for small grids)
+    int shape = 0;        // octave shape (enum nz_fractal_shape; the kernels have it as a template argument), 0 = fBm
+};
+// the ridged shape's two constants: a trailing kernel argument, so the shape-0 kernels keep their argument layout
+struct nz_ridge_params {
+    float offset = 1.0f, gain = 2.0f;
+};
+struct nz_fractal_params : nz_fractal_kparams {
+    nz_ridge_params ridge;  // NZ_SHAPE_RIDGED only
 };
 
 // plane geometry handed to every stencil kernel: clamp rows are the global border seen from the
@@ -212,6 +221,9 @@ int32_t nz_fractal_rows(nz_ctx *ctx, hipStream_t stream, int noiseType, float *d
 int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
                           const nz_fractal_params &p, const float *d_rgrad, const void *d_simplex, int count = 1,
                           size_t bstride = 0, const int32_t *positions = nullptr);
+// the billow / ridged kernels (nz_fractal_shaped.hip); p complete, rows_per_wg / positions / bstride included
+int32_t nz_launch_fractal_shaped(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
+                                 const nz_fractal_params &p, const float *d_rgrad, const void *d_simplex, int count);
 
 int nz_conv_max_fused(int ksize);
 // T fused applications of (X pass, Z pass) src -> dst on rows [or0, or1)

@@ -47,7 +47,8 @@ static float calc_fractal_norm(float hurst, int octaves) {
 static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, float *dst, int rows, int cols, int pitch,
                             float hurst,
                             float amp, float stepdown, float detune, int octaves, int xpos, int zpos_first_row,
-                            int noiseSize, int count = 1, size_t bstride = 0, const int32_t *positions = nullptr) {
+                            int noiseSize, int count = 1, size_t bstride = 0, const int32_t *positions = nullptr,
+                            int shape = NZ_SHAPE_FBM, float ridgeOffset = 1.0f, float ridgeGain = 2.0f) {
     NZ_REQUIRE(dst, "src is NULL");
     NZ_REQUIRE(noiseType >= 0 && noiseType <= NZ_NOISE_DOMAIN_ROTATED_SIMPLEX, "unknown noise type %d", noiseType);
     NZ_REQUIRE(octaves >= 0, "octaves < 0");
@@ -62,6 +63,9 @@ static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, floa
     p.detune_rate = detune;
     p.norm = calc_fractal_norm(hurst, octaves);
     p.octaves = octaves;
+    p.shape = shape;
+    p.ridge.offset = ridgeOffset;
+    p.ridge.gain = ridgeGain;
     // largest |f| of FractalGenerator.NoiseValue's recurrence (Fractal.cs:121-127): lets a kernel decide once
     // per row whether every octave stays inside the range its lattice tables cover
     p.fmax = 0.0f;
@@ -396,6 +400,45 @@ extern "C" int32_t nz_fractal_stripe(nz_ctx *ctx, int32_t noiseType, float *buf,
         NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, buf + (size_t)st->own0 * pitch, rows, st->cols, pitch, hurst,
                             startingAmplitude, stepdown, detuneRate, octaves, xpos, zpos + st->grow0 + st->own0,
                             noiseSize));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+static int32_t check_shape(int32_t shape) {
+    NZ_REQUIRE(shape >= NZ_SHAPE_FBM && shape <= NZ_SHAPE_RIDGED, "unknown octave shape %d", shape);
+    return NZ_OK;
+}
+
+// nz_fractal / nz_fractal_stripe with an octave shape (new-framework feature, enum nz_fractal_shape)
+extern "C" int32_t nz_fractal_shaped(nz_ctx *ctx, int32_t noiseType, float *src, int32_t resolution, float hurst,
+                                     float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                                     int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                                     float ridgeGain, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_res(resolution));
+    NZ_TRY(check_shape(shape));
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, src, resolution, resolution, resolution, hurst, startingAmplitude,
+                        stepdown, detuneRate, octaves, xpos, zpos, noiseSize, 1, 0, nullptr, shape, ridgeOffset,
+                        ridgeGain));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fractal_shaped_stripe(nz_ctx *ctx, int32_t noiseType, float *buf, const nz_stripe *st, float hurst,
+                                            float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                                            int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape,
+                                            float ridgeOffset, float ridgeGain, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(buf, "buf is NULL");
+    NZ_TRY(check_shape(shape));
+    int pitch = st->pitch > 0 ? st->pitch : st->cols;
+    int rows = st->own1 - st->own0;
+    if (rows > 0) {
+        NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, buf + (size_t)st->own0 * pitch, rows, st->cols, pitch, hurst,
+                            startingAmplitude, stepdown, detuneRate, octaves, xpos, zpos + st->grow0 + st->own0,
+                            noiseSize, 1, 0, nullptr, shape, ridgeOffset, ridgeGain));
     }
     return nz_ctx_finish(ctx, out);
 }
@@ -775,6 +818,23 @@ extern "C" int32_t nz_fractal_batch(nz_ctx *ctx, int32_t noiseType, float *data,
     nz_ctx_arm_last_launch(ctx);
     NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, data, resolution, resolution, resolution, hurst, startingAmplitude,
                         stepdown, detuneRate, octaves, 0, 0, noiseSize, count, (size_t)resolution * resolution, positions));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fractal_shaped_batch(nz_ctx *ctx, int32_t noiseType, float *data, int32_t resolution,
+                                           int32_t count, const int32_t *positions, float hurst, float startingAmplitude,
+                                           float stepdown, float detuneRate, int32_t octaves, int32_t noiseSize,
+                                           int32_t shape, float ridgeOffset, float ridgeGain, nz_handle dep,
+                                           nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    NZ_REQUIRE(positions, "positions is NULL");
+    NZ_TRY(check_shape(shape));
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, data, resolution, resolution, resolution, hurst, startingAmplitude,
+                        stepdown, detuneRate, octaves, 0, 0, noiseSize, count, (size_t)resolution * resolution, positions,
+                        shape, ridgeOffset, ridgeGain));
     return nz_ctx_finish(ctx, out);
 }
 

@@ -238,6 +238,34 @@ class NoiseStage : public PipelineStage {
     }
 };
 
+// new-framework: NoiseStage with an octave shape (enum nz_fractal_shape); Fbm gives the bits of NoiseStage.  The stock-list
+// fast paths compare the exact type, so a shaped stage never runs there as plain fBm.
+enum class FractalShape { Fbm, Billow, Ridged };
+
+class ShapedNoiseStage : public NoiseStage {
+  public:
+    using NoiseStage::NoiseStage;
+    FractalShape shape = FractalShape::Ridged;
+    float ridgeOffset = 1.f, ridgeGain = 2.f;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        nz_handle h = 0;
+        if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_fractal_shaped_batch(ctx, (int)noiseType, b->data->ptr, b->resolution, b->count, b->positions, hurst,
+                                          startingAmplitude, stepdown, detuneRate, octaves, noiseSize, (int)shape,
+                                          ridgeOffset, ridgeGain, dependency.id, &h),
+                  "nz_fractal_shaped_batch");
+            jobHandle = done(h);
+            return;
+        }
+        check(nz_fractal_shaped(ctx, (int)noiseType, d->data->ptr, d->resolution, hurst, startingAmplitude, stepdown,
+                                detuneRate, octaves, d->xpos, d->zpos, noiseSize, (int)shape, ridgeOffset, ridgeGain,
+                                dependency.id, &h),
+              "nz_fractal_shaped");
+        jobHandle = done(h);
+    }
+};
+
 class TmpStage : public PipelineStage {  // stages that own one scratch plane
   public:
     using PipelineStage::PipelineStage;
@@ -967,7 +995,8 @@ inline bool stockListParams(const std::vector<PipelineStage *> &stages, nz_terra
 }
 
 inline bool BasePipeline::RegeneratesItsTile() const {
-    return !stage_instances.empty() && typeid(*stage_instances[0]) == typeid(NoiseStage);
+    // a NoiseStage or one derived from it (ShapedNoiseStage), as isinstance in the Python host and `is` in the C# one
+    return !stage_instances.empty() && dynamic_cast<NoiseStage *>(stage_instances[0]) != nullptr;
 }
 
 // ---- one large grid over the GPUs of a node (new-framework feature; include/noize_hip.h, nz_comm.cpp) -------------------

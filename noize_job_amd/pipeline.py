@@ -34,6 +34,12 @@ class FractalNoise(enum.IntEnum):  # Noise/NoiseStage.cs:15-24
     DomainRotatedSimplex = 7
 
 
+class FractalShape(enum.IntEnum):  # new-framework: the octave shape of ShapedNoiseStage (enum nz_fractal_shape)
+    Fbm = 0
+    Billow = 1
+    Ridged = 2
+
+
 class KernelFilterType(enum.IntEnum):  # Filter/Kernel/KernelJob.cs:79-94
     Gauss9_S1 = 0
     Gauss7_S1 = 1
@@ -298,6 +304,33 @@ class NoiseStage(PipelineStage):  # Noise/NoiseStage.cs:13-61
         self.jobHandle = self.ctx.call("nz_fractal", int(self.noiseType), d.data.ptr, d.resolution, self.hurst,
                                        self.startingAmplitude, self.stepdown, self.detuneRate, self.octaves, d.xpos,
                                        d.zpos, self.noiseSize, dep=dependency)
+
+
+class ShapedNoiseStage(NoiseStage):
+    """New-framework: NoiseStage with an octave shape -- FractalShape.Billow (|2v - 1| per octave) or FractalShape.Ridged
+    (Musgrave's ridged multifractal, (ridgeOffset - |2v - 1|)^2 weighted by the previous octave through ridgeGain).  Fbm
+    gives the bits of NoiseStage.  A subclass, so the stock-list fast paths (exact type) never take it for plain fBm."""
+
+    def __init__(self, ctx, noiseType=FractalNoise.Sin, hurst=0.0, startingAmplitude=1.0, octaves=1, stepdown=2.0,
+                 detuneRate=0.0, noiseSize=1000, shape=FractalShape.Ridged, ridgeOffset=1.0, ridgeGain=2.0):
+        super().__init__(ctx, noiseType, hurst, startingAmplitude, octaves, stepdown, detuneRate, noiseSize)
+        self.shape = shape
+        self.ridgeOffset = ridgeOffset
+        self.ridgeGain = ridgeGain
+
+    def Schedule(self, requirements, dependency):
+        self.CheckRequirements(GeneratorData, requirements)
+        d = requirements.data
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_fractal_shaped_batch", int(self.noiseType), d.data.ptr, d.resolution,
+                                           d.count, d.positions.ptr, self.hurst, self.startingAmplitude, self.stepdown,
+                                           self.detuneRate, self.octaves, self.noiseSize, int(self.shape),
+                                           self.ridgeOffset, self.ridgeGain, dep=dependency)
+            return
+        self.jobHandle = self.ctx.call("nz_fractal_shaped", int(self.noiseType), d.data.ptr, d.resolution, self.hurst,
+                                       self.startingAmplitude, self.stepdown, self.detuneRate, self.octaves, d.xpos,
+                                       d.zpos, self.noiseSize, int(self.shape), self.ridgeOffset, self.ridgeGain,
+                                       dep=dependency)
 
 
 class KernelFilterStage(PipelineStage):  # Filter/KernelFilterStage.cs:13-51
