@@ -249,14 +249,9 @@ int32_t launch_stream(hipStream_t s, const float *src, float *dst, const nz_geom
                            (uintptr_t)(g.bstride * 4);
     const int aligned = (bits & 7) == 0;
     const dim3 grid((unsigned)(nstrips * nseg), g.count);
-    const bool fast = nz_tls_float_mode >= NZ_FLOAT_FAST;
-#define NZ_CSL(U, F) NZ_LAUNCH((conv_stream_kernel<KS, T, U, F>), grid, dim3(64), 0, s, src, dst, g, k, S, nstrips, aligned)
-    if (k.factor == 1.0f) {
-        if (fast) NZ_CSL(true, true); else NZ_CSL(true, false);
-    } else {
-        if (fast) NZ_CSL(false, true); else NZ_CSL(false, false);
-    }
-#undef NZ_CSL
+    nz_with_unit_fast(k, [&](auto unit, auto fast) {
+        NZ_LAUNCH((conv_stream_kernel<KS, T, unit, fast>), grid, dim3(64), 0, s, src, dst, g, k, S, nstrips, aligned);
+    });
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
@@ -266,7 +261,7 @@ int32_t launch_stream(hipStream_t s, const float *src, float *dst, const nz_geom
 // largest T the streaming form holds (0: this tap count has none)
 int nz_conv_stream_max(int ksize) { return ksize == 3 || ksize == 5 ? 6 : 0; }
 
-// NZ_CONV_STREAM=1: the streaming form for grids of 40 M cells and more; 2: every size (test matrix); default 0: never.
+// NZ_CONV_STREAM=1 (the default): the streaming form for grids of 40 M cells and more; 2: every size (test matrix); 0: never.
 // Measured against the tile kernels (chained at 4096^2, separate launches elsewhere), Gauss5 x17: 4096^2 0.228 against
 // 0.206 ms (a segment of ~50 rows spends a fifth of its steps filling the pipeline), 8192^2 0.743 against 0.767,
 // 16384^2 2.90 against 2.52, a 2048 x 16384 stripe 0.432 against 0.391: per output cell it executes 7 % fewer

@@ -272,14 +272,12 @@ __device__ __forceinline__ void spread_pool_step(float *pool, int res, int x, in
 // A pass cannot clear bits itself (its own class's bits are what the other threads cut their runs by, and the other
 // classes' bits are being set by it), and does not have to: a step that has stopped acting stays in its run and does
 // nothing there -- any SUPERSET of the acting steps cuts the walks into runs that give the row walk's values.
-#ifndef NZ_POOL_MASKS_NT
-#define NZ_POOL_MASKS_NT 256
-#endif
+constexpr int POOL_MASKS_NT = 256;  // threads per workgroup
 template <bool LIST>
-__global__ __launch_bounds__(NZ_POOL_MASKS_NT) void pool_masks_kernel(const float *__restrict__ pool, pool_masks pm, int res) {
+__global__ __launch_bounds__(POOL_MASKS_NT) void pool_masks_kernel(const float *__restrict__ pool, pool_masks pm, int res) {
     // a lane owns walk k of both z parities: rows z = 2k and 2k + 1 are neighbours in memory, one 8-byte load per column;
     // a workgroup's waves sit side by side in z, so every row is read in pieces of NT * 8 bytes
-    const int k = blockIdx.x * NZ_POOL_MASKS_NT + threadIdx.x, w = blockIdx.y;
+    const int k = blockIdx.x * POOL_MASKS_NT + threadIdx.x, w = blockIdx.y;
     const bool valid = k < pm.walks;  // (no early return: the wave's lanes count and number their entries together below)
     const int odd = k & 1, z = 2 * k;
     unsigned m0[2] = {0, 0}, m1[2] = {0, 0};  // xoff = 0: x = 64 w + odd + 2 b; xoff = 1: x = 64 w + 1 + odd + 2 b
@@ -395,10 +393,7 @@ __global__ __launch_bounds__(256) void pool_masks_clean_kernel(const float *__re
 }
 
 constexpr int PRT = 256;  // threads per workgroup: a pass is 50 tiny launches, 4x fewer workgroups dispatch faster
-#ifndef NZ_POOL_PR
-#define NZ_POOL_PR 8
-#endif
-constexpr int PR = NZ_POOL_PR;  // steps of a run whose loads are in flight together (all-wet 8192^2: 305 ms one step at a time, 212 with 8, 222 with 16: what is left is the ~1 us instruction stream of a step)
+constexpr int PR = 8;  // steps of a run whose loads are in flight together (all-wet 8192^2: 305 ms one step at a time, 212 with 8, 222 with 16: what is left is the ~1 us instruction stream of a step)
 // The one-lane-per-row form of the same pass (NZ_POOL_RUNS=0): the loads of PU consecutive steps are issued together,
 // ahead of the arithmetic, and the one carried cell travels in a register, so the walk pays one memory round trip per
 // PU steps.  Faster than the run form only where standing water covers most of the plane.
@@ -725,10 +720,7 @@ __global__ __launch_bounds__(CT) void map_range_partial_kernel(const float *__re
     const size_t stride = (size_t)gridDim.x * CT;
     if (vec) {
         const size_t n4 = n / 4;
-#ifndef NZ_MAP_RANGE_U
-#define NZ_MAP_RANGE_U 4
-#endif
-        constexpr int U = NZ_MAP_RANGE_U;  // 16-byte loads in flight per thread (rocprofv3, 4096^2: 4 -> 13.2 us, 8 -> 14.3; round 5's 28-instruction fold: 16.7)
+        constexpr int U = 4;  // 16-byte loads in flight per thread (rocprofv3, 4096^2: 4 -> 13.2 us, 8 -> 14.3; round 5's 28-instruction fold: 16.7)
         map_range_lane l{__builtin_inff(), -__builtin_inff(), 0ull};
         for (size_t i0 = (size_t)blockIdx.x * CT + threadIdx.x; i0 < n4; i0 += U * stride) {
             float4 t[U];
@@ -984,9 +976,9 @@ size_t nz_pool_automata_mask_words(int res) {
 int32_t nz_launch_pool_automata_masks(hipStream_t s, const float *pool, int res, unsigned *mask, int *ctl, int with_list) {
     if (res / 2 <= 0) return NZ_OK;
     const pool_masks pm = pool_masks_of(res, mask, ctl, with_list != 0);
-    const dim3 grid((unsigned)((pm.walks + NZ_POOL_MASKS_NT - 1) / NZ_POOL_MASKS_NT), (unsigned)pm.words);
-    if (with_list) hipLaunchKernelGGL(pool_masks_kernel<true>, grid, dim3(NZ_POOL_MASKS_NT), 0, s, pool, pm, res);
-    else hipLaunchKernelGGL(pool_masks_kernel<false>, grid, dim3(NZ_POOL_MASKS_NT), 0, s, pool, pm, res);
+    const dim3 grid((unsigned)((pm.walks + POOL_MASKS_NT - 1) / POOL_MASKS_NT), (unsigned)pm.words);
+    if (with_list) hipLaunchKernelGGL(pool_masks_kernel<true>, grid, dim3(POOL_MASKS_NT), 0, s, pool, pm, res);
+    else hipLaunchKernelGGL(pool_masks_kernel<false>, grid, dim3(POOL_MASKS_NT), 0, s, pool, pm, res);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

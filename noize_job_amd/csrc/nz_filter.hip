@@ -34,18 +34,12 @@ constexpr int TH = 64;       // LDS tile height, rows
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Workgroups are dealt round-robin to the 8 XCDs (blockIdx.x % 8), each with its own L2.  Giving XCD x the x-th
-// contiguous eighth of the tiles keeps tiles that share halo rows / columns on one L2 (NZ_XCD_REMAP=0: identity).
-#ifndef NZ_XCD_REMAP
-#define NZ_XCD_REMAP 1
-#endif
+// contiguous eighth of the tiles keeps tiles that share halo rows / columns on one L2.
 __device__ __forceinline__ int xcd_tile_index() {
     int bid = blockIdx.x;
-#if NZ_XCD_REMAP
     int nb = gridDim.x, q = nb >> 3, r = nb & 7;
     int x = bid & 7, k = bid >> 3;
-    bid = x * q + (x < r ? x : r) + k;
-#endif
-    return bid;
+    return x * q + (x < r ? x : r) + k;
 }
 
 __device__ __forceinline__ void tile_origin(const nz_geom &g, int OW, int OH, int &ox0, int &oz0) {
@@ -70,15 +64,10 @@ constexpr int RB = 8;  // rows per thread
 
 // bound_ctrl: the lane without a source reads 0 -- the value update_dpp(0, ...) left there, without the v_mov 0 that
 // initialised its destination (a VALU slot per shifted value: 4 of ~85 per row of the 5-tap X pass)
-#ifndef NZ_DPP_OLD
-#define NZ_DPP_OLD 0
-#endif
 __device__ __forceinline__ float dpp_prev(float v) {  // lane i <- lane i-1
-    if (NZ_DPP_OLD) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float dpp_next(float v) {  // lane i <- lane i+1
-    if (NZ_DPP_OLD) return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
     return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
 
@@ -108,16 +97,11 @@ __device__ unsigned long long *nz_probe_buf = nullptr;  // [workgroup][24]
 // 512-thread workgroups per CU (6 waves per SIMD, 80 VGPRs, one edge buffer of 32 KB each) so one workgroup's
 // load/store phase overlaps the others' VALU phases: 5 % faster than two workgroups at 121 VGPRs; the 7- and
 // 9-tap windows do not fit 80 registers without spilling and stay at two.
-#ifndef NZ_CONV5_NBUF
-#define NZ_CONV5_NBUF 1  // 2: double-buffered edge rows for the 5-tap kernel (one barrier per application, 64 KB of LDS: two workgroups per CU)
-#endif
-#ifndef NZ_CONV5_WAVES
-#define NZ_CONV5_WAVES 6
-#endif
+constexpr int conv_waves(int ks, int nt, int rbt) { return rbt < RB ? 4 : ks == 5 ? 6 : (nt >= 512 || ks >= 7) ? 4 : 6; }
 // edge-row buffers: two (one barrier per application) for the 3-tap kernel, one (two barriers) for the others -- see conv_tile.
-// (The small grids' shapes with two: Gauss5 x17 512^2 30.1 -> 29.5 us, 1024^2 47.8 -> 48.8, 2048^2 67.9 -> 76.9: one it stays.)
-constexpr int conv_nbuf(int o) { return (o == 2 && NZ_CONV5_NBUF == 2) ? 2 : (o >= 2 ? 1 : 2); }
-constexpr int conv_waves(int ks, int nt, int rbt) { return rbt < RB ? 4 : ks == 5 ? NZ_CONV5_WAVES : (nt >= 512 || ks >= 7) ? 4 : 6; }
+// (Two for the 5-tap kernel costs a resident workgroup: 64 KB of LDS.  The small grids' shapes with two: Gauss5 x17 512^2
+// 30.1 -> 29.5 us, 1024^2 47.8 -> 48.8, 2048^2 67.9 -> 76.9: one it stays.)
+constexpr int conv_nbuf(int o) { return o >= 2 ? 1 : 2; }
 
 // 16-byte accesses that other XCDs can see / that see other XCDs' stores while the kernel runs: `sc1` buffer loads and
 // stores (they bypass the CU's L1; the stores write through and leave the XCD's L2), 4-byte ones as agent-scope relaxed
@@ -781,14 +765,9 @@ int32_t launch_wide_nt(hipStream_t s, const float *src, float *dst, const nz_geo
     constexpr int WD_H = NT / 8;
     long long blocks = (long long)((g.cols + WD_W - 1) / WD_W) * ((g.or1 - g.or0 + WD_H - 1) / WD_H);
     int aligned = (g.pitch % 4 == 0) && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-    const bool fast = nz_tls_float_mode >= NZ_FLOAT_FAST;
-#define NZ_WD(U, F) NZ_LAUNCH((conv_wide_kernel<O, U, NT, F>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, aligned)
-    if (k.factor == 1.0f) {
-        if (fast) NZ_WD(true, true); else NZ_WD(true, false);
-    } else {
-        if (fast) NZ_WD(false, true); else NZ_WD(false, false);
-    }
-#undef NZ_WD
+    nz_with_unit_fast(k, [&](auto unit, auto fast) {
+        NZ_LAUNCH((conv_wide_kernel<O, unit, NT, fast>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, aligned);
+    });
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
@@ -801,13 +780,6 @@ int32_t launch_wide(hipStream_t s, const float *src, float *dst, const nz_geom &
     else return launch_wide_nt<O, 256>(s, src, dst, g, k);
 }
 
-#ifndef NZ_CONV_NT
-#define NZ_CONV_NT 256
-#endif
-#ifndef NZ_CONV_NT_WIDE
-#define NZ_CONV_NT_WIDE 512  // threads per workgroup for the 5-, 7- and 9-tap kernels: 128-row tiles (rows = NT / 4)
-#endif
-
 // Threads per workgroup = rows of the register tile / 4 at eight rows per thread.  The 5-, 7- and 9-tap kernels use 128-row
 // tiles (512 threads) where throughput counts; a SMALL grid -- a tile of the reference's own sizes (256 ... 1024^2), a stripe's
 // ghost-row window -- cannot fill the chip whatever the tile, and what it waits for is the latency of one workgroup's dependent
@@ -819,78 +791,95 @@ int32_t launch_wide(hipStream_t s, const float *src, float *dst, const nz_geom &
 // 117; 2816^2 127 against 131 and 3072^2 134 against 151.  Round 5, four rows per thread, chained from two launches on
 // (nz_stages.cpp): 2048^2 68, 2560^2 95, 3072^2 133 against 124 with the big tiles, 4096^2 221 against 188: from 7 M cells on the
 // big tiles stay.)
-#ifndef NZ_CONV_SMALL_NT
-#define NZ_CONV_SMALL_NT 512  // the 64-row tile of a small grid: NZ_CONV_SMALL_NT threads x NZ_CONV_SMALL_RB rows each
-#define NZ_CONV_SMALL_RB 4
-#endif
-static_assert(NZ_CONV_SMALL_NT / 32 * NZ_CONV_SMALL_RB == 64, "the hosts size a small grid's tiles as 64 rows");
+constexpr long long CONV_SMALL_CELLS = 7 * 1024 * 1024;
 // A TINY grid -- a tile of 256^2 ... 768^2 cells, at most a workgroup per CU -- goes one step further with the 5-tap kernel
 // (whose window needs two rows of a neighbouring block at most): 1024 threads x 2 rows, four waves per SIMD.  Gauss5 x17,
 // one 512^2 tile at a time: 256 x 8 rows 42.0 us, 512 x 4 rows 33.4 us, 1024 x 2 rows 30.9 us; at 2048^2 (several workgroups per
 // CU) 95.9 / 87.1 / 116 us.
-constexpr long long NZ_CONV_TINY_CELLS = 600 * 1024;
+constexpr long long CONV_TINY_CELLS = 600 * 1024;
 // (At 1024^2 the 1024-thread shape is faster by itself, 42.8 against 45.4 us, and slower in a tile's pipeline, 9 720 against 9 930
 // tiles/s: a 1024-thread workgroup cannot start beside the tail of the stage before.)
-static inline bool conv_tiny_grid(const nz_geom &g) { return (long long)g.cols * (g.or1 - g.or0) * g.count <= NZ_CONV_TINY_CELLS; }
-#ifndef NZ_CONV_SMALL_CELLS
-#define NZ_CONV_SMALL_CELLS (7 * 1024 * 1024)
-#endif
-static inline bool conv_small_grid(int ksize, const nz_geom &g) {
-    if (ksize < 5 || NZ_CONV_NT_WIDE <= 256) return false;
+
+// The register tile's shapes, NT threads x RBT rows per thread (NT / 32 * RBT rows x 128 columns): BIG 512 x 8 for 5, 7 and
+// 9 taps and 256 x 8 for 3, SMALL 512 x 4, TINY 1024 x 2 (5 taps only).
+enum conv_shape { CONV_BIG, CONV_SMALL, CONV_TINY };
+constexpr int CONV_SMALL_NT = 512, CONV_SMALL_RB = 4, CONV_TINY_NT = 1024, CONV_TINY_RB = 2;
+static_assert(CONV_SMALL_NT / 32 * CONV_SMALL_RB == 64 && CONV_TINY_NT / 32 * CONV_TINY_RB == 64,
+              "the hosts size a small grid's tiles as 64 rows (nz_conv_max_fused, the fusion caps of nz_stages.cpp)");
+
+static bool conv_small_grid(int ksize, const nz_geom &g) {
+    if (ksize < 5) return false;
     static const int env = getenv("NZ_CONV_SMALL") ? atoi(getenv("NZ_CONV_SMALL")) : 1;  // 0: never; 2: always (test matrix)
     if (env == 0) return false;
     if (env == 2) return true;
-    return (long long)g.cols * (g.or1 - g.or0) * g.count < (long long)NZ_CONV_SMALL_CELLS;
+    return (long long)g.cols * (g.or1 - g.or0) * g.count < CONV_SMALL_CELLS;
+}
+// the one rule that picks a launch's shape: launch_fused, launch_chain and nz_conv_chain_items go through it
+static conv_shape conv_shape_of(int ksize, const nz_geom &g) {
+    if (!conv_small_grid(ksize, g)) return CONV_BIG;
+    return ksize == 5 && (long long)g.cols * (g.or1 - g.or0) * g.count <= CONV_TINY_CELLS ? CONV_TINY : CONV_SMALL;
 }
 
-template <int KS, int NT, int RBT = RB>
+// f(NT, RBT) as std::integral_constant arguments for the KS-tap kernel's shape `sh` (conv_shape_of never gives the 3-tap
+// kernel SMALL; its SMALL instantiations are compiled all the same)
+template <int KS, class F>
+auto with_conv_shape(conv_shape sh, F &&f) {
+    using std::integral_constant;
+    if constexpr (KS == 5)
+        if (sh == CONV_TINY) return f(integral_constant<int, CONV_TINY_NT>(), integral_constant<int, CONV_TINY_RB>());
+    if (sh != CONV_BIG) return f(integral_constant<int, CONV_SMALL_NT>(), integral_constant<int, CONV_SMALL_RB>());
+    return f(integral_constant<int, (KS >= 5 ? 512 : 256)>(), integral_constant<int, RB>());
+}
+
+// tiles across (x) and down (y) of one launch of depth T: interiors of (TW - 2 HX) x (NT / 32 * RBT - 2 H) cells
+struct conv_tiling { int x, y; };
+template <int KS, int NT, int RBT>
+conv_tiling conv_tiles(const nz_geom &g, int T) {
+    constexpr int O = (KS - 1) / 2, RTH = NT / 32 * RBT;
+    const int H = T * O, HX = conv_hx(H);
+    const int OW = TW - 2 * HX, OH = RTH - 2 * H;
+    return {(g.cols + OW - 1) / OW, (g.or1 - g.or0 + OH - 1) / OH};
+}
+
+template <int KS, int NT, int RBT>
 int32_t launch_fused_nt(hipStream_t s, const float *src, float *dst, const nz_geom &g, const nz_kernel_taps &k, int T) {
-    constexpr int O = (KS - 1) / 2, RTH = NT / 32 * RBT;  // register tile: RTH rows x 128 columns
-    int H = T * O, HX = conv_hx(H);
-    int OW = TW - 2 * HX, OH = RTH - 2 * H;
-    long long blocks = (long long)((g.cols + OW - 1) / OW) * ((g.or1 - g.or0 + OH - 1) / OH);
+    const conv_tiling t = conv_tiles<KS, NT, RBT>(g, T);
+    const long long blocks = (long long)t.x * t.y;
     int aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | (uintptr_t)(g.pitch * 4)) & 15) == 0;
-    const bool fast = nz_tls_float_mode >= NZ_FLOAT_FAST;
-#define NZ_CR(U, F) NZ_LAUNCH((conv_reg_kernel<KS, U, NT, F, RBT>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, T, aligned)
-    if (k.factor == 1.0f) {
-        if (fast) NZ_CR(true, true); else NZ_CR(true, false);
-    } else {
-        if (fast) NZ_CR(false, true); else NZ_CR(false, false);
-    }
-#undef NZ_CR
+    nz_with_unit_fast(k, [&](auto unit, auto fast) {
+        NZ_LAUNCH((conv_reg_kernel<KS, unit, NT, fast, RBT>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, T, aligned);
+    });
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
 
 template <int KS>
 int32_t launch_fused(hipStream_t s, const float *src, float *dst, const nz_geom &g, const nz_kernel_taps &k, int T) {
-    if (KS >= 5 && conv_small_grid(KS, g)) {
-        if constexpr (KS == 5)
-            if (conv_tiny_grid(g)) return launch_fused_nt<KS, 1024, 2>(s, src, dst, g, k, T);
-        return launch_fused_nt<KS, NZ_CONV_SMALL_NT, NZ_CONV_SMALL_RB>(s, src, dst, g, k, T);
-    }
-    return launch_fused_nt<KS, (KS >= 5 ? NZ_CONV_NT_WIDE : NZ_CONV_NT)>(s, src, dst, g, k, T);
+    return with_conv_shape<KS>(conv_shape_of(KS, g), [&](auto nt, auto rbt) { return launch_fused_nt<KS, nt, rbt>(s, src, dst, g, k, T); });
 }
 
 int g_chain_delay_item = -1, g_chain_delay_sleeps = 0;  // nz_debug_chain_delay
 int g_chain_spin_limit = 1 << 21;                         // nz_debug_chain_poll_limit
 
-template <int KS, int NT, int RBT = RB>
-int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k, const int *Ts,
-                        int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
-    constexpr int O = (KS - 1) / 2;
-    constexpr int RTH = NT / 32 * RBT;
+// the work items of L <= NZ_CHAIN_MAXL chained launches: launch l's tiles are items first[l] .. first[l + 1] - 1
+template <int KS, int NT, int RBT>
+nz_chain conv_chain_plan(const nz_geom &g, const int *Ts, int L) {
     nz_chain ch{};
     ch.L = L;
-    ch.first[0] = 0;
     for (int l = 0; l < L; l++) {
-        int H = Ts[l] * O, HX = conv_hx(H);
-        int OW = TW - 2 * HX, OH = RTH - 2 * H;
+        const conv_tiling t = conv_tiles<KS, NT, RBT>(g, Ts[l]);
         ch.T[l] = Ts[l];
-        ch.tiles_x[l] = (g.cols + OW - 1) / OW;
-        ch.first[l + 1] = ch.first[l] + ch.tiles_x[l] * ((g.or1 - g.or0 + OH - 1) / OH);
+        ch.tiles_x[l] = t.x;
+        ch.first[l + 1] = ch.first[l] + t.x * t.y;
     }
     ch.total = ch.first[L];
+    return ch;
+}
+
+template <int KS, int NT, int RBT>
+int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k, const int *Ts,
+                        int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
+    nz_chain ch = conv_chain_plan<KS, NT, RBT>(g, Ts, L);
     ch.epoch = epoch;
     ch.flags = flags;
     ch.plane[0] = plane0;
@@ -901,14 +890,9 @@ int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_ge
     ch.err_host = err_host;
     ch.err_epoch = err_epoch;
     int aligned = ((reinterpret_cast<uintptr_t>(plane0) | reinterpret_cast<uintptr_t>(plane1) | (uintptr_t)(g.pitch * 4)) & 15) == 0;
-    const bool fast = nz_tls_float_mode >= NZ_FLOAT_FAST;
-#define NZ_CC(U, F) NZ_LAUNCH((conv_chain_kernel<KS, U, NT, F, RBT>), dim3((unsigned)ch.total), dim3(NT), 0, s, g, k, ch, aligned)
-    if (k.factor == 1.0f) {
-        if (fast) NZ_CC(true, true); else NZ_CC(true, false);
-    } else {
-        if (fast) NZ_CC(false, true); else NZ_CC(false, false);
-    }
-#undef NZ_CC
+    nz_with_unit_fast(k, [&](auto unit, auto fast) {
+        NZ_LAUNCH((conv_chain_kernel<KS, unit, NT, fast, RBT>), dim3((unsigned)ch.total), dim3(NT), 0, s, g, k, ch, aligned);
+    });
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
@@ -916,12 +900,14 @@ int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_ge
 template <int KS>
 int32_t launch_chain(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k, const int *Ts,
                      int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
-    if (KS >= 5 && conv_small_grid(KS, g)) {
-        if constexpr (KS == 5)
-            if (conv_tiny_grid(g)) return launch_chain_nt<KS, 1024, 2>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
-        return launch_chain_nt<KS, NZ_CONV_SMALL_NT, NZ_CONV_SMALL_RB>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
-    }
-    return launch_chain_nt<KS, (KS >= 5 ? NZ_CONV_NT_WIDE : NZ_CONV_NT)>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
+    return with_conv_shape<KS>(conv_shape_of(KS, g), [&](auto nt, auto rbt) {
+        return launch_chain_nt<KS, nt, rbt>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
+    });
+}
+
+template <int KS>
+int chain_items(const nz_geom &g, const int *Ts, int L) {
+    return with_conv_shape<KS>(conv_shape_of(KS, g), [&](auto nt, auto rbt) { return conv_chain_plan<KS, nt, rbt>(g, Ts, L).total; });
 }
 
 }  // namespace
@@ -929,19 +915,18 @@ int32_t launch_chain(hipStream_t s, float *plane0, float *plane1, const nz_geom 
 // a grid the 5-, 7- and 9-tap kernels serve with 64-row tiles (see conv_small_grid)
 bool nz_conv_small_grid(int ksize, const nz_geom &g) { return conv_small_grid(ksize, g); }
 // ... and so small that a launch is at most a workgroup per CU (the 5-tap kernel then fuses nine applications, nz_stages.cpp)
-bool nz_conv_tiny_grid(int ksize, const nz_geom &g) { return conv_small_grid(ksize, g) && conv_tiny_grid(g); }
+bool nz_conv_tiny_grid(int ksize, const nz_geom &g) { return conv_shape_of(ksize, g) == CONV_TINY; }
 
-// work items (= flags) the chained form of L launches needs on this geometry
+// work items (= flags) the chained form of L launches needs on this geometry: the grid nz_launch_conv_chain launches
 int nz_conv_chain_items(int ksize, const nz_geom &g, const int *Ts, int L) {
-    const int O = (ksize - 1) / 2;
-    const int RTH = (ksize >= 5 ? (conv_small_grid(ksize, g) ? 256 : NZ_CONV_NT_WIDE) : NZ_CONV_NT) / 32 * RB;
-    int n = 0;
-    for (int l = 0; l < L; l++) {
-        int H = Ts[l] * O, HX = conv_hx(H);
-        int OW = TW - 2 * HX, OH = RTH - 2 * H;
-        n += ((g.cols + OW - 1) / OW) * ((g.or1 - g.or0 + OH - 1) / OH);
+    if (L < 1 || L > NZ_CHAIN_MAXL) return 0;
+    switch (ksize) {
+        case 3: return chain_items<3>(g, Ts, L);
+        case 5: return chain_items<5>(g, Ts, L);
+        case 7: return chain_items<7>(g, Ts, L);
+        case 9: return chain_items<9>(g, Ts, L);
     }
-    return n;
+    return 0;
 }
 
 // L <= 8 fused launches as ONE grid with tile-level dependencies (conv_chain_kernel): launch l reads plane (l & 1) and

@@ -131,13 +131,8 @@ __global__ __launch_bounds__(CT) void normalize_kernel(const float *src, float *
 // 16-byte accesses; pitch 132 floats keeps those conflict free.  Cells outside the grid never feed a
 // cell inside it: border cells substitute their own value for a clamped neighbour, exactly what
 // clamp-to-edge reads return (ReadTileData.GetData, Pipeline/Tiles/TileData.cs:106-116).
-#ifndef NZ_FT_NT
-#define NZ_FT_NT 512
-#endif
-#ifndef NZ_FT_OCC
-#define NZ_FT_OCC 4
-#endif
-constexpr int FT_TH = 48, FT_TW = 128, FT_NT = NZ_FT_NT, FT_LP = FT_TW + 4;
+constexpr int FT_TH = 48, FT_TW = 128, FT_NT = 512, FT_LP = FT_TW + 4;
+constexpr int FT_OCC = 4;  // the 48-row kernel's occupancy argument of __launch_bounds__
 constexpr int FT_TH_TINY = 32, FT_TH_MID = 64;  // the tiles of grids that fit one round of the CUs: 1024 threads (nz_launch_flow_fused)
 // FT_MAX_N = 5 (nz_flow_common.hpp): 2n halo rows, n = 5 leaves a 28 x 104 interior
 
@@ -455,7 +450,7 @@ int32_t nz_launch_flow_fused(hipStream_t s, const float *h, const float *const i
         else if (use_mid)                                                                                                        \
             NZ_LAUNCH((flow_fused_kernel<F, L, 4, M, FT_TH_MID, 1024>), dim3((unsigned)blocks, g.count), dim3(1024), 0, s, NZ_FFA); \
         else                                                                                                                     \
-            NZ_LAUNCH((flow_fused_kernel<F, L, NZ_FT_OCC, M, FT_TH, FT_NT>), dim3((unsigned)blocks, g.count), dim3(FT_NT), 0, s, NZ_FFA); \
+            NZ_LAUNCH((flow_fused_kernel<F, L, FT_OCC, M, FT_TH, FT_NT>), dim3((unsigned)blocks, g.count), dim3(FT_NT), 0, s, NZ_FFA); \
     } while (0)
 #define NZ_FF(F, L)                    \
     do {                               \

@@ -42,9 +42,7 @@ __device__ unsigned long long *nz_flow_probe_buf = nullptr;  // [wave][8]
 #else
 #define NZ_FPROBE(slot, val)
 #endif
-#ifndef NZ_FS_WPE
-#define NZ_FS_WPE 2  // waves per SIMD the four- and five-iteration kernels are register-allocated for: 176 VGPRs, nothing spilled (3: 168 VGPRs and a 25-dword spill; 0.147 against 0.149 ms at 4096^2, round 4)
-#endif
+constexpr int FS_WPE = 2;  // waves per SIMD the four- and five-iteration kernels are register-allocated for: 176 VGPRs, nothing spilled (3: 168 VGPRs and a 25-dword spill; 0.147 against 0.149 ms at 4096^2, round 4)
 constexpr int FS_RING = 16;   // rows of height kept per wave (needs 2n - 1 <= 9)
 // NC = columns per lane: 2 (a 128-column strip per wave, 12 registers of state per column and iteration = 120 at n = 5:
 // three waves per SIMD) or 1 (64-column strips: 1.22x the halo columns, half the state per lane -- five waves per SIMD)
@@ -356,7 +354,7 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
 }
 
 template <int NST, int NC, bool FAST>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NST >= 4 ? NZ_FS_WPE : 4)))
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NST >= 4 ? FS_WPE : 4)))
 void flow_stream_kernel(const float *__restrict__ h, float *__restrict__ dst, nz_geom g, int S, int nstrips, int Se,
                         int nseg_edge, float nmin, float nrange, int aligned) {
     __shared__ fs_row<NC> s_ring[FS_RING * 64];
@@ -411,7 +409,7 @@ int32_t nz_launch_flow_stream(hipStream_t s, const float *h, float *dst, const n
     // two columns per lane: a 128-column strip per wave (one column per lane -- 64-column strips, five waves per SIMD -- was built
     // in round 4 and lost: 0.174 against 0.148 ms, 1.22x the halo columns; removed in round 5)
     constexpr int NC = 2;
-    const int waves = 1024 * NZ_FS_WPE;  // one round of resident waves
+    const int waves = 1024 * FS_WPE;  // one round of resident waves
     const int H = 2 * n, OW = 64 * NC - 2 * H;
     const int nstrips = (g.cols + OW - 1) / OW, rows = g.or1 - g.or0;
     const long long per = (long long)nstrips * g.count;

@@ -33,29 +33,14 @@ __device__ __forceinline__ float permutef(float x) { return mod289f((34.0f * x +
 // integer below 2^12, every product below 2^24) the fused instruction returns the very same bits as
 // the reference's separate multiply and add, one VALU slot cheaper.  NOT valid for psrnoise's first
 // permute, whose un-reduced argument overflows 2^24.
-#ifndef NZ_EXACT_FMA
-#define NZ_EXACT_FMA 1
-#endif
 __device__ __forceinline__ float mod289i(float x) {  // x: integer-valued, |x| < 2^24
-#if NZ_EXACT_FMA
     return __builtin_fmaf(-floorf(x * (1.0f / 289.0f)), 289.0f, x);
-#else
-    return mod289f(x);
-#endif
 }
 __device__ __forceinline__ float permutei(float x) {  // x: integer-valued, 0 <= x <= 700
-#if NZ_EXACT_FMA
     return mod289i(__builtin_fmaf(34.0f, x, 1.0f) * x);
-#else
-    return permutef(x);
-#endif
 }
 __device__ __forceinline__ float twice_minus_one(float f) {  // 2*f is exact
-#if NZ_EXACT_FMA
     return __builtin_fmaf(2.0f, f, -1.0f);
-#else
-    return 2.0f * f - 1.0f;
-#endif
 }
 __device__ __forceinline__ float taylor_inv_sqrt(float r) { return 1.79284291400159f - 0.85373472095314f * r; }
 __device__ __forceinline__ float fadef(float t) { return t * t * t * (t * (t * 6.0f - 15.0f) + 10.0f); }
@@ -165,9 +150,6 @@ __device__ __forceinline__ float2 rgrad2_direct(float px, float py, const psr_ta
 // 1/per, q = floor(|x| * inv_lo) is the true quotient or one less for |x|/per < 2^21, q*per and |x| - q*per
 // are exact for |x| < 2^22, so r lands in [0, 2 per) and one conditional subtraction gives the library's
 // value, sign (and signed zero) copied from x -- 7 VALU slots, no data-dependent loop.
-#ifndef NZ_PSR_FMOD
-#define NZ_PSR_FMOD 1
-#endif
 constexpr float PSR_FAST_LIMIT = 2097152.0f;  // |pos| below this keeps every lattice coordinate under 2^22
 __device__ __forceinline__ float fmod_lattice(float x, float per, float inv_lo) {
     float a = fabsf(x);
@@ -199,7 +181,7 @@ __device__ __forceinline__ float psrnoise2(float posx, float posy, const psr_tab
     float d2x = posx - p2x, d2y = posy - p2y;
     constexpr float ipx = (1.0f / 1010.0f) * (1.0f - 0x1p-22f), ipy = (1.0f / 102.0f) * (1.0f - 0x1p-22f);
     float2 g0, g1, g2;
-    if (!WX || !WY || (NZ_PSR_FMOD && fabsf(posx) < PSR_FAST_LIMIT && fabsf(posy) < PSR_FAST_LIMIT)) {
+    if (!WX || !WY || (fabsf(posx) < PSR_FAST_LIMIT && fabsf(posy) < PSR_FAST_LIMIT)) {
         float xw0 = p0x, xw1 = p1x, xw2 = p2x, yw0 = p0y, yw1 = p1y, yw2 = p2y;
         if (WX) { xw0 = fmod_lattice(p0x, perx, ipx); xw1 = fmod_lattice(p1x, perx, ipx); xw2 = fmod_lattice(p2x, perx, ipx); }
         if (WY) { yw0 = fmod_lattice(p0y, pery, ipy); yw1 = fmod_lattice(p1y, pery, ipy); yw2 = fmod_lattice(p2y, pery, ipy); }
@@ -1070,10 +1052,7 @@ int32_t launch_shaped(hipStream_t s, int noiseType, float *dst, int rows, int co
                       const float *d_rgrad, const void *d_simplex, int count) {
     constexpr int use_tab = 1;  // (the direct kernels below serve Sin / psrnoise and every basis beyond its tables' range)
     if (noiseType == NZ_NOISE_SIMPLEX && use_tab && d_simplex) {
-#ifndef NZ_FT_VEC
-#define NZ_FT_VEC 2
-#endif
-        constexpr int VEC = NZ_FT_VEC;
+        constexpr int VEC = 2;  // cells per thread
         int bpr = (cols + 256 * VEC - 1) / (256 * VEC);
         long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
         const int *t1 = reinterpret_cast<const int *>(d_simplex);
@@ -1093,20 +1072,14 @@ int32_t launch_shaped(hipStream_t s, int noiseType, float *dst, int rows, int co
         if (noiseType == NZ_NOISE_CELLULAR) base += NZ_TB1_N * 4 + NZ_TB2_N * 8;
         const int *t1 = reinterpret_cast<const int *>(base);
         const float2 *t2 = reinterpret_cast<const float2 *>(base + NZ_TB1_N * 4);
-#ifndef NZ_TAB2_VEC_PERLIN
-#define NZ_TAB2_VEC_PERLIN 4  // cells per thread: Perlin 0.276 / 0.234 / 0.223 ms with 1 / 2 / 4 (4096^2, 13 octaves); cellular is indifferent
-#endif
-#ifndef NZ_TAB2_VEC_CELLULAR
-#define NZ_TAB2_VEC_CELLULAR 4  // 0.510 -> 0.494 ms
-#endif
         if (noiseType == NZ_NOISE_PERLIN) {
-            constexpr int V = NZ_TAB2_VEC_PERLIN;
+            constexpr int V = 4;  // cells per thread: 0.276 / 0.234 / 0.223 ms with 1 / 2 / 4 (4096^2, 13 octaves)
             int bpr = (cols + 256 * V - 1) / (256 * V);
             long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
             NZ_LAUNCH((fractal_tab2_kernel<NZ_NOISE_PERLIN, V, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows,
                                cols, pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
         } else {
-            constexpr int V = NZ_TAB2_VEC_CELLULAR;
+            constexpr int V = 4;  // cellular is indifferent: 0.510 -> 0.494 ms
             int bpr = (cols + 256 * V - 1) / (256 * V);
             long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
             NZ_LAUNCH((fractal_tab2_kernel<NZ_NOISE_CELLULAR, V, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst,
@@ -1121,10 +1094,7 @@ int32_t launch_shaped(hipStream_t s, int noiseType, float *dst, int rows, int co
                            2 * (NZ_TB1_N * 4 + NZ_TB2_N * 8);
         const int *p3 = reinterpret_cast<const int *>(base);
         const float4 *g3 = reinterpret_cast<const float4 *>(base + NZ_P3_N * 4);
-#ifndef NZ_TAB3_VEC
-#define NZ_TAB3_VEC 1
-#endif
-        constexpr int V3 = NZ_TAB3_VEC;  // cells per thread
+        constexpr int V3 = 1;  // cells per thread
         int bpr = (cols + 256 * V3 - 1) / (256 * V3);
         long long blocks = (long long)bpr * ((rows + p.rows_per_wg - 1) / p.rows_per_wg);
         if (noiseType == NZ_NOISE_DOMAIN_ROTATED_PERLIN)
@@ -1136,20 +1106,15 @@ int32_t launch_shaped(hipStream_t s, int noiseType, float *dst, int rows, int co
         NZ_HIP(hipGetLastError());
         return NZ_OK;
     }
+    constexpr int PSR_VEC = 4;  // cells per thread: 0.492 / 0.518 / 0.464 ms with 1 / 2 / 4 (4096^2, 13 octaves)
     switch (noiseType) {
         case NZ_NOISE_SIN: return launch_basis<NZ_NOISE_SIN, 4, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_PERLIN: return launch_basis<NZ_NOISE_PERLIN, 2, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
-#ifndef NZ_PSR_VEC
-#define NZ_PSR_VEC 4  // cells per thread: 0.492 / 0.518 / 0.464 ms with 1 / 2 / 4 (4096^2, 13 octaves)
-#endif
         case NZ_NOISE_PERIODIC_PERLIN:
-            return launch_basis<NZ_NOISE_PERIODIC_PERLIN, NZ_PSR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
-#ifndef NZ_FR_VEC
-#define NZ_FR_VEC 2
-#endif
-        case NZ_NOISE_SIMPLEX: return launch_basis<NZ_NOISE_SIMPLEX, NZ_FR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+            return launch_basis<NZ_NOISE_PERIODIC_PERLIN, PSR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+        case NZ_NOISE_SIMPLEX: return launch_basis<NZ_NOISE_SIMPLEX, 2, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_ROTATED_SIMPLEX:
-            return launch_basis<NZ_NOISE_ROTATED_SIMPLEX, NZ_PSR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
+            return launch_basis<NZ_NOISE_ROTATED_SIMPLEX, PSR_VEC, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_CELLULAR: return launch_basis<NZ_NOISE_CELLULAR, 2, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);
         case NZ_NOISE_DOMAIN_ROTATED_PERLIN:
             return launch_basis<NZ_NOISE_DOMAIN_ROTATED_PERLIN, 1, SHAPE>(s, dst, rows, cols, pitch, p, d_rgrad, count);

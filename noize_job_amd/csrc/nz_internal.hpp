@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/noize_hip.h"
@@ -199,6 +200,17 @@ extern thread_local int nz_tls_float_mode;
             hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                             \
         }                                                                                                  \
     } while (0)
+// the four instantiations of a tap-sum kernel: calls f(UNIT, FAST) with std::bool_constant arguments.  UNIT: the taps'
+// factor is 1 (no final multiply); FAST: the context runs NZ_FLOAT_FAST (contracted tap sums)
+template <class F>
+inline void nz_with_unit_fast(const nz_kernel_taps &k, F &&f) {
+    const bool fast = nz_tls_float_mode >= NZ_FLOAT_FAST;
+    if (k.factor == 1.0f) {
+        if (fast) f(std::true_type(), std::true_type()); else f(std::true_type(), std::false_type());
+    } else {
+        if (fast) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type());
+    }
+}
 void nz_ctx_handle_rides(nz_ctx *ctx, bool wanted);
 void nz_ctx_arm_last_launch(nz_ctx *ctx);
 

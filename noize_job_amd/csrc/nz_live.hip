@@ -185,12 +185,7 @@ struct live_planes {
     size_t n;
 };
 
-#ifndef NZ_DESCENT_LANES
-#define NZ_DESCENT_LANES 64  // particles per wave
-#endif
-#ifndef NZ_DESCENT_PREFETCH
-#define NZ_DESCENT_PREFETCH 1
-#endif
+constexpr int DESCENT_LANES = 64;  // particles per wave
 
 #ifdef NZ_DESCENT_PROBE
 // -DNZ_DESCENT_PROBE (tools/probe_descent.sh): shader-clock sums over all waves and steps -- waiting for the step's loads,
@@ -306,7 +301,6 @@ __device__ __forceinline__ bool descent_step(const live_planes &P, live_particle
         pv[k] = ld_off(P.pool, no);
         fv[k] = ld_off(P.flow, no);
     }
-#if NZ_DESCENT_PREFETCH
     // The next step reads the 3 x 3 cells around one of this step's neighbours: rows ix - 2 and ix + 2 are the only
     // cache lines of it this step has not touched (z is the fast index: iz +- 2 shares the lines of iz, a line end
     // aside).  Asking for them now -- BEHIND this step's own loads, returns come back in order -- hides their way
@@ -320,7 +314,6 @@ __device__ __forceinline__ bool descent_step(const live_planes &P, live_particle
         pf[4] = ld_off(P.flow, xm);   pf[5] = ld_off(P.flow, xp);
     }
     __builtin_amdgcn_sched_barrier(0);
-#endif
     const float currentHeight = HEIGHT * (h0 + p0);
     int nb[8];
     int hmin = 0x7fffffff, kmin = 0;
@@ -452,9 +445,9 @@ __global__ __launch_bounds__(64) void descent_kernel(live_planes P, const int32_
 #ifdef NZ_DESCENT_PROBE
     unsigned long long probe_t[4] = {0, 0, 0, 0}, probe_last = clock64(), probe_steps = 0;
 #endif
-    for (long long first_pi = (long long)blockIdx.x * NZ_DESCENT_LANES; first_pi < n; first_pi += (long long)gridDim.x * NZ_DESCENT_LANES) {
+    for (long long first_pi = (long long)blockIdx.x * DESCENT_LANES; first_pi < n; first_pi += (long long)gridDim.x * DESCENT_LANES) {
     const long long pi = first_pi + lane;
-    bool alive = lane < NZ_DESCENT_LANES && pi < n;
+    bool alive = lane < DESCENT_LANES && pi < n;
     nz_particle src{0, 0, 0.0f, 0};
     if (alive) src = particles[pi];
     // a particle uploaded with a position outside the tile (nz_particle_queue_upload cannot know the resolution) is
@@ -503,11 +496,9 @@ __global__ __launch_bounds__(64) void descent_kernel(live_planes P, const int32_
         }
         alive = alive && !dies;
         NZ_DPROBE(2);
-#if NZ_DESCENT_PREFETCH
         __builtin_amdgcn_sched_barrier(0);  // the look-ahead values: looked at last
         sink |= __float_as_uint(pf[0]) & __float_as_uint(pf[1]) & __float_as_uint(pf[2]) & __float_as_uint(pf[3]) &
                 __float_as_uint(pf[4]) & __float_as_uint(pf[5]);
-#endif
     }
     if (pend_firsts) {
         const int base = __builtin_amdgcn_readlane(pend_base, __ffsll((long long)pend_firsts) - 1);
@@ -537,9 +528,7 @@ __global__ __launch_bounds__(CT) void forget_kernel(float *sediment, const int32
     for (int i = blockIdx.x * CT + threadIdx.x; i < n; i += gridDim.x * CT) sediment[list[i]] = 0.0f;
 }
 
-#ifndef NZ_EVENTS_BLOCKS
-#define NZ_EVENTS_BLOCKS 2048  // a cell's eight scattered lines per lane: many lanes in flight
-#endif
+constexpr int EVENTS_BLOCKS = 2048;  // a cell's eight scattered lines per lane: many lanes in flight
 __global__ __launch_bounds__(CT) void process_events_kernel(float *pool, float *track, float *sediment,
                                                            unsigned long long *acc, int32_t *touched, const int32_t *list,
                                                            int32_t *counters, int slot, size_t ncell, float poolMul,
@@ -1276,7 +1265,7 @@ extern "C" int32_t nz_queued_beyer_cycle(nz_ctx *ctx, const float *height, const
     NZ_HIP(hipMemsetAsync(events->counters + 2, 0, 8, ctx->stream));  // piles and events of this cycle
     // the count lives on the device: waves beyond it leave; a wave per SIMD slot at most, each takes 64 particles at a
     // time (a queue sized for a whole plane launched 131 k waves for 10 000 particles)
-    const unsigned blocks = (unsigned)std::min<long long>(((long long)particles->capacity + NZ_DESCENT_LANES - 1) / NZ_DESCENT_LANES, 8192);
+    const unsigned blocks = (unsigned)std::min<long long>(((long long)particles->capacity + DESCENT_LANES - 1) / DESCENT_LANES, 8192);
     hipLaunchKernelGGL(descent_kernel, dim3(blocks), dim3(64), 0, ctx->stream, P, particles->hdr, particles->data, *ep, res,
                        (float)tm->HEIGHT, tm->PATCH_RES[0]);
     NZ_HIP(hipGetLastError());
@@ -1295,7 +1284,7 @@ extern "C" int32_t nz_process_beyer_erosive_events(nz_ctx *ctx, float *height, f
     const int cur = events->cur, prev = cur ^ 1;
     hipLaunchKernelGGL(forget_kernel, dim3(512), dim3(CT), 0, ctx->stream, events->sediment, events->list[prev], events->counters, prev);
     NZ_HIP(hipMemsetAsync(events->counters + prev, 0, 4, ctx->stream));
-    hipLaunchKernelGGL(process_events_kernel, dim3(NZ_EVENTS_BLOCKS), dim3(CT), 0, ctx->stream, pool, track, events->sediment,
+    hipLaunchKernelGGL(process_events_kernel, dim3(EVENTS_BLOCKS), dim3(CT), 0, ctx->stream, pool, track, events->sediment,
                        events->acc, events->touched, events->list[cur], events->counters, cur, (size_t)res * res,
                        ep->POOL_PLACEMENT_MULTIPLIER, ep->TRACK_PLACEMENT_MULTIPLIER);
     NZ_HIP(hipGetLastError());
@@ -1332,9 +1321,12 @@ static int32_t erode_height_maps(nz_ctx *ctx, float *height, nz_erosive_events *
     }
     int32_t *pile_ctl = D >= 1 ? events->pile_blocks + (size_t)nb * nb : nullptr;
     int32_t *pile_list = D >= 1 ? pile_ctl + PILE_CTL : nullptr;
+    // NZ_PILE_TICKET (1): all colours in one launch, the busy blocks handed out by ticket (pile_ticket_kernel); 0: one
+    // launch per colour over every block of it -- also what a context does for good after a ticket launch of its gave up
+    static const bool ticket_env = [] { const char *e = getenv("NZ_PILE_TICKET"); return !e || atoi(e) != 0; }();
+    const bool ticket = ticket_env && !ctx->pile_ticket_off;
     // safe mode keeps the plane as the job found it (one plane copy per cycle, ~25 us at 8192^2)
-    static const bool ticket_wanted = [] { const char *e = getenv("NZ_PILE_TICKET"); return !e || atoi(e) != 0; }();
-    const bool safe = ctx->pile_safe && D >= 1 && ticket_wanted && !ctx->pile_ticket_off;
+    const bool safe = ctx->pile_safe && D >= 1 && ticket;
     if (safe) {
         if (!events->height_snapshot) NZ_HIP(hipMalloc((void **)&events->height_snapshot, (size_t)res * res * sizeof(float)));
         NZ_HIP(hipMemcpyAsync(events->height_snapshot, height, (size_t)res * res * sizeof(float), hipMemcpyDeviceToDevice, ctx->stream));
@@ -1372,10 +1364,6 @@ static int32_t erode_height_maps(nz_ctx *ctx, float *height, nz_erosive_events *
         const size_t lds = (((size_t)nverts * 9 + 15) & ~(size_t)15) + (size_t)B * B * 4 + (size_t)nverts * 4;
         if (lds > 64 * 1024)
             NZ_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        // NZ_PILE_TICKET (1): all colours in one launch, the busy blocks handed out by ticket (pile_ticket_kernel); 0: one
-        // launch per colour over every block of it -- also what a context does for good after a ticket launch of its gave up
-        static const bool ticket_env = [] { const char *e = getenv("NZ_PILE_TICKET"); return !e || atoi(e) != 0; }();
-        const bool ticket = ticket_env && !ctx->pile_ticket_off;
         const float incr = ep->MIN_PILE_INCREMENT / (float)tm->HEIGHT;
         auto colour_launches = [&]() -> int32_t {
             for (int colour = 0; colour < 4; colour++) {

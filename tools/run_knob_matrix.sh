@@ -1,6 +1,7 @@
 #!/bin/bash
 # The whole GPU suite under every launch-form knob of DESIGN.md section 6 (none of them may change a result).
 #   tools/run_knob_matrix.sh [first [last]]   -- knobs first..last of the list (0-based), default all
+# Stops at the first knob whose pytest run exits with anything but 0 or 1 (a time limit or a crash).
 cd "$(dirname "$0")/.."
 # Eleven knobs are left: NZ_RCCL_LIB names a library; the other ten FORCE a launch form at sizes where it is not
 # the default, so that the small-grid parity tests cover every form that is the default somewhere.
@@ -14,6 +15,13 @@ for ((i = first; i <= last && i < ${#KNOBS[@]}; i++)); do
   log=gpurun_out/knob_$i.log
   mkdir -p gpurun_out
   env $kv timeout -k 10 300 python3 -m pytest tests -m gpu -q -rf > $log 2>&1
+  rc=$?
   grep -E "^FAILED|^ERROR" $log
   tail -1 $log
+  # 0: passed, 1: tests failed.  Anything else (124 / 137: time limit, 134: abort, 139: segfault, ...) may have left the
+  # GPU faulted: start nothing more on it.
+  if [ $rc -gt 1 ]; then
+    echo "== $kv: pytest exited $rc -- stopping, no further knobs run"
+    exit $rc
+  fi
 done
