@@ -409,13 +409,6 @@ struct nz_sharded {
 
 namespace {
 
-std::vector<int> split_iterations(int n, int cap) {
-    const int launches = (n + cap - 1) / cap, base = n / launches, rem = n % launches;
-    std::vector<int> v;
-    for (int i = 0; i < launches; i++) v.push_back(base + (i < rem ? 1 : 0));
-    return v;
-}
-
 int32_t launch_radii(const nz_terrain_params &p, nz_kernel_taps *taps, std::vector<launch_rad> *out) {
     out->clear();
     NZ_REQUIRE(p.filterIterations >= 0 && p.flowIterations >= 0 && p.erosionIterations >= 0, "negative iteration count");
@@ -427,10 +420,10 @@ int32_t launch_radii(const nz_terrain_params &p, nz_kernel_taps *taps, std::vect
             return NZ_ERR_UNSUPPORTED;
         }
         const int O = (taps->ksize - 1) / 2;
-        for (int T : split_iterations(p.filterIterations, cap)) out->push_back({1, T, T * O, T * O});
+        for (int T : nz_split_iterations(p.filterIterations, cap)) out->push_back({1, T, T * O, T * O});
     }
     if (p.flowIterations > 0)
-        for (int n : split_iterations(p.flowIterations, nz_flow_fused_max())) out->push_back({2, n, 2 * n, 2 * n});
+        for (int n : nz_split_iterations(p.flowIterations, nz_flow_fused_max())) out->push_back({2, n, 2 * n, 2 * n});
     for (int left = p.erosionIterations; left > 0;) {
         const int E = std::min(left, nz_erosion_max_fused());
         out->push_back({3, E, E, 0});  // the min window reaches upwards only

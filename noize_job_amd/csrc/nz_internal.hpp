@@ -214,10 +214,16 @@ inline void nz_with_unit_fast(const nz_kernel_taps &k, F &&f) {
 void nz_ctx_handle_rides(nz_ctx *ctx, bool wanted);
 void nz_ctx_arm_last_launch(nz_ctx *ctx);
 
-// every stage launch goes through here: one place that knows which stream a context's work runs on
-template <class F>
-inline int32_t launch_on_ctx(nz_ctx *ctx, const nz_geom &g, F launch) {
-    return launch(ctx->stream, g);
+// `n` >= 1 iterations as the fewest launches of at most `cap` each, split as evenly as they go: the depth of every launch,
+// larger ones first.  even: the series ping-pongs in place and must leave its result where it started, so an odd launch
+// count takes one launch more while every launch still gets an iteration (it stays odd only when each launch holds one
+// iteration already: the caller copies back)
+inline std::vector<int> nz_split_iterations(int n, int cap, bool even = false) {
+    int L = (n + cap - 1) / cap;
+    if (even && (L & 1) && L + 1 <= n) L += 1;
+    std::vector<int> d(L);
+    for (int i = 0; i < L; i++) d[i] = n / L + (i < n % L ? 1 : 0);
+    return d;
 }
 
 int32_t nz_check_stripe(const nz_stripe *st, int halo, int halo_below = -1);  // rows needed above / below the owned ones

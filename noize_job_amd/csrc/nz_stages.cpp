@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "nz_internal.hpp"
@@ -170,15 +171,42 @@ static int conv_tcap(int ksize) {
     return cap < hw ? cap : hw;
 }
 
-// `iterations` applications of (X pass, Z pass).  swapped == nullptr: the result must be back in `src`, so the
-// applications are grouped into an even number of fused launches that ping-pong src <-> tmp (or an odd number and a
-// copy).  Otherwise (READ / WRITE pair, nz_rw_tile) the launch count is free and *swapped tells whether the result
-// is in `tmp`.
+// the copy back that ends an in-place series with an odd launch count: rows [or0, or1) of every grid, `from` -> `to`.
+// It is the series' last operation, so the entry's handle rides on it.
+static int32_t copy_back(nz_ctx *ctx, const nz_geom &g, float *to, const float *from) {
+    const size_t off = (size_t)g.or0 * g.pitch;
+    nz_ctx_arm_last_launch(ctx);
+    return nz_launch_copy(ctx->stream, to + off, from + off, nz_geom_span(g));
+}
+
+// One launch per entry of `depths`, step(from, to, depth), ping-ponging src <-> tmp.  swapped == nullptr: the result must
+// be back in `src`, and an odd launch count is followed by a copy back; otherwise (READ / WRITE pair, nz_rw_tile) *swapped
+// tells whether the result is in `tmp`.  The operation that ends the series carries the entry's handle.
+template <class Step>
+static int32_t run_series(nz_ctx *ctx, const nz_geom &g, float *src, float *tmp, const std::vector<int> &depths,
+                          bool *swapped, Step step) {
+    const int L = (int)depths.size();
+    const bool copy = !swapped && (L & 1);
+    float *cur = src, *other = tmp;
+    for (int i = 0; i < L; i++) {
+        if (i == L - 1 && !copy) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY_(step(cur, other, depths[i]));
+        std::swap(cur, other);
+    }
+    if (swapped) *swapped = (L & 1) != 0;
+    return copy ? copy_back(ctx, g, src, tmp) : NZ_OK;
+}
+
+// `iterations` applications of (X pass, Z pass) as a series of launches (run_series): in place (swapped == nullptr) the
+// fused applications are grouped into an even number of launches where they can be.
 static int32_t conv_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geom &g, const nz_kernel_taps &t,
                                int iterations, bool *swapped = nullptr) {
     NZ_REQUIRE(src && tmp && src != tmp, "src/tmp must be two distinct planes");
     NZ_REQUIRE(iterations >= 1, "iterations < 1");
     if (swapped) *swapped = false;
+    if (nz_conv_has_wide(t.ksize))  // one launch per application
+        return run_series(ctx, g, src, tmp, nz_split_iterations(iterations, 1), swapped,
+                          [&](const float *from, float *to, int) { return nz_launch_conv_wide(ctx->stream, from, to, g, t); });
     int cap = (t.ksize & 1) ? conv_tcap(t.ksize) : 0;
     // a small grid is served by one round of workgroups whatever the depth: one launch less beats the deeper halo
     // (512^2 tiles, READ / WRITE pair, 17 applications as 6 + 6 + 5 instead of 5 + 4 + 4 + 4: 11 100 -> 11 700 tiles/s)
@@ -188,42 +216,6 @@ static int32_t conv_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geo
     // time; from 1024^2 on the deeper halo costs more than the launch it saves: 55 -> 59 us)
     if (t.ksize == 5 && cap == 5 && nz_conv_small_grid(t.ksize, g))
         cap = nz_conv_tiny_grid(t.ksize, g) ? 9 : 6;
-    if (nz_conv_has_wide(t.ksize)) {  // one launch per application, ping-pong, copy back after an odd count
-        float *cur = src, *other = tmp;
-        for (int i = 0; i < iterations; i++) {
-            // (a READ / WRITE pair ends with this launch -- odd count or not, nothing is copied back: see below)
-            if (swapped && i == iterations - 1) nz_ctx_arm_last_launch(ctx);
-            NZ_TRY_(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-                return nz_launch_conv_wide(st, cur, other, gb, t);
-            }));
-            float *s = cur; cur = other; other = s;
-        }
-        if (cur != src && swapped) {
-            *swapped = true;
-        } else if (cur != src) {
-            nz_ctx_arm_last_launch(ctx);  // the copy back is the last operation
-            NZ_TRY_(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-                size_t off = (size_t)gb.or0 * gb.pitch;
-                return nz_launch_copy(st, src + off, tmp + off, nz_geom_span(gb));
-            }));
-        }
-        return NZ_OK;
-    }
-    if (cap > 0 && iterations == 1) {  // the delegate's single application: one launch into tmp, copy back
-        if (swapped) nz_ctx_arm_last_launch(ctx);
-        NZ_TRY_(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            return nz_launch_conv_fused(st, src, tmp, gb, t, 1);
-        }));
-        if (swapped) {
-            *swapped = true;
-            return NZ_OK;
-        }
-        nz_ctx_arm_last_launch(ctx);  // the copy back is the last operation
-        return launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            size_t off = (size_t)gb.or0 * gb.pitch;
-            return nz_launch_copy(st, src + off, tmp + off, nz_geom_span(gb));
-        });
-    }
     if (cap == 0) {  // even or out-of-table sizes: the two passes as launched by the reference
         if (g.count > 1) {  // no batched form of the generic passes: grid by grid
             nz_geom one = g;
@@ -234,20 +226,13 @@ static int32_t conv_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geo
             return NZ_OK;
         }
         for (int i = 0; i < iterations; i++) {
-            int32_t rc = launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-                return nz_launch_conv_pass_x(st, src, tmp, gb, t);
-            });
-            if (rc) return rc;
-            rc = launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-                return nz_launch_conv_pass_z(st, tmp, src, gb, t);
-            });
-            if (rc) return rc;
+            NZ_TRY_(nz_launch_conv_pass_x(ctx->stream, src, tmp, g, t));
+            NZ_TRY_(nz_launch_conv_pass_z(ctx->stream, tmp, src, g, t));
         }
         return NZ_OK;
     }
-    int L = (iterations + cap - 1) / cap;
-    if (!swapped && (L & 1) && L + 1 <= iterations) L += 1;  // an even count leaves the result in src
-    int base = iterations / L, rem = iterations % L;
+    const std::vector<int> Ts = nz_split_iterations(iterations, cap, !swapped);
+    const int L = (int)Ts.size();
     // three or more launches of a 5..9-tap kernel run as ONE grid with tile-level dependencies (nz_filter.hip,
     // conv_chain_kernel): Gauss5 x17 0.212 -> 0.198 ms at 4096^2.  Two launches gain nothing (Gauss9 x6 -3 %, Gauss5 x6
     // +2.5 %, two single applications +15 %: a tile's poll and its sc1 accesses cost what the missing launch boundary
@@ -255,7 +240,7 @@ static int32_t conv_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geo
     // NZ_CONV_CHAIN=2: whenever there are two launches or more (the test suite runs the parity tests under it).
     static const int chain_mode = getenv("NZ_CONV_CHAIN") ? atoi(getenv("NZ_CONV_CHAIN")) : 1;
     // (where the row-streaming form of a launch applies -- big grids, 3 / 5 taps -- plain launches of it are faster still)
-    const bool streamed = nz_conv_stream_wanted(g, t.ksize, base + (rem ? 1 : 0)) && nz_conv_stream_wanted(g, t.ksize, base);
+    const bool streamed = nz_conv_stream_wanted(g, t.ksize, Ts.front()) && nz_conv_stream_wanted(g, t.ksize, Ts.back());
     // (A small grid -- fewer than ~7 M cells, 64-row tiles -- chains from TWO launches on since round 5: with the ticket gone and
     // four rows per thread the chained grid wins there too.  Gauss5 x17 2048^2 87.2 -> 67.9 us, 2560^2 110.9 -> 95.0; 1024^2 by
     // itself 45.6 -> 47.3 us, in a tile's pipeline 10 550 -> 11 020 tiles/s (one launch to enqueue and to start instead of three);
@@ -267,89 +252,29 @@ static int32_t conv_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geo
         // T must not decrease along the chain: a tile of launch l + 1 waits for the launch-l tiles whose INTERIOR meets
         // its input window (read after write); its own stores land in the plane launch l reads, and the launch-l tiles
         // that read that region are all among the awaited ones only while H(l) <= H(l + 1) (write after read)
-        int Ts[8];
-        for (int i = 0; i < L; i++) Ts[i] = base + (i >= L - rem ? 1 : 0);
+        int Tc[8];
+        for (int i = 0; i < L; i++) Tc[i] = Ts[L - 1 - i];
         int *flags = nullptr;
         unsigned epoch = 0, *err_host = nullptr, *err_epoch = nullptr;
-        NZ_TRY_(nz_ctx_chain_state(ctx, (size_t)nz_conv_chain_items(t.ksize, g, Ts, L), &flags, &epoch, &err_host, &err_epoch));
+        NZ_TRY_(nz_ctx_chain_state(ctx, (size_t)nz_conv_chain_items(t.ksize, g, Tc, L), &flags, &epoch, &err_host, &err_epoch));
         nz_ctx_arm_last_launch(ctx);  // (one launch; no copy follows in either form: an even count or a pair)
-        NZ_TRY_(nz_launch_conv_chain(ctx->stream, src, tmp, g, t, Ts, L, flags, epoch, err_host, err_epoch));
+        NZ_TRY_(nz_launch_conv_chain(ctx->stream, src, tmp, g, t, Tc, L, flags, epoch, err_host, err_epoch));
         if (swapped) *swapped = (L & 1) != 0;
         return NZ_OK;
     }
-    float *cur = src, *other = tmp;
-    for (int i = 0; i < L; i++) {
-        int T = base + (i < rem ? 1 : 0);
-        // the last launch is the stage's last operation unless a copy back follows (single plane, odd count)
-        if (i == L - 1 && (swapped || !(L & 1))) nz_ctx_arm_last_launch(ctx);
-        int32_t rc = launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            return nz_launch_conv_fused(st, cur, other, gb, t, T);
-        });
-        if (rc) return rc;
-        float *s = cur; cur = other; other = s;
-    }
-    if (cur != src && swapped) {
-        *swapped = true;
-        return NZ_OK;
-    }
-    if (cur != src) {  // odd count (only when cap == 1): copy back
-        nz_ctx_arm_last_launch(ctx);
-        return launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            size_t off = (size_t)gb.or0 * gb.pitch;
-            return nz_launch_copy(st, src + off, tmp + off, nz_geom_span(gb));
-        });
-    }
-    return NZ_OK;
+    return run_series(ctx, g, src, tmp, Ts, swapped,
+                      [&](const float *from, float *to, int T) { return nz_launch_conv_fused(ctx->stream, from, to, g, t, T); });
 }
 
+// ErosionKernelJob.ScheduleSeries KernelJob.cs:318-335: min-X then min-Z (size 3) = the min over {x-1,x} x {z-1,z}, up to
+// nz_erosion_max_fused() of them per launch; in place, a single iteration is one launch into tmp and the copy back that
+// stands for the flush
 static int32_t erosion_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geom &g, int iterations,
                                   bool *swapped = nullptr) {
     NZ_REQUIRE(src && tmp && src != tmp, "src/tmp must be two distinct planes");
     NZ_REQUIRE(iterations >= 1, "iterations < 1");
-    if (swapped) *swapped = false;
-    if (iterations == 1 && !swapped) {
-        // ErosionKernelJob.ScheduleSeries KernelJob.cs:318-335: min-X then min-Z (size 3) = the min over
-        // {x-1,x} x {z-1,z}; one launch into tmp, then the copy back that stands for the flush
-        NZ_TRY_(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            return nz_launch_erosion_fused(st, src, tmp, gb, 1);
-        }));
-        nz_ctx_arm_last_launch(ctx);  // the copy back is the last operation
-        return launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            size_t off = (size_t)gb.or0 * gb.pitch;
-            return nz_launch_copy(st, src + off, tmp + off, nz_geom_span(gb));
-        });
-    }
-    // an even number of launches ends in src; when every launch already holds its one iteration and the
-    // count is odd, the last result is copied back instead
-    int cap = nz_erosion_max_fused();
-    int L = (iterations + cap - 1) / cap;
-    if (!swapped) {
-        if (L < 2) L = 2;
-        if ((L & 1) && L + 1 <= iterations) L += 1;
-    }
-    int base = iterations / L, rem = iterations % L;
-    float *cur = src, *other = tmp;
-    for (int i = 0; i < L; i++) {
-        int E = base + (i < rem ? 1 : 0);
-        if (i == L - 1 && (swapped || !(L & 1))) nz_ctx_arm_last_launch(ctx);  // no copy back follows
-        int32_t rc = launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            return nz_launch_erosion_fused(st, cur, other, gb, E);
-        });
-        if (rc) return rc;
-        float *s = cur; cur = other; other = s;
-    }
-    if (cur != src && swapped) {
-        *swapped = true;
-        return NZ_OK;
-    }
-    if (cur != src) {
-        nz_ctx_arm_last_launch(ctx);  // the copy back is the last operation
-        return launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            size_t off = (size_t)gb.or0 * gb.pitch;
-            return nz_launch_copy(st, src + off, tmp + off, nz_geom_span(gb));
-        });
-    }
-    return NZ_OK;
+    return run_series(ctx, g, src, tmp, nz_split_iterations(iterations, nz_erosion_max_fused(), !swapped), swapped,
+                      [&](const float *from, float *to, int E) { return nz_launch_erosion_fused(ctx->stream, from, to, g, E); });
 }
 
 // what nz_comm.cpp (the sharded plan) needs of the above
@@ -446,6 +371,14 @@ extern "C" int32_t nz_fractal_shaped_stripe(nz_ctx *ctx, int32_t noiseType, floa
 // ---------------------------------------------------------------------------------------------
 // separable filters
 // ---------------------------------------------------------------------------------------------
+// the in-place and batched bodies of the filter and blur stages, once their taps are resolved
+static int32_t conv_stage(nz_ctx *ctx, float *src, float *tmp, const nz_geom &g, const nz_kernel_taps &t, int32_t iterations,
+                          nz_handle *out) {
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms the operation that ends it)
+    NZ_TRY(conv_iterations(ctx, src, tmp, g, t, iterations));
+    return nz_ctx_finish(ctx, out);
+}
+
 // SeparableKernelFilter.ScheduleReduce<RootSumSquaresTiles> (KernelJob.cs:187-215) for Sobel3_2D: the horizontal
 // filter on src, the vertical filter on a copy of the ORIGINAL plane, then src = sqrt(src^2 + copy^2); both with
 // kernelFactor 1.  (The reference takes its copy on the host at schedule time, i.e. before `dependency` has run --
@@ -480,9 +413,7 @@ extern "C" int32_t nz_kernel_filter_stage(nz_ctx *ctx, float *src, float *tmp, i
     }
     nz_kernel_taps t;
     NZ_TRY(filter_taps(filter, &t));
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms its last launch unless a copy back follows it)
-    NZ_TRY(conv_iterations(ctx, src, tmp, nz_geom_tile(resolution), t, iterations));
-    return nz_ctx_finish(ctx, out);
+    return conv_stage(ctx, src, tmp, nz_geom_tile(resolution), t, iterations, out);
 }
 
 // Edge1DFilter.Schedule / Edge2DFilter.Schedule, Filter/Kernel/Edge/EdgeJob.cs:11-44 (kernels: EdgeDetection.cs:23-84,
@@ -517,9 +448,7 @@ extern "C" int32_t nz_gauss_blur_stage(nz_ctx *ctx, float *src, float *tmp, int3
     NZ_TRY(check_res(resolution));
     nz_kernel_taps t;
     NZ_TRY(gauss_taps(width, sigma, &t));
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms its last launch unless a copy back follows it)
-    NZ_TRY(conv_iterations(ctx, src, tmp, nz_geom_tile(resolution), t, iterations));
-    return nz_ctx_finish(ctx, out);
+    return conv_stage(ctx, src, tmp, nz_geom_tile(resolution), t, iterations, out);
 }
 
 extern "C" int32_t nz_gauss_filter(nz_ctx *ctx, float *src, float *tmp, int32_t width, int32_t sigma,
@@ -533,9 +462,7 @@ extern "C" int32_t nz_smooth_blur_stage(nz_ctx *ctx, float *src, float *tmp, int
     NZ_TRY(check_res(resolution));
     nz_kernel_taps t;
     NZ_TRY(smooth_taps(width, &t));
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms its last launch unless a copy back follows it)
-    NZ_TRY(conv_iterations(ctx, src, tmp, nz_geom_tile(resolution), t, iterations));
-    return nz_ctx_finish(ctx, out);
+    return conv_stage(ctx, src, tmp, nz_geom_tile(resolution), t, iterations, out);
 }
 
 extern "C" int32_t nz_smooth_filter(nz_ctx *ctx, float *src, float *tmp, int32_t width, int32_t resolution,
@@ -736,6 +663,37 @@ extern "C" size_t nz_flowmap_stage_work_floats(int32_t resolution) {
     return resolution > 0 ? (size_t)11 * resolution * resolution : 0;  // the reference stage's 11 planes
 }
 
+// FlowMapStage (FlowMapStage.cs:52-194) on `g`: `iterations` split into launches of <= nz_flow_fused_max() iterations that
+// keep the tile on chip, the state {water, fN, fS, fE, fW} ping-ponging between the READ and WRITE planes of `work`
+// (FlowMapStage.cs:52-62, plane p of a batch = work + p * count * res^2).  The first launch implies water == 0.0001
+// (fillStage, FlowMapStage.cs:129) and flux == 0 (defined); the last one ends in writeStage + normStage
+// (FlowMapStage.cs:179-194), args = {normMin, normMax, normMax - normMin} (:48-51), and writes `dst`.
+// hcopy == nullptr: every launch reads the heights from `h`, which nothing overwrites.  Otherwise the result overwrites
+// the height plane (dst == h), which the last launch still reads with a halo: the first launch keeps a private copy of it
+// in `hcopy` for the later ones, and a single launch writes `hcopy`, copied back to `dst` behind it.
+static int32_t flow_series(nz_ctx *ctx, const nz_geom &g, float *work, int32_t iterations, float normMin, float normMax,
+                           const float *h, float *dst, float *hcopy) {
+    const size_t n = (size_t)g.cols * g.rows * g.count;
+    float *A[5], *B[5];
+    for (int i = 0; i < 5; i++) {
+        A[i] = work + (size_t)i * n;
+        B[i] = work + (size_t)(5 + i) * n;
+    }
+    const std::vector<int> its = nz_split_iterations(iterations, nz_flow_fused_max());
+    const int L = (int)its.size();
+    const bool copy = hcopy && L == 1;
+    float **cur = A, **nxt = B;
+    for (int i = 0; i < L; i++) {
+        const int first = i == 0, last = i == L - 1;
+        if (last && !copy) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_flow_fused(ctx->stream, first || !hcopy ? h : hcopy, first ? nullptr : cur, last ? nullptr : nxt,
+                                    !last ? nullptr : (copy ? hcopy : dst), first && !last ? hcopy : nullptr, g, its[i],
+                                    first, last, normMin, normMax - normMin));
+        std::swap(cur, nxt);
+    }
+    return copy ? copy_back(ctx, g, dst, hcopy) : NZ_OK;
+}
+
 static int32_t flowmap_stage_impl(nz_ctx *ctx, float *src, float *work, int32_t iterations, float normMin,
                                   float normMax, int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
     NZ_BEGIN(ctx, dep);
@@ -743,49 +701,10 @@ static int32_t flowmap_stage_impl(nz_ctx *ctx, float *src, float *work, int32_t 
     NZ_REQUIRE(src && work, "src/work is NULL");
     NZ_REQUIRE(iterations >= 1, "iterations < 1");
     NZ_REQUIRE(count >= 1 && count <= 65535, "count %d out of range [1,65535]", count);
-    // a batch keeps plane p of all its tiles together: plane p = work + p * count * res^2
-    size_t n = (size_t)resolution * resolution * count;
     nz_geom g = count > 1 ? nz_geom_batch(resolution, count) : nz_geom_tile(resolution);
-    float *A[5], *B[5];  // {water, fN, fS, fE, fW} x {READ, WRITE}, FlowMapStage.cs:52-62
-    for (int i = 0; i < 5; i++) {
-        A[i] = work + (size_t)i * n;
-        B[i] = work + (size_t)(5 + i) * n;
-    }
-    // `iterations` split into launches of <= nz_flow_fused_max() iterations that keep the tile on chip.
-    // The first launch implies water == 0.0001 (fillStage, FlowMapStage.cs:129) and flux == 0 (defined);
-    // the last one ends in writeStage + normStage (FlowMapStage.cs:179-194), args = {normMin, normMax,
-    // normMax - normMin} (:48-51).
-    int cap = nz_flow_fused_max();
-    int launches = (iterations + cap - 1) / cap;
-    int base = iterations / launches, rem = iterations % launches;
-    float **cur = A, **nxt = B;
-    // The result overwrites the height plane, which the last launch still reads with a halo: the
-    // first launch keeps a private copy of it (the stage's 11th plane) for the later ones.
-    float *hcopy = work + (size_t)10 * n;
-    for (int i = 0; i < launches; i++) {
-        int nit = base + (i < rem ? 1 : 0);
-        int first = i == 0, last = i == launches - 1;
-        const float *hsrc = first ? src : hcopy;
-        float *dst = !last ? nullptr : (launches == 1 ? hcopy : src);
-        if (last && launches > 1) {  // the stage's last operation (a single launch is followed by the copy back below)
-            nz_ctx_handle_rides(ctx, out != nullptr);
-            nz_ctx_arm_last_launch(ctx);
-        }
-        NZ_TRY(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            return nz_launch_flow_fused(st, hsrc, first ? nullptr : cur, last ? nullptr : nxt, dst,
-                                        (first && !last) ? hcopy : nullptr, gb, nit, first, last, normMin,
-                                        normMax - normMin);
-        }));
-        float **s = cur; cur = nxt; nxt = s;
-    }
-    if (launches == 1) {
-        nz_ctx_handle_rides(ctx, out != nullptr);
-        nz_ctx_arm_last_launch(ctx);
-        NZ_TRY(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            size_t off = (size_t)gb.or0 * gb.pitch;
-            return nz_launch_copy(st, src + off, hcopy + off, nz_geom_span(gb));
-        }));
-    }
+    float *hcopy = work + (size_t)10 * resolution * resolution * count;  // the stage's 11th plane
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (flow_series arms the operation that ends it)
+    NZ_TRY(flow_series(ctx, g, work, iterations, normMin, normMax, src, src, hcopy));
     return nz_ctx_finish(ctx, out);
 }
 
@@ -844,9 +763,7 @@ extern "C" int32_t nz_kernel_filter_stage_batch(nz_ctx *ctx, float *src, float *
     NZ_TRY(check_batch(resolution, count));
     nz_kernel_taps t;
     NZ_TRY(filter_taps(filter, &t));
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms its last launch unless a copy back follows it)
-    NZ_TRY(conv_iterations(ctx, src, tmp, nz_geom_batch(resolution, count), t, iterations));
-    return nz_ctx_finish(ctx, out);
+    return conv_stage(ctx, src, tmp, nz_geom_batch(resolution, count), t, iterations, out);
 }
 
 extern "C" int32_t nz_gauss_blur_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t width, int32_t sigma,
@@ -856,9 +773,7 @@ extern "C" int32_t nz_gauss_blur_stage_batch(nz_ctx *ctx, float *src, float *tmp
     NZ_TRY(check_batch(resolution, count));
     nz_kernel_taps t;
     NZ_TRY(gauss_taps(width, sigma, &t));
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms its last launch unless a copy back follows it)
-    NZ_TRY(conv_iterations(ctx, src, tmp, nz_geom_batch(resolution, count), t, iterations));
-    return nz_ctx_finish(ctx, out);
+    return conv_stage(ctx, src, tmp, nz_geom_batch(resolution, count), t, iterations, out);
 }
 
 extern "C" int32_t nz_smooth_blur_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t width, int32_t iterations,
@@ -867,9 +782,7 @@ extern "C" int32_t nz_smooth_blur_stage_batch(nz_ctx *ctx, float *src, float *tm
     NZ_TRY(check_batch(resolution, count));
     nz_kernel_taps t;
     NZ_TRY(smooth_taps(width, &t));
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (conv_iterations arms its last launch unless a copy back follows it)
-    NZ_TRY(conv_iterations(ctx, src, tmp, nz_geom_batch(resolution, count), t, iterations));
-    return nz_ctx_finish(ctx, out);
+    return conv_stage(ctx, src, tmp, nz_geom_batch(resolution, count), t, iterations, out);
 }
 
 extern "C" int32_t nz_erosion_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t iterations, int32_t resolution,
@@ -965,32 +878,8 @@ extern "C" int32_t nz_flowmap_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, float *wor
     NZ_TRY(check_rw(tile));
     NZ_REQUIRE(work, "work is NULL");
     NZ_REQUIRE(iterations >= 1, "iterations < 1");
-    size_t n = (size_t)tile->resolution * tile->resolution * tile->count;
-    nz_geom g = rw_geom(tile);
-    float *A[5], *B[5];  // {water, fN, fS, fE, fW} x {READ, WRITE}, FlowMapStage.cs:52-62
-    for (int i = 0; i < 5; i++) {
-        A[i] = work + (size_t)i * n;
-        B[i] = work + (size_t)(5 + i) * n;
-    }
-    int cap = nz_flow_fused_max();
-    int launches = (iterations + cap - 1) / cap;
-    int base = iterations / launches, rem = iterations % launches;
-    float **cur = A, **nxt = B;
-    // every launch reads the heights from the READ plane, which nothing overwrites; the last one writes the WRITE plane
-    for (int i = 0; i < launches; i++) {
-        int nit = base + (i < rem ? 1 : 0);
-        int first = i == 0, last = i == launches - 1;
-        if (last) {  // the stage's last operation: its handle rides on this launch
-            nz_ctx_handle_rides(ctx, out != nullptr);
-            nz_ctx_arm_last_launch(ctx);
-        }
-        NZ_TRY(launch_on_ctx(ctx, g, [&](hipStream_t st, const nz_geom &gb) {
-            return nz_launch_flow_fused(st, tile->read, first ? nullptr : cur, last ? nullptr : nxt,
-                                        last ? tile->write : nullptr, nullptr, gb, nit, first, last, normMin,
-                                        normMax - normMin);
-        }));
-        float **s = cur; cur = nxt; nxt = s;
-    }
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (flow_series arms its last launch)
+    NZ_TRY(flow_series(ctx, rw_geom(tile), work, iterations, normMin, normMax, tile->read, tile->write, nullptr));
     rw_swap(tile, true);
     return nz_ctx_finish(ctx, out);
 }

@@ -50,35 +50,59 @@ def test_dependency_on_another_contexts_handle_orders_the_streams(nj, ctx, oracl
         plane.Dispose()
 
 
-def test_handles_that_ride_on_a_launch_complete_with_it(nj, oracle):
-    # The stage entries of the metric pipeline hand out handles that ride on their last kernel launch (no event record of
-    # their own).  Producer (context A): noise -> Gauss5 x17 -> flow x5 -> erosion x5 on a READ / WRITE pair, ~0.2 ms of GPU
-    # work at 2048^2; consumer (context B): a copy of the result plane, enqueued at once with the LAST stage's handle as
-    # its dependency and no host wait in between -- a handle that completed before its kernel would copy a half-made plane.
-    # Then the same with the filter stage's handle and a copy of what the filter left.
-    res = 2048
-    want = oracle.pipeline(res, res, octaves=6, noise_size=500, xpos=11, zpos=-7)
-    want_f = oracle.kernel_filter(oracle.fractal(oracle.SIMPLEX, res, res, 0.4, 1.0, 2.0, 0.0, 6, 11, -7, 500), 2, 17)
+RIDE_RES = 2048
+# case: (the stages behind the noise stage, READ / WRITE pair or in place, what the oracle makes of the noise plane)
+RIDING = {
+    "pair-pipeline": (lambda nj, a: [nj.KernelFilterStage(a, nj.KernelFilterType.Gauss5_S1, 17),
+                                     nj.FlowMapStage(a, 5, 0.0, 0.005), nj.ErosionStage(a, 5)], True,
+                      lambda O, h: O.pipeline(RIDE_RES, RIDE_RES, octaves=6, noise_size=500, xpos=11, zpos=-7)),
+    "pair-gauss5x17": (lambda nj, a: [nj.KernelFilterStage(a, nj.KernelFilterType.Gauss5_S1, 17)], True,
+                       lambda O, h: O.kernel_filter(h, 2, 17)),
+}
+RIDING.update({"gauss5x%d" % it: (lambda nj, a, it=it: [nj.KernelFilterStage(a, nj.KernelFilterType.Gauss5_S1, it)], False,
+                                  lambda O, h, it=it: O.kernel_filter(h, 2, it)) for it in (1, 4, 17)})
+RIDING.update({"wide13x%d" % it: (lambda nj, a, it=it: [nj.StageGaussianBlur(a, it, nj.GaussSigma(4), 13)], False,
+                                  lambda O, h, it=it: O.gauss(h, 13, 4, it)) for it in (1, 2)})
+RIDING.update({"erosionx%d" % it: (lambda nj, a, it=it: [nj.ErosionStage(a, it)], False,
+                                   lambda O, h, it=it: O.erosion_min(h, it)) for it in (1, 9)})
+RIDING.update({"flowx%d" % it: (lambda nj, a, it=it: [nj.FlowMapStage(a, it, 0.0, 0.005)], False,
+                                lambda O, h, it=it: O.flowmap(h, it, 0.0, 0.005)) for it in (1, 7)})
+
+
+@pytest.fixture(scope="module")
+def ride_noise(oracle):
+    return oracle.fractal(oracle.SIMPLEX, RIDE_RES, RIDE_RES, 0.4, 1.0, 2.0, 0.0, 6, 11, -7, 500)
+
+
+@pytest.mark.parametrize("case", list(RIDING))
+def test_handles_that_ride_on_a_launch_complete_with_it(nj, oracle, ride_noise, case):
+    # The stage entries hand out handles that ride on the operation that ends them -- their last kernel launch, or the copy
+    # back behind an odd number of in-place launches -- with no event record of their own.  Producer (context A): noise,
+    # then the case's stages, on a READ / WRITE pair (noise -> Gauss5 x17 -> flow x5 -> erosion x5 is ~0.2 ms of GPU work at
+    # 2048^2) or in place; consumer (context B): a copy of the result plane, enqueued at once with the LAST stage's handle
+    # as its dependency and no host wait in between -- a handle that completed before its kernel would copy a half-made
+    # plane.  In place: one launch and a copy back (x1), an even count (Gauss5 x4, erosion x9, wide x2), an even count of
+    # fused launches (x17), two flow launches through the private height copy (flow x7).
+    make, pair, expect = RIDING[case]
+    res = RIDE_RES
+    want = expect(oracle, ride_noise)
     with nj.Context(0) as a, nj.Context(0) as b:
         p0, p1, snap = a.alloc(res * res), a.alloc(res * res), b.alloc(res * res)
-        stages = [nj.NoiseStage(a, nj.FractalNoise.Simplex, 0.4, 1.0, 6, 2.0, 0.0, 500),
-                  nj.KernelFilterStage(a, nj.KernelFilterType.Gauss5_S1, 17), nj.FlowMapStage(a, 5, 0.0, 0.005),
-                  nj.ErosionStage(a, 5)]
-        for upto, expect in ((4, want), (2, want_f)):
-            for rep in range(4):  # repeated: a race would not lose every time
-                b.call("nz_fill_array", snap.ptr, res, float("nan"))
-                b.synchronize()
-                d = nj.GeneratorData("x", p0, res, 11, -7, write=p1)
-                h = nj.JobHandle()
-                for st in stages[:upto]:
-                    st.Schedule(nj.PipelineWorkItem(d), h)
-                    h = st.jobHandle
-                assert h.id != 0
-                done = b.call("nz_flush_write_slice", snap.ptr, d.data.ptr, res * res, dep=h)
-                done.Complete()
-                assert h.IsCompleted
-                assert np.array_equal(snap.ToArray((res, res)), expect), (upto, rep)
-                assert a.elapsed_ms(stages[0].jobHandle, h) > 0.0  # the riding events carry time stamps like recorded ones
+        stages = [nj.NoiseStage(a, nj.FractalNoise.Simplex, 0.4, 1.0, 6, 2.0, 0.0, 500)] + make(nj, a)
+        for rep in range(4):  # repeated: a race would not lose every time
+            b.call("nz_fill_array", snap.ptr, res, float("nan"))
+            b.synchronize()
+            d = nj.GeneratorData("x", p0, res, 11, -7, write=p1 if pair else None)
+            h = nj.JobHandle()
+            for st in stages:
+                st.Schedule(nj.PipelineWorkItem(d), h)
+                h = st.jobHandle
+            assert h.id != 0
+            done = b.call("nz_flush_write_slice", snap.ptr, d.data.ptr, res * res, dep=h)
+            done.Complete()
+            assert h.IsCompleted
+            assert np.array_equal(snap.ToArray((res, res)), want), (case, rep)
+            assert a.elapsed_ms(stages[0].jobHandle, h) > 0.0  # the riding events carry time stamps like recorded ones
         for st in stages:
             st.OnDestroy()
         for t in (p0, p1, snap):
