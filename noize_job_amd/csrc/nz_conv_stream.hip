@@ -59,6 +59,13 @@ template <bool FAST>
 __device__ __forceinline__ float cs_acc(float total, float v, float k) {
     return FAST ? __builtin_fmaf(v, k, total) : total + v * k;
 }
+// the first tap: the Z sums of the last stage, whose results are stored, start from +0 as the reference's (an all -0 sum is
+// +0); FAST seeds every pass -- the rule and its reasons are tap_first's (nz_filter.hip).  (`seed` is a constant: the stage
+// loop is unrolled.)
+template <bool FAST>
+__device__ __forceinline__ float cs_first(float v, float k, bool seed) {
+    return FAST ? __builtin_fmaf(v, k, 0.0f) : seed ? 0.0f + v * k : v * k;
+}
 
 template <int KS, int T, bool UNIT, bool COND, bool XEDGE, bool FAST>
 __device__ __forceinline__ void cs_step(float (&X)[T][KS - 1][2], const int t, const float2 vin, const cs_bounds<T> &b,
@@ -98,7 +105,7 @@ __device__ __forceinline__ void cs_step(float (&X)[T][KS - 1][2], const int t, c
                 w[O + 1] = v[1];
 #pragma unroll
                 for (int e = 0; e < 2; e++) {
-                    float total = w[e] * taps.kx[0];  // 0 + a*b == a*b
+                    float total = cs_first<FAST>(w[e], taps.kx[0], false);
 #pragma unroll
                     for (int kk = 1; kk < KS; kk++) total = cs_acc<FAST>(total, w[e + kk], taps.kx[kk]);
                     xn[e] = UNIT ? total : total * taps.factor;
@@ -120,7 +127,7 @@ __device__ __forceinline__ void cs_step(float (&X)[T][KS - 1][2], const int t, c
             if (em) {
 #pragma unroll
                 for (int e = 0; e < 2; e++) {
-                    float total = xn[e] * taps.kz[0];
+                    float total = cs_first<FAST>(xn[e], taps.kz[0], j == T - 1);
 #pragma unroll
                     for (int kk = 1; kk < KS; kk++) total = cs_acc<FAST>(total, X[j][HW - kk][e], taps.kz[kk]);
                     out[e] = UNIT ? total : total * taps.factor;

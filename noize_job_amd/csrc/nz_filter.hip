@@ -139,6 +139,16 @@ template <bool FAST>
 __device__ __forceinline__ float tap_acc(float total, float v, float k) {
     return FAST ? __builtin_fmaf(v, k, total) : total + v * k;
 }
+// ... and its first tap.  The reference starts every sum from +0 (`total = 0; total += v * k`), so a sum whose products
+// are all -0 (a plane of -0, negative products that underflow, zeros under negative taps) is +0; v * k alone keeps the -0.
+// A sum seeded with +0 is never -0 again (x + y is -0 only when both are), and no nonzero value depends on the sign of a
+// zero, so in strict mode only the sums whose zeros leave the kernel need the seed: the last Z pass of a launch (SEED).
+// The X pass and the Z passes before it may keep their -0s.  FAST seeds every pass through the FMA at no cost:
+// fmaf(v, k, +0) is -0 where a negative product underflows, and the FMAs after it would carry that -0 on.
+template <bool FAST, bool SEED>
+__device__ __forceinline__ float tap_first(float v, float k) {
+    return FAST ? __builtin_fmaf(v, k, 0.0f) : SEED ? 0.0f + v * k : v * k;
+}
 
 template <int KS, bool UNIT, int NT, bool SC1, bool FAST, int RBT>
 __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *__restrict__ dst, const nz_geom &g,
@@ -222,7 +232,7 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
             }
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                float total = w[e] * taps.kx[0];  // 0 + a*b == a*b
+                float total = tap_first<FAST, false>(w[e], taps.kx[0]);
 #pragma unroll
                 for (int kk = 1; kk < KS; kk++) total = tap_acc<FAST>(total, w[e + kk], taps.kx[kk]);
                 v[r][e] = UNIT ? total : total * taps.factor;
@@ -280,13 +290,22 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
         for (int r = 0; r < RBT; r++) {
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                float total = z[r + 2 * O][e] * taps.kz[0];
+                float total = tap_first<FAST, !UNIT>(z[r + 2 * O][e], taps.kz[0]);
 #pragma unroll
                 for (int kk = 1; kk < KS; kk++) total = tap_acc<FAST>(total, z[r + 2 * O - kk][e], taps.kz[kk]);
                 v[r][e] = UNIT ? total : total * taps.factor;
             }
         }
         NZ_PROBE_T(1 + t);
+    }
+
+    // strict: the launch's last Z sums seeded with +0 (tap_first).  With the factor applied after every Z pass, the scaled
+    // forms seed every Z pass (T is not known at compile time); a UNIT sum's seed is this one add: -0 + 0 == +0, x + 0 == x.
+    if constexpr (UNIT && !FAST) {
+#pragma unroll
+        for (int r = 0; r < RBT; r++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) v[r][e] += 0.0f;
     }
 
     // ---- store the interior
@@ -677,7 +696,7 @@ __global__ __launch_bounds__(WD_NT) void conv_wide_kernel(const float *__restric
             float o[8];
 #pragma unroll
             for (int e = 0; e < 8; e++) {
-                float total = w[SH + e] * taps.kx[0];  // 0 + a*b == a*b
+                float total = tap_first<FAST, false>(w[SH + e], taps.kx[0]);
 #pragma unroll
                 for (int kk = 1; kk < KS; kk++) total = tap_acc<FAST>(total, w[SH + e + kk], taps.kx[kk]);
                 o[e] = UNIT ? total : total * taps.factor;
@@ -708,7 +727,7 @@ __global__ __launch_bounds__(WD_NT) void conv_wide_kernel(const float *__restric
             float o[2];
 #pragma unroll
             for (int e = 0; e < 2; e++) {
-                float total = v[j + 2 * O][e] * taps.kz[0];
+                float total = tap_first<FAST, true>(v[j + 2 * O][e], taps.kz[0]);
 #pragma unroll
                 for (int kk = 1; kk < KS; kk++) total = tap_acc<FAST>(total, v[j + 2 * O - kk][e], taps.kz[kk]);
                 o[e] = UNIT ? total : total * taps.factor;
@@ -739,7 +758,7 @@ __global__ __launch_bounds__(WD_NT) void conv_wide_kernel(const float *__restric
             float o[4];
 #pragma unroll
             for (int e = 0; e < 4; e++) {
-                float total = v[j + 2 * O][e] * taps.kz[0];
+                float total = tap_first<FAST, true>(v[j + 2 * O][e], taps.kz[0]);
 #pragma unroll
                 for (int kk = 1; kk < KS; kk++) total = tap_acc<FAST>(total, v[j + 2 * O - kk][e], taps.kz[kk]);
                 o[e] = UNIT ? total : total * taps.factor;

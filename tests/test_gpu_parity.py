@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import adversarial_tiles, assert_parity
+from conv_ref import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
@@ -122,7 +123,7 @@ def test_kernel_filter_delegate_matches_oracle(nj, ctx, oracle, ft):
     for name, t in adversarial_tiles(res).items():
         d = gen(nj, ctx, res, host=t)
         got = run(nj.KernelFilterStage(ctx, nj.KernelFilterType(ft), 1), nj, d)
-        assert np.array_equal(got, oracle.kernel_filter(t, ft)), (ft, name)
+        assert_bits_equal(got, oracle.kernel_filter(t, ft), (ft, name))
         d.data.Dispose()
 
 
@@ -138,7 +139,7 @@ def test_kernel_filter_stage_iterations(nj, ctx, oracle, ft, iters):
             got = run(nj.KernelFilterStage(ctx, nj.KernelFilterType(ft), iters), nj, d)
             want = oracle.kernel_filter(tiles[name], ft, iters)
             assert_parity(got, want, "ft=%d it=%d res=%d %s" % (ft, iters, res, name))
-            assert np.array_equal(got, want), "ft=%d it=%d res=%d %s not bit-equal" % (ft, iters, res, name)
+            assert_bits_equal(got, want, "ft=%d it=%d res=%d %s" % (ft, iters, res, name))
             d.data.Dispose()
 
 
@@ -147,10 +148,10 @@ def test_sobel_2d_runs_both_filters_and_reduces(nj, ctx, oracle, res, iters):
     # SeparableKernelFilter.ScheduleReduce<RootSumSquaresTiles> (KernelJob.cs:187-215)
     t = np.random.default_rng(res).random((res, res), dtype=f32)
     got = run(nj.KernelFilterStage(ctx, nj.KernelFilterType.Sobel3_2D, iters), nj, gen(nj, ctx, res, host=t))
-    assert np.array_equal(got, oracle.kernel_filter(t, oracle.SOBEL3_2D, iters))
+    assert_bits_equal(got, oracle.kernel_filter(t, oracle.SOBEL3_2D, iters))
     flat = np.full((res, res), 0.25, f32)       # no gradient anywhere, clamped borders included
     got = run(nj.KernelFilterStage(ctx, nj.KernelFilterType.Sobel3_2D, 1), nj, gen(nj, ctx, res, host=flat))
-    assert np.array_equal(got, np.zeros((res, res), f32))
+    assert_bits_equal(got, np.zeros((res, res), f32))
 
 
 def test_edge_filter_delegates(nj, ctx, oracle):
@@ -162,13 +163,13 @@ def test_edge_filter_delegates(nj, ctx, oracle):
             src, tmp = ctx.from_host(t), ctx.alloc(res * res)
             ctx.call("nz_edge_1d_filter", src.ptr, tmp.ptr, algo, dirn, res).Complete()
             kx, kz, _, _ = oracle.kernel_filter_table(ft)
-            assert np.array_equal(src.ToArray((res, res)), oracle.separable(t, 3, kx, kz, 1.0)), (algo, dirn)
+            assert_bits_equal(src.ToArray((res, res)), oracle.separable(t, 3, kx, kz, 1.0), (algo, dirn))
         src, tmp = ctx.from_host(t), ctx.alloc(res * res)
         ctx.call("nz_edge_2d_filter", src.ptr, tmp.ptr, algo, res).Complete()
         hx, hz, _, _ = oracle.kernel_filter_table(fh)
         vx, vz, _, _ = oracle.kernel_filter_table(fv)
         want = oracle.reduce(oracle.separable(t, 3, hx, hz, 1.0), oracle.separable(t, 3, vx, vz, 1.0), 2)
-        assert np.array_equal(src.ToArray((res, res)), want), algo
+        assert_bits_equal(src.ToArray((res, res)), want, algo)
     with pytest.raises(nj.NoizeError):
         ctx.call("nz_edge_2d_filter", src.ptr, tmp.ptr, 2, res)
 
@@ -181,7 +182,7 @@ def test_gaussian_blur_stage(nj, ctx, oracle, sigma, width, iters):
     d = gen(nj, ctx, res, host=t)
     got = run(nj.StageGaussianBlur(ctx, iters, nj.GaussSigma(sigma), width), nj, d)
     want = oracle.gauss(t, oracle.limit_width(width), sigma, iters)  # the stage passes limitWidth(width)
-    assert np.array_equal(got, want)
+    assert_bits_equal(got, want)
 
 
 @pytest.mark.parametrize("width", [11, 13, 15, 17, 19, 21, 23, 25])
@@ -192,13 +193,13 @@ def test_wide_blur_kernels_interior_and_edge_tiles(nj, ctx, oracle, width):
         t = np.random.default_rng(width * 1000 + res).random((res, res), dtype=f32)
         d = gen(nj, ctx, res, host=t)
         got = run(nj.StageGaussianBlur(ctx, iters, nj.GaussSigma(width % 16), width), nj, d)
-        assert np.array_equal(got, oracle.gauss(t, width, width % 16, iters))
+        assert_bits_equal(got, oracle.gauss(t, width, width % 16, iters))
         d.data.Dispose()
     res = 300
     t = np.random.default_rng(width).random((res, res), dtype=f32)
     d = gen(nj, ctx, res, host=t)
     got = run(nj.StageSmoothBlur(ctx, 3, width), nj, d)   # factor 1, taps 1/width; odd count: copy back
-    assert np.array_equal(got, oracle.smooth(t, width, 3))
+    assert_bits_equal(got, oracle.smooth(t, width, 3))
     d.data.Dispose()
 
 
@@ -208,7 +209,7 @@ def test_gauss_filter_delegate_even_width_quirk(nj, ctx, oracle):
     t = adversarial_tiles(res)["uniform"]
     src, tmp = ctx.from_host(t), ctx.alloc(res * res)
     ctx.call("nz_gauss_filter", src.ptr, tmp.ptr, 4, 3, res).Complete()
-    assert np.array_equal(src.ToArray((res, res)), oracle.gauss(t, 4, 3))
+    assert_bits_equal(src.ToArray((res, res)), oracle.gauss(t, 4, 3))
     with pytest.raises(nj.NoizeError):
         ctx.call("nz_gauss_filter", src.ptr, tmp.ptr, 40, 3, res)  # indexes outside the 25-tap body
 
@@ -219,7 +220,7 @@ def test_smooth_blur_stage(nj, ctx, oracle, width, iters):
     t = adversarial_tiles(res)["uniform"]
     d = gen(nj, ctx, res, host=t)
     got = run(nj.StageSmoothBlur(ctx, iters, width), nj, d)
-    assert np.array_equal(got, oracle.smooth(t, width, iters))
+    assert_bits_equal(got, oracle.smooth(t, width, iters))
 
 
 def test_separable_series_custom_kernels(nj, ctx, oracle):
@@ -230,7 +231,7 @@ def test_separable_series_custom_kernels(nj, ctx, oracle):
     src, tmp = ctx.from_host(t), ctx.alloc(res * res)
     ctx.call("nz_separable_series", src.ptr, tmp.ptr, res, 5, kx.ctypes.data_as(nj._native.f32p),
              kz.ctypes.data_as(nj._native.f32p), 0.37).Complete()
-    assert np.array_equal(src.ToArray((res, res)), oracle.separable(t, 5, kx, kz, 0.37))
+    assert_bits_equal(src.ToArray((res, res)), oracle.separable(t, 5, kx, kz, 0.37))
 
 
 @pytest.mark.parametrize("iters", [1, 2, 3, 5, 8, 16, 33])

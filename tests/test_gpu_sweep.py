@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+from conv_ref import assert_bits_equal
+
 pytestmark = pytest.mark.gpu
 f32 = np.float32
 
@@ -46,13 +48,13 @@ def test_filters_erosion_flow_random_sizes(nj, ctx, oracle, seed):
         ft = int(rng.choice([0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13]))
         it = int(rng.integers(1, 12)) if ft != 11 else int(rng.integers(1, 3))
         got = _run(nj, nj.KernelFilterStage(ctx, nj.KernelFilterType(ft), it), nj.GeneratorData("k", ctx.from_host(t), res))
-        assert np.array_equal(got, oracle.kernel_filter(t, ft, it)), ("filter", res, ft, it)
+        assert_bits_equal(got, oracle.kernel_filter(t, ft, it), ("filter", res, ft, it))
         width, sigma, it = int(rng.integers(1, 27)), int(rng.integers(0, 16)), int(rng.integers(1, 4))
         got = _run(nj, nj.StageGaussianBlur(ctx, it, nj.GaussSigma(sigma), width), nj.GeneratorData("g", ctx.from_host(t), res))
-        assert np.array_equal(got, oracle.gauss(t, oracle.limit_width(width), sigma, it)), ("gauss", res, width, sigma, it)
+        assert_bits_equal(got, oracle.gauss(t, oracle.limit_width(width), sigma, it), ("gauss", res, width, sigma, it))
         width, it = int(rng.integers(1, 26)), int(rng.integers(1, 4))
         got = _run(nj, nj.StageSmoothBlur(ctx, it, width), nj.GeneratorData("s", ctx.from_host(t), res))
-        assert np.array_equal(got, oracle.smooth(t, oracle.limit_width(width), it)), ("smooth", res, width, it)  # the stage passes limitWidth(width)
+        assert_bits_equal(got, oracle.smooth(t, oracle.limit_width(width), it), ("smooth", res, width, it))  # the stage passes limitWidth(width)
         it = int(rng.integers(1, 14))
         got = _run(nj, nj.ErosionStage(ctx, it), nj.GeneratorData("e", ctx.from_host(t), res))
         assert np.array_equal(got, oracle.erosion_min(t, it)), ("erosion", res, it)
@@ -120,9 +122,9 @@ def test_non_finite_cells_propagate_like_the_oracle(nj, ctx, oracle, seed):
         t[-1, -1] = np.inf
         eq = lambda a, b: np.array_equal(a, b, equal_nan=True)  # noqa: E731
         got = _run(nj, nj.KernelFilterStage(ctx, nj.KernelFilterType.Gauss5_S1, 4), nj.GeneratorData("k", ctx.from_host(t), res))
-        assert eq(got, oracle.kernel_filter(t, 2, 4)), ("filter", res)
+        assert_bits_equal(got, oracle.kernel_filter(t, 2, 4), ("filter", res))
         got = _run(nj, nj.StageGaussianBlur(ctx, 1, nj.GaussSigma(3), 21), nj.GeneratorData("g", ctx.from_host(t), res))
-        assert eq(got, oracle.gauss(t, 21, 3, 1)), ("wide blur", res)
+        assert_bits_equal(got, oracle.gauss(t, 21, 3, 1), ("wide blur", res))
         for it in (1, 3, 6):
             got = _run(nj, nj.ErosionStage(ctx, it), nj.GeneratorData("e", ctx.from_host(t), res))
             assert eq(got, oracle.erosion_min(t, it)), ("erosion", res, it)
@@ -215,7 +217,7 @@ def test_stripe_entry_points_random_geometry_and_pitch(nj, ctx, oracle, seed):
         st = nj.Stripe(cols, rows, b0, grows, g0 - b0, g1 - b0, pitch)
         ctx.call("nz_kernel_filter_stripe", src.ptr, dst.ptr, C.byref(st), ft, T).Complete()
         out = dst.ToArray((rows, pitch))
-        assert np.array_equal(out[g0 - b0:g1 - b0, :cols], want[g0:g1]), ("conv", cols, grows, pitch, ft, T, g0, g1)
+        assert_bits_equal(out[g0 - b0:g1 - b0, :cols], want[g0:g1], ("conv", cols, grows, pitch, ft, T, g0, g1))
         assert np.isnan(out[:g0 - b0]).all() and np.isnan(out[g1 - b0:]).all() and np.isnan(out[:, cols:]).all()
         # erosion: E applications reach E rows upwards only
         E = int(rng.integers(1, 1 + nj._native.lib.nz_erosion_max_fused_iterations()))
@@ -252,7 +254,7 @@ def test_chained_filter_launches_tolerate_a_straggling_tile(nj, ctx, oracle):
             gd = nj.GeneratorData("t", data, res, 0, 0, write=write)
             stage.ReceiveHandledInput(nj.PipelineWorkItem(gd), nj.JobHandle())
             stage.jobHandle.Complete()
-            assert np.array_equal(gd.data.ToArray((res, res)), want), item
+            assert_bits_equal(gd.data.ToArray((res, res)), want, item)
     finally:
         lib.nz_debug_chain_delay(-1, 0)
     stage.OnDestroy()
