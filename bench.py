@@ -14,6 +14,7 @@ erosion x5) over one device-resident grid; nothing crosses PCIe inside the timed
           data-path communication); it is reported beside the headline in `grid_16384`.
   `python bench.py --gpus N` without a launcher starts its own: N ranks through torch.distributed.run, before
   this process touches the GPU, and relays rank 0's line.
+A plain run does what the headline needs and no more: set-up, warm-up, the K timed steps, --dump-outputs, the line.
 Rank 0 prints ONE JSON line:
   * `stages`  : per stage, launch time from HIP events recorded on the kernels' stream inside the timed steps, and
                 -- from the counter summary profiles/*_counters.json that belongs to THESE kernel sources -- the
@@ -21,8 +22,12 @@ Rank 0 prints ONE JSON line:
   * `roofline`: the kernel with the largest share of the step under the bound that limits it (frac <= 1).
   * `pipeline_hbm`: the 400 B/cell algorithmic-equivalent figure of SURVEY.md 8(d) (exceeds the HBM peak by design:
                 filter / flow iterations are fused on chip, so it is not a roofline).
+With --full, beside these, every measurement and check that runs outside the timed steps:
+  * `cold_ms` and `literal_command`: one step from an idle chip, and the command taken literally (no preheat).
   * `cpu_baseline`: the CPU oracle (reference-shaped restatement of the Burst jobs) timed on this box's host cores,
-                and `verified`: the device plane of the last timed step compared with the oracle's plane, bit for bit.
+                and `verified`: the device plane of the last timed step compared with the oracle's plane, bit for bit
+                (sharded runs: the rows every rank owns against the oracle's rows of the monolithic grid).
+  * `float_modes`, `in_place_entries`, `two_tiles_in_flight`: the other float modes, flush form and tile concurrency.
   * `grid_16384`: BASELINE config 5's grid split over the N ranks (N = 1: the whole grid on one GPU) -- the strong-
                 scaling quantity the >= 6x target is defined on -- with ghost rows recomputed and, at N > 1, exchanged.
 """
@@ -84,9 +89,15 @@ def parse():
                     help="rows per rank at N>1 (0: --grid / N, strong scaling; a fixed count gives weak scaling)")
     ap.add_argument("--cols", type=int, default=16384, help="grid columns at N>1")
     ap.add_argument("--grid", type=int, default=16384,
-                    help="side of the strong-scaling grid reported as grid_16384 at every N (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the informational measurements after the timed steps")
+                    help="--full: side of the strong-scaling grid reported as grid_16384 at every N (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, every measurement and check outside the timed steps: the cold step and the "
+                         "literal command, the CPU baseline and the oracle comparison, the other float modes, the in-place "
+                         "and two-tile forms, the --grid strong-scaling grid (a plain run: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline and the comparisons with the oracle")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the informational measurements after the timed steps")
     ap.add_argument("--sharded", action="store_true", help="run the row-stripe path even with one rank (rehearsal)")
     ap.add_argument("--halo", choices=("recompute", "exchange", "exchange_once"), default=None,
                     help="N>1 (default exchange): ghost rows exchanged with the neighbour ranks over RCCL before every "
@@ -560,6 +571,10 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if args.halo is None:
         args.halo = "exchange" if world > 1 else "recompute"
+    # a plain run times the headline and nothing else; --full adds the checks against the oracle and the informational
+    # measurements, which --no-cpu-baseline / --no-extras narrow
+    checks = args.full and not args.no_cpu_baseline
+    extras = args.full and not args.no_extras
     # stdout carries the ONE JSON line only: whatever libraries print while they initialise (RCCL's version
     # banner under NCCL_DEBUG=VERSION) is sent to stderr
     sys.stdout.flush()
@@ -683,7 +698,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if not sharded:
+    if args.full and not sharded:
         # first-tile latency: what a tile server sees for a request that finds the chip idle (code objects loaded and
         # buffers allocated by one untimed pass, then half a second of idleness for the clocks to fall back)
         step(False)
@@ -707,7 +722,7 @@ def main():
     gc.disable()
     preheat = max(0, PREHEAT_MIN_STEPS - args.warmup)
     literal = None
-    if preheat > 0:
+    if args.full and preheat > 0:
         # The command exactly as given -- W warm-ups, then K timed steps, from a chip that has been idle for half a second,
         # no preheat: reported as `literal_command` beside the steady-state headline (whose `warmup_effective` says what ran)
         fence()
@@ -785,15 +800,16 @@ def main():
               file=sys.stderr)
     exchange_ms = host_enqueue_ms = host_idle_ms = None
     if sharded:
-        # the host's own cost of enqueueing a step, measured where the queue cannot push back: eight steps on an idle
-        # stream, each call timed on its own (the timed steps above run against a full queue)
-        probe = []
-        for _ in range(8):
-            h0 = time.perf_counter()
-            step(False)
-            probe.append(time.perf_counter() - h0)
-        fence()
-        host_idle_ms = sorted(probe)[len(probe) // 2] * 1e3
+        if args.full:
+            # the host's own cost of enqueueing a step, measured where the queue cannot push back: eight steps on an idle
+            # stream, each call timed on its own (the timed steps above run against a full queue)
+            probe = []
+            for _ in range(8):
+                h0 = time.perf_counter()
+                step(False)
+                probe.append(time.perf_counter() - h0)
+            fence()
+            host_idle_ms = sorted(probe)[len(probe) // 2] * 1e3
         ex = 0.0
         if timed_exchanges:
             ex = (grid.exchange_ms() if grid is not None else comm.total_ms()) / ex_steps
@@ -872,15 +888,15 @@ def main():
                                    "every wait, max over ranks); 0 ghost-row traffic with --halo recompute; "
                                    "host_enqueue_ms_per_step = host time inside the step's enqueue calls during the timed steps "
                                    "(max over ranks; includes the time the full command queue pushes back); "
-                                   "host_enqueue_ms_idle_queue = the same call on an idle stream (median of 8, rank 0): the "
+                                   "host_enqueue_ms_idle_queue = the same call on an idle stream (--full; median of 8, rank 0): the "
                                    "host's own cost -- the step is host-bound if THIS approaches ms_per_step"}
             out["comm"]["ranks"] = rank_reports
             out["config"]["strong_scaling"] = (
-                "the same %dx%d grid at every N; denominator = `grid_%d`.recompute of the N = 1 line (the whole grid on one "
-                "GPU)" % (plan.grows, plan.cols, plan.grows)) if strong else None
+                "the same %dx%d grid at every N; denominator = `grid_%d`.recompute of the N = 1 line of bench.py --full (the "
+                "whole grid on one GPU)" % (plan.grows, plan.cols, plan.grows)) if strong else None
         else:
             out["config"]["strong_scaling"] = ("this N = 1 line is the 4096^2 metric tile; the N > 1 lines run the %d^2 grid "
-                                               "split over the ranks, whose one-GPU figure is `grid_%d` below" %
+                                               "split over the ranks, whose one-GPU figure is `grid_%d` (bench.py --full)" %
                                                (args.grid, args.grid)) if args.grid else None
         if cold_ms is not None:
             out["cold_ms"] = round(cold_ms, 4)
@@ -925,8 +941,11 @@ def main():
         for n, note in stage_note.items():
             stages_out[n]["note"] = note
         # The in-place tile API's one-launch flow stage ends with a plane copy back into the caller's buffer (and the
-        # in-place erosion with none: two launches): time that copy on its own so the flow KERNEL's time is known
-        if not pingpong and flow_launches == 1:
+        # in-place erosion with none: two launches): time that copy on its own so the flow KERNEL's time is known (--full;
+        # a plain run leaves the copy inside the flow stage's time and says so with copy_back_ms = None)
+        if not pingpong and flow_launches == 1 and not args.full:
+            stages_out["flow"]["copy_back_ms"] = None
+        elif not pingpong and flow_launches == 1:
             scratch = ctx.alloc(rcells)
             hc0 = ctx.record()
             for _ in range(20):
@@ -1010,7 +1029,7 @@ def main():
 
     if rank == 0 and marks:
         out.update(analyse(marks, args.float_mode, ms_per_step))
-    if rank == 0 and not args.no_cpu_baseline and not sharded:
+    if rank == 0 and checks and not sharded:
         cres = args.cpu_res or res
         out["cpu_baseline"], plane = cpu_baseline(cres)
         if cres == res:
@@ -1031,8 +1050,8 @@ def main():
                     "max_abs_diff": float(np.abs(got.reshape(res, res) - plane).max())})
         else:
             out["verified"] = None
-    plane_oracle = plane if (rank == 0 and not args.no_cpu_baseline and not sharded and (args.cpu_res or res) == res) else None
-    if sharded and grid is not None and not args.no_cpu_baseline:
+    plane_oracle = plane if (rank == 0 and checks and not sharded and (args.cpu_res or res) == res) else None
+    if sharded and grid is not None and checks:
         # every rank: the rows it owns after the last timed pass against the CPU oracle's rows of the monolithic grid
         if args.as_rank is not None and args.halo != "recompute":
             ver = {"verified": None, "note": "rehearsal with exchanged ghost rows: the neighbour ranks are played by the rank "
@@ -1043,7 +1062,7 @@ def main():
         if rank == 0:
             out["verified"] = ver.pop("verified")
             out["verified_detail"] = ver
-    if rank == 0 and not sharded and not args.no_extras:
+    if rank == 0 and not sharded and extras:
         # the other float modes beside the headline: the same step on the same planes, 100 timed steps after 30 untimed ones,
         # then 40 marked steps for the stage times; the plane each mode leaves is compared with the oracle's
         modes_out = {}
@@ -1092,7 +1111,6 @@ def main():
             "differentiates the filtered heights (neighbours 1e-3 apart, each known to 6e-8), so one ulp in its input plane moves "
             "its output by ~1e-4 relative -- as between any two FloatMode.Fast builds of the reference")
         out["float_modes"] = modes_out
-    extras = not args.no_extras
     if rank == 0 and extras and not sharded:
         # informational, outside the timed steps; never allowed to cost the JSON line: an exception is recorded, and
         # should one of them ever block, a watchdog prints the line without them and ends the process
@@ -1126,7 +1144,7 @@ def main():
         if not sharded:  # N = 1 without a process group: the whole grid as one stripe
             g = None
             try:
-                g = strong_grid(nj, sh, torch, None, ctx, args.grid, 0, 1, impl=args.impl, verify=not args.no_cpu_baseline,
+                g = strong_grid(nj, sh, torch, None, ctx, args.grid, 0, 1, impl=args.impl, verify=checks,
                                 strict=args.float_mode == "strict")
             except Exception as e:  # noqa: BLE001  (e.g. not enough free memory next to other processes)
                 g = {"error": "%s: %s" % (type(e).__name__, e)}
@@ -1135,7 +1153,7 @@ def main():
             if args.impl == "native" and ncomm is None and world > 1:
                 ncomm = make_native_comm(sh, torch, dist, ctx, rank, world)
             g = strong_grid(nj, sh, torch, dist, ctx, args.grid, rank, world, impl=args.impl, ncomm=ncomm,
-                            verify=not args.no_cpu_baseline, strict=args.float_mode == "strict")
+                            verify=checks, strict=args.float_mode == "strict")
             if rank == 0:
                 out["grid_%d" % args.grid] = g
     if sharded:

@@ -1,5 +1,6 @@
-"""bench.py keeps its contract: ONE JSON line on stdout with the metric, the roofline of the dominant
-kernel (measured with HIP events inside the timed steps) and the CPU baseline."""
+"""bench.py keeps its contract: ONE JSON line on stdout with the metric and the roofline of the dominant
+kernel (measured with HIP events inside the timed steps); with --full also the CPU baseline, the checks against
+the oracle and the informational measurements."""
 import json
 import os
 import subprocess
@@ -23,7 +24,7 @@ def _run(*args):
 
 
 def test_single_gpu_line():
-    d = _run("--steps", "6", "--warmup", "2", "--res", "1024", "--grid", "2048")
+    d = _run("--full", "--steps", "6", "--warmup", "2", "--res", "1024", "--grid", "2048")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "verified", "cold_ms"):
         assert key in d, key
@@ -70,25 +71,39 @@ def test_single_gpu_line():
     assert all(v["cells_outside"] == 0 for v in fm["fast"]["stages_vs_oracle"].values())
 
 
+def test_plain_line_is_the_headline_only():
+    # without --full: set-up, warm-up, the timed steps and the line -- the same headline fields, nothing that needs runs
+    # of its own or the oracle
+    d = _run("--steps", "6", "--warmup", "2", "--res", "1024", "--grid", "2048")
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "Mcells/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["metric"].startswith("Mcells/s 4096^2")
+    assert d["value"] == pytest.approx(d["config"]["cells"] / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    assert d["warmup_effective"] == 50 and d["config"]["preheat_steps"] == 48
+    assert set(d["stages"]) == {"noise", "gauss", "flow", "erosion"} and d["roofline"]["stage"] in d["stages"]
+    for key in ("cpu_baseline", "verified", "cold_ms", "literal_command", "float_modes", "in_place_entries",
+                "two_tiles_in_flight", "grid_2048"):
+        assert key not in d, key
+
+
 def test_a_wrong_plane_fails_the_run():
     # debug hook: one cell of the downloaded plane is changed before it is compared with the oracle's -> the line is still
     # printed (verified: false, with the count), and the process does NOT exit 0
     env = dict(os.environ, NZ_BENCH_FLIP_CELL="1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--res", "512",
-                          "--grid", "0", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--res",
+                          "512", "--grid", "0", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["verified"] is False and d["verified_detail"]["cells_outside_1e-5_rel"] == 1
     assert out.returncode not in (0, None) and "FAILED" in out.stderr
     # the same command without the hook is clean
-    ok = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--res", "512",
-                         "--grid", "0", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    ok = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--res",
+                         "512", "--grid", "0", "--no-extras"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert ok.returncode == 0 and json.loads(ok.stdout.strip())["verified"] is True
 
 
 def test_stripe_rehearsal_line():
-    d = _run("--steps", "4", "--warmup", "1", "--as-rank", "1", "4", "--stripe-rows", "256", "--cols", "1024")
+    d = _run("--full", "--steps", "4", "--warmup", "1", "--as-rank", "1", "4", "--stripe-rows", "256", "--cols", "1024")
     assert d["n_gpus"] == 1 and "cpu_baseline" not in d and "roofline" in d
     assert "rehearsal of rank 1 of 4" in d["config"]["parallelism"] and d["config"]["cells"] == 256 * 1024
     # the rank's owned rows (global rows 256 .. 511 of the 1024-row grid) equal the oracle's rows of the monolithic grid
@@ -110,7 +125,7 @@ def test_launched_like_the_driver_at_n_gt_1(halo):
         out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                               "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                               "--gpus", "1", "--sharded", "--halo", halo, "--steps", "4", "--warmup", "1",
-                              "--stripe-rows", "384", "--cols", "1024", "--grid", "1024", "--no-cpu-baseline"],
+                              "--stripe-rows", "384", "--cols", "1024", "--grid", "1024", "--full", "--no-cpu-baseline"],
                              capture_output=True, text=True, timeout=380, cwd=ROOT)
         if out.returncode == 0 or "EADDRINUSE" not in out.stderr:
             break
@@ -139,8 +154,8 @@ def _self_launched(*args):
 def test_bench_starts_its_own_ranks_one_rank():
     # the one-GPU box drives the self-launch path with one rank: RCCL process group, stripe schedule, exchanges with
     # the rank's own neighbours absent (first and last stripe at once), `comm` in the line
-    d = _self_launched("--gpus", "1", "--sharded", "--self-launch", "--steps", "4", "--warmup", "1", "--stripe-rows", "384",
-                       "--cols", "1024", "--grid", "1024", "--halo", "exchange")
+    d = _self_launched("--gpus", "1", "--sharded", "--self-launch", "--full", "--steps", "4", "--warmup", "1", "--stripe-rows",
+                       "384", "--cols", "1024", "--grid", "1024", "--halo", "exchange")
     assert d["n_gpus"] == 1 and d["config"]["cells"] == 384 * 1024 and d["value"] > 0
     assert d["verified"] is True and d["grid_1024"]["verified"] is True
     c = d["comm"]
@@ -159,7 +174,7 @@ def test_bench_gpus_2_without_a_launcher():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two visible GPUs")
     # N = 2 exactly as the driver would type it: the 2048^2 grid split over two ranks, ghost rows exchanged over RCCL
-    d = _self_launched("--gpus", "2", "--steps", "4", "--warmup", "1", "--grid", "2048", "--cols", "2048")
+    d = _self_launched("--gpus", "2", "--full", "--steps", "4", "--warmup", "1", "--grid", "2048", "--cols", "2048")
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["cells"] == 2048 * 2048
     assert d["verified"] is True and d["grid_2048"]["verified"] is True
     assert sorted(r["device"] for r in d["comm"]["ranks"]) == [0, 1] and all(r["native_comm"]["world"] == 2 for r in d["comm"]["ranks"])
@@ -173,8 +188,7 @@ def test_dump_outputs_are_the_last_timed_plane(oracle, tmp_path):
     # --dump-outputs DIR: the plane the last timed step left, as a caller of the timed path receives it, against the oracle
     want = oracle.pipeline(512, 512, oracle.SIMPLEX, 0.4, 1.0, 2.0, 0.0, 13, 0, 0, 1700, oracle.GAUSS5_S1, 17, 5, 0.0, 0.005, 5)
     tile = tmp_path / "tile"
-    d = _run("--steps", "3", "--warmup", "1", "--res", "512", "--grid", "0", "--no-extras", "--no-cpu-baseline",
-             "--dump-outputs", str(tile))
+    d = _run("--steps", "3", "--warmup", "1", "--res", "512", "--grid", "0", "--dump-outputs", str(tile))
     assert d["steps"] == 3 and d["ms_per_step"] > 0
     h, rows = np.load(tile / "height.npy"), np.load(tile / "height_rows.npy")
     assert h.dtype == np.float32 and h.shape == (512, 512) and rows.dtype == np.float64
@@ -183,7 +197,7 @@ def test_dump_outputs_are_the_last_timed_plane(oracle, tmp_path):
     want = oracle.pipeline(1024, 1024, oracle.SIMPLEX, 0.4, 1.0, 2.0, 0.0, 13, 0, 0, 1700, oracle.GAUSS5_S1, 17, 5, 0.0, 0.005, 5)
     stripe = tmp_path / "stripe"
     d = _run("--steps", "2", "--warmup", "1", "--as-rank", "1", "4", "--stripe-rows", "256", "--cols", "1024", "--grid", "0",
-             "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(stripe))
+             "--dump-outputs", str(stripe))
     assert d["steps"] == 2
     h, rows = np.load(stripe / "height.npy"), np.load(stripe / "height_rows.npy")
     assert np.array_equal(rows, np.arange(256, 512)) and np.array_equal(h, want[256:512])

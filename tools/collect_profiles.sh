@@ -33,5 +33,5 @@ rm -rf "$P"
 # the bench line of these kernels, now that their counter summary exists (bench.py reads profiles/*_counters.json)
 cp "$OUT/${TAG}_counters.json" "$ROOT/profiles/${TAG}_counters.json"
 if [ -z "$NZ_SKIP_BENCH" ]; then
-  python3 bench.py --flush $FLUSH --float-mode $MODE > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
+  python3 bench.py --full --flush $FLUSH --float-mode $MODE > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.err"
 fi
