@@ -2,6 +2,7 @@
 // calls a static Burst-job delegate, these call the C ABI (one extern "C" entry per delegate, include/noize_hip.h).
 //   NoiseStage            Noise/NoiseStage.cs:13-61
 //   ShapedNoiseStage      new-framework: NoiseStage with an octave shape (billow, ridged multifractal)
+//   WarpedNoiseStage      new-framework: ShapedNoiseStage at domain-warped coordinates
 //   KernelFilterStage     Filter/KernelFilterStage.cs:13-51
 //   StageGaussianBlur     Filter/Kernel/Blur/StageGaussianBlur.cs:14-53
 //   StageSmoothBlur       Filter/Kernel/Blur/StageSmoothBlur.cs:14-52
@@ -82,6 +83,31 @@ namespace xshazwar.noize.hip {
             Native.Check(Native.nz_fractal_shaped(ctx.Handle, (int) noiseType, d.data.Ptr, d.resolution, hurst, startingAmplitude, stepdown,
                                                   detuneRate, octaves, d.xpos, d.zpos, noiseSize, (int) shape, ridgeOffset, ridgeGain,
                                                   dependency.id, out ulong h), "nz_fractal_shaped");
+            jobHandle = Done(h);
+        }
+    }
+
+    // ShapedNoiseStage read at domain-warped coordinates: each cell moves by (2q - 1) * warpStrength cells, q a plain fBm of the
+    // same basis over warpOctaves octaves at warpScale times the noise's frequency.  warpStrength 0 or warpOctaves 0 gives the
+    // bits of ShapedNoiseStage.
+    public class WarpedNoiseStage : ShapedNoiseStage {
+        public float warpStrength = 0f, warpScale = 1f;
+        public int warpOctaves = 4;
+        public WarpedNoiseStage(GpuContext ctx) : base(ctx) { shape = FractalShape.Fbm; }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_fractal_warped_batch(ctx.Handle, (int) noiseType, b.data.Ptr, b.resolution, b.count, b.positions.Ptr,
+                                                            hurst, startingAmplitude, stepdown, detuneRate, octaves, noiseSize, (int) shape,
+                                                            ridgeOffset, ridgeGain, warpStrength, warpScale, warpOctaves, dependency.id,
+                                                            out ulong hb), "nz_fractal_warped_batch");
+                jobHandle = Done(hb);
+                return;
+            }
+            Native.Check(Native.nz_fractal_warped(ctx.Handle, (int) noiseType, d.data.Ptr, d.resolution, hurst, startingAmplitude, stepdown,
+                                                  detuneRate, octaves, d.xpos, d.zpos, noiseSize, (int) shape, ridgeOffset, ridgeGain,
+                                                  warpStrength, warpScale, warpOctaves, dependency.id, out ulong h), "nz_fractal_warped");
             jobHandle = Done(h);
         }
     }

@@ -189,6 +189,26 @@ int32_t nz_fractal_shaped_stripe(nz_ctx *ctx, int32_t noiseType, float *buf, con
                                  int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
                                  float ridgeGain, nz_handle dep, nz_handle *out);
 
+/* nz_fractal_shaped / nz_fractal_shaped_stripe read at domain-warped coordinates (Quilez's f(p + s q(p))).  Cell (c, r)
+ * at X = c + xpos, Z = r + zpos (world cells, so adjacent tiles agree on shared cells), ns = noiseSize:
+ *   u = X / ns * warpScale, v = Z / ns * warpScale;  qx = D(u, v), qz = D(u + 5.2, v + 1.3)
+ *   the shaped octave loop at ((X + (2 qx - 1) warpStrength) / ns, (Z + (2 qz - 1) warpStrength) / ns)
+ * D is the plain fBm of the same basis, hurst, amplitude, stepdown and detune over warpOctaves octaves, divided by its
+ * norm, and is evaluated with the strict sequence in every float mode.  warpStrength is in cells (a cell moves by at most
+ * about |warpStrength|); warpScale is the displacement's frequency relative to the noise.  warpStrength == 0 or
+ * warpOctaves == 0 returns the bits of nz_fractal_shaped.  warpOctaves < 0, a non-finite warpStrength / warpScale or an
+ * unknown shape is NZ_ERR_INVALID and writes nothing. */
+int32_t nz_fractal_warped(nz_ctx *ctx, int32_t noiseType, float *src, int32_t resolution, float hurst,
+                          float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                          int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                          float ridgeGain, float warpStrength, float warpScale, int32_t warpOctaves, nz_handle dep,
+                          nz_handle *out);
+int32_t nz_fractal_warped_stripe(nz_ctx *ctx, int32_t noiseType, float *buf, const nz_stripe *st, float hurst,
+                                 float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                                 int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                                 float ridgeGain, float warpStrength, float warpScale, int32_t warpOctaves,
+                                 nz_handle dep, nz_handle *out);
+
 /* ---- separable kernel filters ------------------------------------------------------------- */
 /* SeperableKernelFilterDelegate, Filter/Kernel/KernelJob.cs:308-314 (one X+Z application) */
 int32_t nz_kernel_filter(nz_ctx *ctx, float *src, float *tmp, int32_t filter, int32_t resolution,
@@ -321,6 +341,11 @@ int32_t nz_fractal_shaped_batch(nz_ctx *ctx, int32_t noiseType, float *data, int
                                 const int32_t *positions, float hurst, float startingAmplitude, float stepdown,
                                 float detuneRate, int32_t octaves, int32_t noiseSize, int32_t shape, float ridgeOffset,
                                 float ridgeGain, nz_handle dep, nz_handle *out);
+int32_t nz_fractal_warped_batch(nz_ctx *ctx, int32_t noiseType, float *data, int32_t resolution, int32_t count,
+                                const int32_t *positions, float hurst, float startingAmplitude, float stepdown,
+                                float detuneRate, int32_t octaves, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                                float ridgeGain, float warpStrength, float warpScale, int32_t warpOctaves,
+                                nz_handle dep, nz_handle *out);
 int32_t nz_kernel_filter_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t filter, int32_t iterations,
                                      int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
 int32_t nz_gauss_blur_stage_batch(nz_ctx *ctx, float *src, float *tmp, int32_t width, int32_t sigma,

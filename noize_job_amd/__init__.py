@@ -10,7 +10,7 @@ from .runtime import Context, DeviceTile, JobHandle
 from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DownsampleData, ErosionStage, FlowMapStage, FractalNoise, FractalShape, GaussSigma,
                        GeneratorData, GeneratorDataBatch, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
-                       ReducePipeline, ReduceStage, ShapedNoiseStage, Upstream,
+                       ReducePipeline, ReduceStage, ShapedNoiseStage, Upstream, WarpedNoiseStage,
                        ReductionType, StageGaussianBlur, StageThermalErosion,
                        StageIO, StageSmoothBlur)
 

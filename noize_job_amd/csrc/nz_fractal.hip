@@ -1137,10 +1137,10 @@ int32_t nz_launch_fractal_shaped(hipStream_t s, int noiseType, float *dst, int r
     nz_set_error("unknown octave shape %d", p.shape);
     return NZ_ERR_INVALID;
 }
-#else
+#elif !defined(NZ_FRACTAL_WARPED_TU)
 int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
                           const nz_fractal_params &p_in, const float *d_rgrad, const void *d_simplex, int count,
-                          size_t bstride, const int32_t *positions) {
+                          size_t bstride, const int32_t *positions, const nz_warp_params *warp) {
     if (count < 1) return NZ_OK;
     nz_fractal_params p = p_in;
     p.positions = positions;
@@ -1153,6 +1153,7 @@ int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, in
         long long wg_per_row = (cols + 511) / 512;
         while (p.rows_per_wg > 1 && wg_per_row * ((rows + p.rows_per_wg - 1) / p.rows_per_wg) * count < 2048) p.rows_per_wg >>= 1;
     }
+    if (warp) return nz_launch_fractal_warped(s, noiseType, dst, rows, cols, pitch, p, *warp, d_rgrad, d_simplex, count);
     if (p.shape == NZ_SHAPE_FBM) return launch_shaped<NZ_SHAPE_FBM>(s, noiseType, dst, rows, cols, pitch, p, d_rgrad, d_simplex, count);
     return nz_launch_fractal_shaped(s, noiseType, dst, rows, cols, pitch, p, d_rgrad, d_simplex, count);
 }

@@ -139,6 +139,14 @@ struct nz_ridge_params {
 struct nz_fractal_params : nz_fractal_kparams {
     nz_ridge_params ridge;  // NZ_SHAPE_RIDGED only
 };
+// the domain warp's constants (nz_fractal_warped*): a trailing kernel argument of the warped kernels.  norm / fmax are the
+// displacement loop's CalcFractalNormValue and max |frequency| (as fractal_impl computes them for the main loop); the
+// kernels bound the displacement coordinates u = x * scale themselves, the 5.2 / 1.3 offsets of D's second evaluation included
+struct nz_warp_params {
+    float strength = 0.0f, scale = 1.0f;
+    int octaves = 0;
+    float norm = 0.0f, fmax = 0.0f;
+};
 
 // plane geometry handed to every stencil kernel: clamp rows are the global border seen from the
 // buffer, intersected with the buffer itself.
@@ -238,10 +246,14 @@ int32_t nz_fractal_rows(nz_ctx *ctx, hipStream_t stream, int noiseType, float *d
 // `positions` (nullable, device): {xpos, zpos} per grid of a batched launch of `count` grids `bstride` floats apart
 int32_t nz_launch_fractal(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
                           const nz_fractal_params &p, const float *d_rgrad, const void *d_simplex, int count = 1,
-                          size_t bstride = 0, const int32_t *positions = nullptr);
+                          size_t bstride = 0, const int32_t *positions = nullptr, const nz_warp_params *warp = nullptr);
 // the billow / ridged kernels (nz_fractal_shaped.hip); p complete, rows_per_wg / positions / bstride included
 int32_t nz_launch_fractal_shaped(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
                                  const nz_fractal_params &p, const float *d_rgrad, const void *d_simplex, int count);
+// the domain-warped kernels (nz_fractal_warped.hip); p complete as above, wp.octaves >= 1
+int32_t nz_launch_fractal_warped(hipStream_t s, int noiseType, float *dst, int rows, int cols, int pitch,
+                                 const nz_fractal_params &p, const nz_warp_params &wp, const float *d_rgrad,
+                                 const void *d_simplex, int count);
 
 int nz_conv_max_fused(int ksize);
 // T fused applications of (X pass, Z pass) src -> dst on rows [or0, or1)

@@ -45,11 +45,24 @@ static float calc_fractal_norm(float hurst, int octaves) {
     return t;
 }
 
+// largest |f| of FractalGenerator.NoiseValue's recurrence (Fractal.cs:121-127): lets a kernel decide once per row
+// whether every octave stays inside the range its lattice tables cover
+static float fractal_fmax(float stepdown, float detune, int octaves) {
+    float fmax = 0.0f, f = 1.0f, det = 0.0f;
+    for (int i = 0; i < octaves; i++) {
+        if (!(fabsf(f) <= fmax)) fmax = fabsf(f);
+        det += detune;
+        f *= (stepdown - det);
+    }
+    return fmax;
+}
+
 static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, float *dst, int rows, int cols, int pitch,
                             float hurst,
                             float amp, float stepdown, float detune, int octaves, int xpos, int zpos_first_row,
                             int noiseSize, int count = 1, size_t bstride = 0, const int32_t *positions = nullptr,
-                            int shape = NZ_SHAPE_FBM, float ridgeOffset = 1.0f, float ridgeGain = 2.0f) {
+                            int shape = NZ_SHAPE_FBM, float ridgeOffset = 1.0f, float ridgeGain = 2.0f,
+                            const nz_warp_params *warp = nullptr) {
     NZ_REQUIRE(dst, "src is NULL");
     NZ_REQUIRE(noiseType >= 0 && noiseType <= NZ_NOISE_DOMAIN_ROTATED_SIMPLEX, "unknown noise type %d", noiseType);
     NZ_REQUIRE(octaves >= 0, "octaves < 0");
@@ -67,17 +80,16 @@ static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, floa
     p.shape = shape;
     p.ridge.offset = ridgeOffset;
     p.ridge.gain = ridgeGain;
-    // largest |f| of FractalGenerator.NoiseValue's recurrence (Fractal.cs:121-127): lets a kernel decide once
-    // per row whether every octave stays inside the range its lattice tables cover
-    p.fmax = 0.0f;
-    float f = 1.0f, det = 0.0f;
-    for (int i = 0; i < octaves; i++) {
-        if (!(fabsf(f) <= p.fmax)) p.fmax = fabsf(f);
-        det += detune;
-        f *= (stepdown - det);
+    p.fmax = fractal_fmax(stepdown, detune, octaves);
+    // domain warp: the displacement loop's norm and frequency bound, the same two values for warp->octaves
+    nz_warp_params wp;
+    if (warp) {
+        wp = *warp;
+        wp.norm = calc_fractal_norm(hurst, wp.octaves);
+        wp.fmax = fractal_fmax(stepdown, detune, wp.octaves);
     }
     return nz_launch_fractal(stream, noiseType, dst, rows, cols, pitch, p, ctx->d_rgrad, ctx->d_simplex, count, bstride,
-                             positions);
+                             positions, warp ? &wp : nullptr);
 }
 
 // SeparableKernelFilter tables, Filter/Kernel/KernelJob.cs:97-136.  Gaussian bodies are
@@ -364,6 +376,58 @@ extern "C" int32_t nz_fractal_shaped_stripe(nz_ctx *ctx, int32_t noiseType, floa
         NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, buf + (size_t)st->own0 * pitch, rows, st->cols, pitch, hurst,
                             startingAmplitude, stepdown, detuneRate, octaves, xpos, zpos + st->grow0 + st->own0,
                             noiseSize, 1, 0, nullptr, shape, ridgeOffset, ridgeGain));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+// nz_fractal_shaped / _stripe read at domain-warped coordinates (new-framework feature, include/noize_hip.h).  The
+// warp's arguments are checked here; no warp (strength 0 or no octaves) is the shaped path itself
+static int32_t check_warp(float warpStrength, float warpScale, int32_t warpOctaves, nz_warp_params *wp) {
+    NZ_REQUIRE(warpOctaves >= 0, "warpOctaves %d < 0", warpOctaves);
+    NZ_REQUIRE(std::isfinite(warpStrength), "warpStrength is not finite");
+    NZ_REQUIRE(std::isfinite(warpScale), "warpScale is not finite");
+    wp->strength = warpStrength;
+    wp->scale = warpScale;
+    wp->octaves = warpOctaves;
+    return NZ_OK;
+}
+static bool warps(const nz_warp_params &wp) { return wp.strength != 0.0f && wp.octaves > 0; }
+
+extern "C" int32_t nz_fractal_warped(nz_ctx *ctx, int32_t noiseType, float *src, int32_t resolution, float hurst,
+                                     float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                                     int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape, float ridgeOffset,
+                                     float ridgeGain, float warpStrength, float warpScale, int32_t warpOctaves,
+                                     nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_res(resolution));
+    NZ_TRY(check_shape(shape));
+    nz_warp_params wp;
+    NZ_TRY(check_warp(warpStrength, warpScale, warpOctaves, &wp));
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, src, resolution, resolution, resolution, hurst, startingAmplitude,
+                        stepdown, detuneRate, octaves, xpos, zpos, noiseSize, 1, 0, nullptr, shape, ridgeOffset,
+                        ridgeGain, warps(wp) ? &wp : nullptr));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fractal_warped_stripe(nz_ctx *ctx, int32_t noiseType, float *buf, const nz_stripe *st, float hurst,
+                                            float startingAmplitude, float stepdown, float detuneRate, int32_t octaves,
+                                            int32_t xpos, int32_t zpos, int32_t noiseSize, int32_t shape,
+                                            float ridgeOffset, float ridgeGain, float warpStrength, float warpScale,
+                                            int32_t warpOctaves, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(buf, "buf is NULL");
+    NZ_TRY(check_shape(shape));
+    nz_warp_params wp;
+    NZ_TRY(check_warp(warpStrength, warpScale, warpOctaves, &wp));
+    int pitch = st->pitch > 0 ? st->pitch : st->cols;
+    int rows = st->own1 - st->own0;
+    if (rows > 0) {
+        NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, buf + (size_t)st->own0 * pitch, rows, st->cols, pitch, hurst,
+                            startingAmplitude, stepdown, detuneRate, octaves, xpos, zpos + st->grow0 + st->own0,
+                            noiseSize, 1, 0, nullptr, shape, ridgeOffset, ridgeGain, warps(wp) ? &wp : nullptr));
     }
     return nz_ctx_finish(ctx, out);
 }
@@ -754,6 +818,25 @@ extern "C" int32_t nz_fractal_shaped_batch(nz_ctx *ctx, int32_t noiseType, float
     NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, data, resolution, resolution, resolution, hurst, startingAmplitude,
                         stepdown, detuneRate, octaves, 0, 0, noiseSize, count, (size_t)resolution * resolution, positions,
                         shape, ridgeOffset, ridgeGain));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fractal_warped_batch(nz_ctx *ctx, int32_t noiseType, float *data, int32_t resolution,
+                                           int32_t count, const int32_t *positions, float hurst, float startingAmplitude,
+                                           float stepdown, float detuneRate, int32_t octaves, int32_t noiseSize,
+                                           int32_t shape, float ridgeOffset, float ridgeGain, float warpStrength,
+                                           float warpScale, int32_t warpOctaves, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    NZ_REQUIRE(positions, "positions is NULL");
+    NZ_TRY(check_shape(shape));
+    nz_warp_params wp;
+    NZ_TRY(check_warp(warpStrength, warpScale, warpOctaves, &wp));
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(fractal_impl(ctx, ctx->stream, noiseType, data, resolution, resolution, resolution, hurst, startingAmplitude,
+                        stepdown, detuneRate, octaves, 0, 0, noiseSize, count, (size_t)resolution * resolution, positions,
+                        shape, ridgeOffset, ridgeGain, warps(wp) ? &wp : nullptr));
     return nz_ctx_finish(ctx, out);
 }
 

@@ -266,6 +266,33 @@ class ShapedNoiseStage : public NoiseStage {
     }
 };
 
+// new-framework: ShapedNoiseStage read at domain-warped coordinates (nz_fractal_warped): each cell moves by
+// (2q - 1) * warpStrength cells, q a plain fBm of the same basis over warpOctaves octaves at warpScale times the noise's
+// frequency.  warpStrength 0 or warpOctaves 0 gives the bits of ShapedNoiseStage.
+class WarpedNoiseStage : public ShapedNoiseStage {
+  public:
+    explicit WarpedNoiseStage(nz_ctx *c) : ShapedNoiseStage(c) { shape = FractalShape::Fbm; }
+    float warpStrength = 0.f, warpScale = 1.f;
+    int warpOctaves = 4;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        nz_handle h = 0;
+        if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_fractal_warped_batch(ctx, (int)noiseType, b->data->ptr, b->resolution, b->count, b->positions, hurst,
+                                          startingAmplitude, stepdown, detuneRate, octaves, noiseSize, (int)shape,
+                                          ridgeOffset, ridgeGain, warpStrength, warpScale, warpOctaves, dependency.id, &h),
+                  "nz_fractal_warped_batch");
+            jobHandle = done(h);
+            return;
+        }
+        check(nz_fractal_warped(ctx, (int)noiseType, d->data->ptr, d->resolution, hurst, startingAmplitude, stepdown,
+                                detuneRate, octaves, d->xpos, d->zpos, noiseSize, (int)shape, ridgeOffset, ridgeGain,
+                                warpStrength, warpScale, warpOctaves, dependency.id, &h),
+              "nz_fractal_warped");
+        jobHandle = done(h);
+    }
+};
+
 class TmpStage : public PipelineStage {  // stages that own one scratch plane
   public:
     using PipelineStage::PipelineStage;

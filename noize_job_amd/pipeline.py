@@ -333,6 +333,37 @@ class ShapedNoiseStage(NoiseStage):
                                        dep=dependency)
 
 
+class WarpedNoiseStage(ShapedNoiseStage):
+    """New-framework: a ShapedNoiseStage read at domain-warped coordinates (Quilez's f(p + s q(p))): each cell moves by
+    (2q - 1) warpStrength cells, q a plain fBm of the same basis over warpOctaves octaves at warpScale times the noise's
+    frequency.  warpStrength 0 or warpOctaves 0 gives the bits of ShapedNoiseStage.  A subclass of NoiseStage, so the
+    stock-list fast paths (exact type) never take it for plain fBm."""
+
+    def __init__(self, ctx, noiseType=FractalNoise.Sin, hurst=0.0, startingAmplitude=1.0, octaves=1, stepdown=2.0,
+                 detuneRate=0.0, noiseSize=1000, shape=FractalShape.Fbm, ridgeOffset=1.0, ridgeGain=2.0,
+                 warpStrength=0.0, warpScale=1.0, warpOctaves=4):
+        super().__init__(ctx, noiseType, hurst, startingAmplitude, octaves, stepdown, detuneRate, noiseSize, shape,
+                         ridgeOffset, ridgeGain)
+        self.warpStrength = warpStrength
+        self.warpScale = warpScale
+        self.warpOctaves = warpOctaves
+
+    def Schedule(self, requirements, dependency):
+        self.CheckRequirements(GeneratorData, requirements)
+        d = requirements.data
+        warp = (self.warpStrength, self.warpScale, self.warpOctaves)
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_fractal_warped_batch", int(self.noiseType), d.data.ptr, d.resolution,
+                                           d.count, d.positions.ptr, self.hurst, self.startingAmplitude, self.stepdown,
+                                           self.detuneRate, self.octaves, self.noiseSize, int(self.shape),
+                                           self.ridgeOffset, self.ridgeGain, *warp, dep=dependency)
+            return
+        self.jobHandle = self.ctx.call("nz_fractal_warped", int(self.noiseType), d.data.ptr, d.resolution, self.hurst,
+                                       self.startingAmplitude, self.stepdown, self.detuneRate, self.octaves, d.xpos,
+                                       d.zpos, self.noiseSize, int(self.shape), self.ridgeOffset, self.ridgeGain, *warp,
+                                       dep=dependency)
+
+
 class KernelFilterStage(PipelineStage):  # Filter/KernelFilterStage.cs:13-51
     def __init__(self, ctx, filter=KernelFilterType.Gauss9_S1, iterations=1):
         super().__init__(ctx)
