@@ -246,6 +246,42 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; }                          // :216-219
     }
 
+    // Grid hydraulic erosion with sediment transport (new-framework feature; the model: nz_hydraulic_erosion_stage in
+    // include/noize_hip.h).  Owns its work planes like FlowMapStage; once the handle completes, Water holds the final water
+    // depth of the last payload (count * resolution^2 floats), a river and lake mask.
+    public class HydraulicErosionStage : PipelineStage {
+        public int iterations = 200;
+        public float initialWater = 1e-4f, rain = 1e-4f, evaporation = 0.01f, capacity = 1f, dissolve = 0.3f, deposit = 0.3f, minTilt = 0.01f;
+        DeviceTile work;                         // nz_hydraulic_erosion_work_floats planes; the first count * resolution^2 floats: the water
+        int resolution, count = 1;
+        public HydraulicErosionStage(GpuContext ctx) : base(ctx) {}
+        public DeviceTile Water => work?.Offset(0, count * resolution * resolution);
+        public override void ResizeNativeContainers(int size) {
+            work?.Dispose();
+            work = ctx.Alloc((int) (ulong) Native.nz_hydraulic_erosion_work_floats(resolution, count));
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
+            GeneratorData d = (GeneratorData) requirements.data;
+            ulong h;
+            if (d.write != null) {
+                NzRwTile t = new NzRwTile { read = d.data.Ptr, write = d.write.Ptr, resolution = d.resolution, count = count };
+                Native.Check(Native.nz_hydraulic_erosion_stage_rw(ctx.Handle, ref t, work.Ptr, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, dependency.id, out h), "nz_hydraulic_erosion_stage_rw");
+                Adopt(d, t);
+            } else if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_hydraulic_erosion_stage_batch(ctx.Handle, b.data.Ptr, work.Ptr, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, b.resolution, b.count, dependency.id, out h), "nz_hydraulic_erosion_stage_batch");
+            } else {
+                Native.Check(Native.nz_hydraulic_erosion_stage(ctx.Handle, d.data.Ptr, work.Ptr, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, d.resolution, dependency.id, out h), "nz_hydraulic_erosion_stage");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() { work?.Dispose(); work = null; }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

@@ -327,6 +327,52 @@ int32_t nz_flow_fused_stripe(nz_ctx *ctx, const float *height, const float *cons
                              float *dst, const nz_stripe *st, int32_t iterations, int32_t first, int32_t last,
                              float normMin, float normMax, nz_handle dep, nz_handle *out);
 
+/* ---- grid hydraulic erosion with sediment transport (new-framework feature) ---------------------------
+ * Takes material from where water runs fast and steep and lays it down where the water slows (the subtractive flow
+ * stage Geologic/Stage/ErosionStageSubtractiveFlow.cs leaves commented out).  Cell state: height b, water d, suspended
+ * sediment s and the four outflows fN fS fE fW of the flow map (N is +z, E is +x).  Start: d = initialWater, s = 0, flux 0.
+ * DT = 0.2, the flow map's TIMESTEP.  "Clamped": a clamp-to-edge read, as in the flow map.  Every iteration, in float32 in
+ * this order, no contraction:
+ *   1. d1 = d + rain
+ *   2. new flux: ComputeFlowStep with totalHt = b + d1 and water_0 = d1 over the clamped neighbours' b + d1 and the old
+ *      flux (nz_flowmap_compute_flow's arithmetic)
+ *   3. d2 = UpdateWaterStep(d1, new flux), its in-terms clamped at the border (nz_flowmap_update_water's arithmetic)
+ *   4. discharge q = CreateVelocityField's magnitude of the new flux, not normalised
+ *   5. gx = (b[x+1] - b[x-1]) * 0.5, gz = (b[z+1] - b[z-1]) * 0.5 (clamped, b before this iteration's erosion),
+ *      g2 = gx*gx + gz*gz, S = max(minTilt, sqrt(g2 / (1 + g2))) (the sine of the tilt)
+ *   6. C = (capacity * q) * S
+ *   7. C > s:     e = min(dissolve * (C - s), max(0, b - bmin4)), b -= e, s += e  (bmin4: the lowest of the four clamped
+ *                 neighbours -- erosion never digs a pit);
+ *      otherwise: e = deposit * (s - C), b += e, s -= e
+ *   8. r = d1 >= 2^-126 ? DT / d1 : 0 (water shallower than the smallest normal float carries nothing: DT / d1 would
+ *      overflow and 0 * inf lose the sediment); a_X = s * (fX * r) for X in W E S N; out = ((a_W + a_E) + a_S) + a_N;
+ *      in = ((a_E[x-1] + a_W[x+1]) + a_N[z-1]) + a_S[z+1], a neighbour outside the tile contributing 0 (no flux leaves
+ *      through the border, so the sediment is conserved); s = max(0, (s - out) + in)
+ *   9. d = d2 * (1 - evaporation)
+ * min(a, c) = c < a ? c : a and max(lo, v) = v > lo ? v : lo (a tie keeps the first operand).  After the last iteration
+ * the sediment settles: the result is b + s, so the sum of the heights is conserved up to rounding.  iterations == 0
+ * leaves the heights unchanged.  Strict arithmetic in every float mode (nz_ctx_set_float_mode does not apply), equal
+ * bit for bit across the in-place, _rw and _batch forms and across batch positions; each tile is clamped at its own border.
+ * Ranges: every argument finite; initialWater, rain, capacity, minTilt >= 0; evaporation, dissolve, deposit in [0, 1];
+ * iterations >= 0 -- otherwise NZ_ERR_INVALID, the message names the argument, and nothing is written.
+ * Stable range: the defaults of the hosts' HydraulicErosionStage (initialWater 1e-4, rain 1e-4, evaporation 0.01,
+ * capacity 1, dissolve 0.3, deposit 0.3, minTilt 0.01) stay finite over thousands of iterations on a smoothed fBm
+ * tile; capacity 0 leaves the heights unchanged, and capacities up to ~4 stay finite over 1000 iterations.
+ * `work` = nz_hydraulic_erosion_work_floats(resolution, count) floats, stage-owned.  After the call completes, its first
+ * count * resolution^2 floats hold the final water depth d (initialWater with no iteration) -- a river and lake mask.
+ * The result lands in `src`; the _rw form reads tile->read, ping-pongs between the pair and returns with tile->read holding
+ * the result; the _batch form runs `count` tiles stored back to back. */
+size_t nz_hydraulic_erosion_work_floats(int32_t resolution, int32_t count);
+int32_t nz_hydraulic_erosion_stage(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater, float rain,
+                                   float evaporation, float capacity, float dissolve, float deposit, float minTilt,
+                                   int32_t resolution, nz_handle dep, nz_handle *out);
+int32_t nz_hydraulic_erosion_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, int32_t iterations, float initialWater,
+                                      float rain, float evaporation, float capacity, float dissolve, float deposit,
+                                      float minTilt, nz_handle dep, nz_handle *out);
+int32_t nz_hydraulic_erosion_stage_batch(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater,
+                                         float rain, float evaporation, float capacity, float dissolve, float deposit,
+                                         float minTilt, int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
+
 /* ---- batched stage bodies (new-framework feature) ------------------------------------------------
  * `count` independent tiles of resolution^2 cells stored back to back (tile k at data + k * resolution^2) go
  * through one launch sequence: the reference runs one BasePipeline per tile request

@@ -148,6 +148,10 @@ SIGNATURES = {
     "nz_flow_fused_max_iterations": (_i, []),
     "nz_flow_fused_stripe": (_i, [ctx_p, dev_ptr, C.POINTER(dev_ptr), C.POINTER(dev_ptr), dev_ptr, stripe_p, _i, _i, _i,
                                   _f, _f] + _tail),
+    "nz_hydraulic_erosion_work_floats": (_sz, [_i, _i]),
+    "nz_hydraulic_erosion_stage": (_i, [ctx_p, dev_ptr, dev_ptr, _i] + [_f] * 7 + [_i] + _tail),
+    "nz_hydraulic_erosion_stage_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, _i] + [_f] * 7 + _tail),
+    "nz_hydraulic_erosion_stage_batch": (_i, [ctx_p, dev_ptr, dev_ptr, _i] + [_f] * 7 + [_i, _i] + _tail),
     "nz_constant_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, _f, _i] + _tail),
     "nz_reduction_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, dev_ptr, _i] + _tail),
     "nz_update_flow_from_track": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, _f, _f, _f, _i] + _tail),

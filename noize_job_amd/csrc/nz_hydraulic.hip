@@ -1,0 +1,173 @@
+// nz_hydraulic.hip -- grid hydraulic erosion with sediment transport (gfx950; new-framework feature, the stage
+// Geologic/Stage/ErosionStageSubtractiveFlow.cs leaves commented out).  The model is stated in include/noize_hip.h and
+// restated step by step in tests/hydraulic_ref.py; the pipe-model flux, the water update and the discharge are the flow
+// map's own arithmetic (nz_flow_common.hpp), so with capacity 0 the water and flux are the flow map's state bit for bit.
+//
+// One launch per iteration.  A workgroup produces an HX x HZ tile of one plane and stages its halo through LDS:
+//   fill     heights b and water d1 = d + rain on the tile at radius 3
+//   phase A  the new flux (compute_flow) at radius 2
+//   phase B  discharge, slope, erosion / deposition and the sediment's outflows a_X at radius 1
+//   phase C  the water update and the sediment's in-flow on the tile itself
+// Every LDS cell holds the value of the clamped plane cell it stands for: a cell beyond the border is a copy of the border
+// cell, and a clamped neighbour read is a read at the clamped plane coordinate -- which always lies inside the next larger
+// radius -- so the clamp-to-edge reads are the flow map's.  The sediment's in-flow alone reads unclamped neighbours (0
+// beyond the border).  Strict IEEE binary32 in every float mode, no contraction (-ffp-contract=off, Makefile); every step
+// is a radius-1 stencil with no atomics, so the result is independent of the launch shape.
+#include "nz_internal.hpp"
+#include "nz_flow_common.hpp"
+
+namespace {
+
+constexpr int HX = 64, HZ = 16;  // tile produced by one workgroup
+constexpr int HT = 512;          // threads: 8 waves
+constexpr int HR = 3;           // halo radius of the staged state
+constexpr int LW = HX + 2 * HR, LH = HZ + 2 * HR, LN = LW * LH;
+
+// tie-keeping selects (tests/hydraulic_ref.py): max(lo, v) keeps lo unless v is larger, min(a, c) keeps a unless c is smaller
+__device__ __forceinline__ float smax(float lo, float v) { return v > lo ? v : lo; }
+__device__ __forceinline__ float smin(float a, float c) { return c < a ? c : a; }
+
+// FIRST: the state is the start state (water initialWater, no sediment, no flux) and `in` is not read.
+// LAST: the launch writes b + s to h_out and the water to out[0] only.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__ h_in, float *__restrict__ h_out,
+                                                       nz_hydraulic_planes p, nz_hydraulic_params k, int res) {
+    __shared__ float B[LN], D1[LN];           // radius 3
+    __shared__ float FN[LN], FS[LN], FE[LN], FW[LN];  // radius 2 (same layout)
+    __shared__ float AN[LN], AS[LN], AE[LN], AW[LN];  // radius 1 (same layout)
+    __shared__ float BN[HX * HZ], PS[HX * HZ];        // the tile: eroded height, s - out
+
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * HX, z0 = blockIdx.y * HZ;
+    const size_t base = (size_t)blockIdx.z * res * res;
+    const int hi = res - 1;
+    // LDS column / row of plane column / row v (v within the staged radius)
+    auto lx_of = [&](int v) { return v - x0 + HR; };
+    auto lz_of = [&](int v) { return v - z0 + HR; };
+
+    // ---- fill: radius 3 ----
+    for (int i = tid; i < LN; i += HT) {
+        const int lz = i / LW, lx = i - lz * LW;
+        const int px = clampi(x0 - HR + lx, 0, hi), pz = clampi(z0 - HR + lz, 0, hi);
+        const size_t c = base + (size_t)pz * res + px;
+        B[i] = h_in[c];
+        D1[i] = (FIRST ? k.initial_water : p.in[0][c]) + k.rain;
+    }
+    __syncthreads();
+
+    // ---- phase A: new flux at radius 2 (ComputeFlowStep with water_0 = d1) ----
+    for (int i = tid; i < (LW - 2) * (LH - 2); i += HT) {
+        const int lz = 1 + i / (LW - 2), lx = 1 + i % (LW - 2);
+        const int px = clampi(x0 - HR + lx, 0, hi), pz = clampi(z0 - HR + lz, 0, hi);
+        const int l = lz * LW + lx;
+        const int lW = lz * LW + lx_of(clampi(px - 1, 0, hi)), lE = lz * LW + lx_of(clampi(px + 1, 0, hi));
+        const int lS = lz_of(clampi(pz - 1, 0, hi)) * LW + lx, lN = lz_of(clampi(pz + 1, 0, hi)) * LW + lx;
+        flux4 old{0.0f, 0.0f, 0.0f, 0.0f};
+        if (!FIRST) {
+            const size_t c = base + (size_t)pz * res + px;
+            old.w = p.in[5][c];
+            old.e = p.in[4][c];
+            old.s = p.in[3][c];
+            old.n = p.in[2][c];
+        }
+        // totalHt = water + height, as nzo_flow_step / flow_step_kernel add them
+        const flux4 f = compute_flow(D1[l] + B[l], D1[l], D1[lW] + B[lW], D1[lE] + B[lE], D1[lS] + B[lS],
+                                     D1[lN] + B[lN], old);
+        FW[l] = f.w;
+        FE[l] = f.e;
+        FS[l] = f.s;
+        FN[l] = f.n;
+    }
+    __syncthreads();
+
+    // ---- phase B: discharge, slope, erosion / deposition, sediment outflows at radius 1 ----
+    for (int i = tid; i < (LW - 4) * (LH - 4); i += HT) {
+        const int lz = 2 + i / (LW - 4), lx = 2 + i % (LW - 4);
+        const int px = clampi(x0 - HR + lx, 0, hi), pz = clampi(z0 - HR + lz, 0, hi);
+        const int l = lz * LW + lx;
+        const int lW = lz * LW + lx_of(clampi(px - 1, 0, hi)), lE = lz * LW + lx_of(clampi(px + 1, 0, hi));
+        const int lS = lz_of(clampi(pz - 1, 0, hi)) * LW + lx, lN = lz_of(clampi(pz + 1, 0, hi)) * LW + lx;
+        // CreateVelocityField's magnitude (normalised by min 0, range 1: the identity)
+        const float q = velocity_norm_m<false>(FE[lW] - FW[l], FE[l] - FW[lE], FS[lN] - FN[l], FS[l] - FN[lS], 0.0f, 1.0f,
+                                               1.0f);
+        const float b = B[l];
+        const float bW = B[lW], bE = B[lE], bS = B[lS], bN = B[lN];
+        const float gx = (bE - bW) * 0.5f;
+        const float gz = (bN - bS) * 0.5f;
+        const float g2 = gx * gx + gz * gz;
+        const float S = smax(k.min_tilt, sqrtf(g2 / (1.0f + g2)));
+        const float C = (k.capacity * q) * S;
+        float s = FIRST ? 0.0f : p.in[1][base + (size_t)pz * res + px];
+        float bb;
+        if (C > s) {
+            const float bmin4 = smin(smin(smin(bW, bE), bS), bN);
+            const float e = smin(k.dissolve * (C - s), smax(0.0f, b - bmin4));
+            bb = b - e;
+            s = s + e;
+        } else {
+            const float e = k.deposit * (s - C);
+            bb = b + e;
+            s = s - e;
+        }
+        const float d1 = D1[l];
+        const float r = d1 >= 0x1p-126f ? TIMESTEP / d1 : 0.0f;  // the smallest normal: DT / d1 stays finite
+        const float aW = s * (FW[l] * r), aE = s * (FE[l] * r), aS = s * (FS[l] * r), aN = s * (FN[l] * r);
+        AW[l] = aW;
+        AE[l] = aE;
+        AS[l] = aS;
+        AN[l] = aN;
+        const int tx = lx - HR, tz = lz - HR;
+        if (tx >= 0 && tx < HX && tz >= 0 && tz < HZ) {
+            BN[tz * HX + tx] = bb;
+            PS[tz * HX + tx] = s - (((aW + aE) + aS) + aN);
+        }
+    }
+    __syncthreads();
+
+    // ---- phase C: water update and sediment in-flow on the tile ----
+    for (int i = tid; i < HX * HZ; i += HT) {
+        const int tz = i / HX, tx = i % HX;
+        const int px = x0 + tx, pz = z0 + tz;
+        if (px > hi || pz > hi) continue;
+        const int lx = tx + HR, lz = tz + HR;
+        const int l = lz * LW + lx;
+        const int lW = lz * LW + lx_of(clampi(px - 1, 0, hi)), lE = lz * LW + lx_of(clampi(px + 1, 0, hi));
+        const int lS = lz_of(clampi(pz - 1, 0, hi)) * LW + lx, lN = lz_of(clampi(pz + 1, 0, hi)) * LW + lx;
+        const flux4 own{FW[l], FE[l], FS[l], FN[l]};
+        const float d2 = update_water(D1[l], own, FE[lW], FW[lE], FN[lS], FS[lN]);
+        // in-flow: 0 from beyond the border (no flux leaves the tile, so the sediment is conserved)
+        const float inW = px > 0 ? AE[l - 1] : 0.0f;
+        const float inE = px < hi ? AW[l + 1] : 0.0f;
+        const float inS = pz > 0 ? AN[l - LW] : 0.0f;
+        const float inN = pz < hi ? AS[l + LW] : 0.0f;
+        const float s = smax(0.0f, PS[i] + (((inW + inE) + inS) + inN));
+        const float d = d2 * k.keep;
+        const size_t c = base + (size_t)pz * res + px;
+        if (LAST) {
+            h_out[c] = BN[i] + s;
+            p.out[0][c] = d;
+        } else {
+            h_out[c] = BN[i];
+            p.out[0][c] = d;
+            p.out[1][c] = s;
+            p.out[2][c] = own.n;
+            p.out[3][c] = own.s;
+            p.out[4][c] = own.e;
+            p.out[5][c] = own.w;
+        }
+    }
+}
+
+}  // namespace
+
+int32_t nz_launch_hydraulic(hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
+                            const nz_hydraulic_params &k, int res, int count, int first, int last) {
+    if (res <= 0 || count <= 0) return NZ_OK;
+    const dim3 grid((res + HX - 1) / HX, (res + HZ - 1) / HZ, count);
+    if (first && last) NZ_LAUNCH((hydraulic_kernel<true, true>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
+    else if (first) NZ_LAUNCH((hydraulic_kernel<true, false>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
+    else if (last) NZ_LAUNCH((hydraulic_kernel<false, true>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
+    else NZ_LAUNCH((hydraulic_kernel<false, false>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}

@@ -307,6 +307,20 @@ int32_t nz_launch_flow_fused(hipStream_t s, const float *h, const float *const i
 bool nz_flow_stream_wanted(const nz_geom &g, int n);
 int32_t nz_launch_flow_stream(hipStream_t s, const float *h, float *dst, const nz_geom &g, int n, float nmin, float nrange);
 
+// grid hydraulic erosion (nz_hydraulic.hip): one iteration per launch on `count` tiles of res^2 cells stored back to back.
+// State planes {d, s, fN, fS, fE, fW}; `in` is not read by the first launch (the start state is implied), the last launch
+// writes b + s to h_out and the water to out[0] only
+struct nz_hydraulic_planes {
+    const float *in[6];
+    float *out[6];
+};
+struct nz_hydraulic_params {
+    float initial_water, rain, keep;  // keep = 1 - evaporation
+    float capacity, dissolve, deposit, min_tilt;
+};
+int32_t nz_launch_hydraulic(hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
+                            const nz_hydraulic_params &k, int res, int count, int first, int last);
+
 int32_t nz_launch_mesh_planar(hipStream_t s, void *vertices, uint32_t *indices, int res);
 int32_t nz_launch_mesh(hipStream_t s, int meshType, void *vertices, uint32_t *indices, int res, int in_res,
                        float tile_height, float tile_size, const float *heights, int count = 1, int index16 = 0);

@@ -989,6 +989,115 @@ extern "C" int32_t nz_flow_fused_stripe(nz_ctx *ctx, const float *height, const 
 }
 
 // ---------------------------------------------------------------------------------------------
+// grid hydraulic erosion with sediment transport (new-framework feature, include/noize_hip.h, nz_hydraulic.hip)
+// ---------------------------------------------------------------------------------------------
+// work planes of count * res^2 floats each: 0 the final water, 1-6 and 7-12 the state sets {d, s, fN, fS, fE, fW} the
+// launches ping-pong between, 13 the in-place forms' second height plane
+constexpr int HYD_PLANES = 14;
+
+extern "C" size_t nz_hydraulic_erosion_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? (size_t)HYD_PLANES * resolution * resolution * count : 0;
+}
+
+static int32_t check_hydraulic(int32_t iterations, float initialWater, float rain, float evaporation, float capacity,
+                               float dissolve, float deposit, float minTilt, nz_hydraulic_params *k) {
+    NZ_REQUIRE(iterations >= 0, "iterations %d < 0", iterations);
+    const struct { const char *name; float v; float lo, hi; } args[] = {
+        {"initialWater", initialWater, 0.0f, INFINITY}, {"rain", rain, 0.0f, INFINITY},
+        {"evaporation", evaporation, 0.0f, 1.0f},       {"capacity", capacity, 0.0f, INFINITY},
+        {"dissolve", dissolve, 0.0f, 1.0f},             {"deposit", deposit, 0.0f, 1.0f},
+        {"minTilt", minTilt, 0.0f, INFINITY}};
+    for (const auto &a : args) {
+        NZ_REQUIRE(std::isfinite(a.v), "%s is not finite", a.name);
+        if (a.hi == INFINITY) NZ_REQUIRE(a.v >= a.lo, "%s %g < 0", a.name, (double)a.v);
+        else NZ_REQUIRE(a.v >= a.lo && a.v <= a.hi, "%s %g outside [0, 1]", a.name, (double)a.v);
+    }
+    *k = nz_hydraulic_params{initialWater, rain, 1.0f - evaporation, capacity, dissolve, deposit, minTilt};
+    return NZ_OK;
+}
+
+// `iterations` launches on `count` tiles; the height ping-pongs between h0 (which holds the input) and h1, the state
+// between the two sets of `work`.  The result lands in h0 when `iterations` is even and in h1 when it is odd (*in_h1);
+// keep_h0: the caller wants it in h0 whatever the count, and an odd count copies h0 to h1 first.  Ends with the final
+// water in work plane 0 (initialWater itself when there is no iteration).
+static int32_t hydraulic_series(nz_ctx *ctx, float *h0, float *h1, float *work, int res, int count, int32_t iterations,
+                                const nz_hydraulic_params &k, bool keep_h0, bool *in_h1) {
+    const size_t n = (size_t)res * res * count;
+    *in_h1 = false;
+    if (iterations == 0) {
+        nz_ctx_arm_last_launch(ctx);
+        return nz_launch_fill(ctx->stream, work, n, k.initial_water);
+    }
+    float *cur = h0, *nxt = h1;
+    if (keep_h0 && (iterations & 1)) {
+        NZ_TRY(nz_launch_copy(ctx->stream, h1, h0, n));
+        std::swap(cur, nxt);
+    }
+    nz_hydraulic_planes sets[2];
+    for (int j = 0; j < 2; j++)
+        for (int i = 0; i < 6; i++) sets[j].in[i] = sets[j].out[i] = work + (size_t)(1 + 6 * j + i) * n;
+    for (int it = 0; it < iterations; it++) {
+        const int first = it == 0, last = it == iterations - 1;
+        nz_hydraulic_planes p;
+        for (int i = 0; i < 6; i++) {
+            p.in[i] = sets[it & 1].in[i];
+            p.out[i] = last ? (i == 0 ? work : nullptr) : sets[(it + 1) & 1].out[i];
+        }
+        if (last) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_hydraulic(ctx->stream, cur, nxt, p, k, res, count, first, last));
+        std::swap(cur, nxt);
+    }
+    *in_h1 = cur == h1;
+    return NZ_OK;
+}
+
+static int32_t hydraulic_stage_impl(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater,
+                                    float rain, float evaporation, float capacity, float dissolve, float deposit,
+                                    float minTilt, int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    NZ_REQUIRE(src && work, "src/work is NULL");
+    nz_hydraulic_params k;
+    NZ_TRY(check_hydraulic(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, &k));
+    float *h1 = work + (size_t)(HYD_PLANES - 1) * resolution * resolution * count;
+    bool in_h1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (hydraulic_series arms its last launch)
+    NZ_TRY(hydraulic_series(ctx, src, h1, work, resolution, count, iterations, k, true, &in_h1));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_stage(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater,
+                                              float rain, float evaporation, float capacity, float dissolve, float deposit,
+                                              float minTilt, int32_t resolution, nz_handle dep, nz_handle *out) {
+    return hydraulic_stage_impl(ctx, src, work, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit,
+                                minTilt, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_stage_batch(nz_ctx *ctx, float *src, float *work, int32_t iterations,
+                                                    float initialWater, float rain, float evaporation, float capacity,
+                                                    float dissolve, float deposit, float minTilt, int32_t resolution,
+                                                    int32_t count, nz_handle dep, nz_handle *out) {
+    return hydraulic_stage_impl(ctx, src, work, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit,
+                                minTilt, resolution, count, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, int32_t iterations,
+                                                 float initialWater, float rain, float evaporation, float capacity,
+                                                 float dissolve, float deposit, float minTilt, nz_handle dep,
+                                                 nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    NZ_REQUIRE(work, "work is NULL");
+    nz_hydraulic_params k;
+    NZ_TRY(check_hydraulic(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, &k));
+    bool in_h1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (hydraulic_series arms its last launch)
+    NZ_TRY(hydraulic_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, iterations, k, false, &in_h1));
+    rw_swap(tile, in_h1);
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
 // mesh
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t nz_mesh_vertex_count(int32_t resolution) {  // VertexCount, Overshoot :26

@@ -537,6 +537,56 @@ class FlowMapStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work;
 };
 
+// Grid hydraulic erosion with sediment transport (new-framework feature; the model: nz_hydraulic_erosion_stage in
+// include/noize_hip.h).  Owns its work planes like FlowMapStage; once the handle completes, water() holds the final water
+// depth of the last payload (waterLength() floats: count * resolution^2), a river and lake mask.
+class HydraulicErosionStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    int iterations = 200;
+    float initialWater = 1e-4f, rain = 1e-4f, evaporation = .01f, capacity = 1.f, dissolve = .3f, deposit = .3f,
+          minTilt = .01f;
+    void ResizeNativeContainers(size_t) override {
+        work.reset(new DeviceTile(ctx, nz_hydraulic_erosion_work_floats(resolution, count)));
+    }
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
+        nz_handle h = 0;
+        if (d->write) {
+            nz_rw_tile t = rw_pair(d, count);
+            check(nz_hydraulic_erosion_stage_rw(ctx, &t, work->ptr, iterations, initialWater, rain, evaporation, capacity,
+                                                dissolve, deposit, minTilt, dependency.id, &h),
+                  "nz_hydraulic_erosion_stage_rw");
+            rw_adopt(d, t);
+            jobHandle = done(h);
+            return;
+        }
+        if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_hydraulic_erosion_stage_batch(ctx, b->data->ptr, work->ptr, iterations, initialWater, rain,
+                                                   evaporation, capacity, dissolve, deposit, minTilt, b->resolution,
+                                                   b->count, dependency.id, &h),
+                  "nz_hydraulic_erosion_stage_batch");
+            jobHandle = done(h);
+            return;
+        }
+        check(nz_hydraulic_erosion_stage(ctx, d->data->ptr, work->ptr, iterations, initialWater, rain, evaporation,
+                                         capacity, dissolve, deposit, minTilt, d->resolution, dependency.id, &h),
+              "nz_hydraulic_erosion_stage");
+        jobHandle = done(h);
+    }
+    const float *water() const { return work ? work->ptr : nullptr; }
+    size_t waterLength() const { return (size_t)count * resolution * resolution; }
+    void OnDestroy() override { work.reset(); }
+
+  private:
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

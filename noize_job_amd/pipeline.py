@@ -640,6 +640,67 @@ class FlowMapStage(PipelineStage):  # Geologic/Stage/FlowMapStage.cs:16-220
         self.DisposeArrays()
 
 
+class HydraulicErosionStage(PipelineStage):
+    """Grid hydraulic erosion with sediment transport (new-framework feature; the model is the comment block of
+    nz_hydraulic_erosion_stage in include/noize_hip.h): carves channels where water runs fast and steep and fills hollows
+    where it slows.  Like FlowMapStage it owns its work planes; after the stage's handle completes, `water` holds the final
+    water depth (a river and lake mask) of the last payload, `count` tiles of resolution^2 cells."""
+
+    def __init__(self, ctx, iterations=200, initialWater=1e-4, rain=1e-4, evaporation=0.01, capacity=1.0, dissolve=0.3,
+                 deposit=0.3, minTilt=0.01):
+        super().__init__(ctx)
+        self.iterations = iterations
+        self.initialWater = initialWater
+        self.rain = rain
+        self.evaporation = evaporation
+        self.capacity = capacity
+        self.dissolve = dissolve
+        self.deposit = deposit
+        self.minTilt = minTilt
+        self.resolution = 0
+        self.count = 0
+        self.work = None  # nz_hydraulic_erosion_work_floats planes; the first count * resolution^2 floats: the water
+
+    def DisposeArrays(self):
+        if self.work is not None and self.work.IsCreated:
+            self.work.Dispose()
+        self.work = None
+
+    def ResizeNativeContainers(self, size):
+        self.DisposeArrays()
+        self.work = self.ctx.alloc(N.lib.nz_hydraulic_erosion_work_floats(self.resolution, self.count))
+
+    def _params(self):
+        return (self.iterations, self.initialWater, self.rain, self.evaporation, self.capacity, self.dissolve, self.deposit,
+                self.minTilt)
+
+    @property
+    def water(self):
+        """The water plane(s) of the last run: a view of the first count * resolution^2 floats of the work planes."""
+        return self.work.offset(0, self.count * self.resolution * self.resolution)
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        # the work planes are sized on the payload's cell count (count * resolution^2), as CheckRequirements tracks it
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        if d.write is not None:
+            self.jobHandle = _call_rw(self.ctx, "nz_hydraulic_erosion_stage_rw", d, self.work.ptr, *self._params(),
+                                      dep=dependency)
+            return
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_hydraulic_erosion_stage_batch", d.data.ptr, self.work.ptr, *self._params(),
+                                           d.resolution, d.count, dep=dependency)
+            return
+        self.jobHandle = self.ctx.call("nz_hydraulic_erosion_stage", d.data.ptr, self.work.ptr, *self._params(),
+                                       d.resolution, dep=dependency)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
     def __init__(self, ctx, meshType=MeshType.SquareGridHeightMap):
         super().__init__(ctx)
