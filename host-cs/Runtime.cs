@@ -40,6 +40,15 @@ namespace xshazwar.noize.hip {
         public int asRank, asWorld;
     }
 
+    // grid hydraulic erosion's scalars, border mode and optional planes (nz_hydraulic_erosion_ex*); IntPtr.Zero = option off
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzHydraulicDesc {                                                                  // nz_hydraulic_desc
+        public int iterations;
+        public float initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt;
+        public int border;
+        public IntPtr rainMap, hardness, wear, deposits;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

@@ -249,16 +249,31 @@ namespace xshazwar.noize.hip {
     // Grid hydraulic erosion with sediment transport (new-framework feature; the model: nz_hydraulic_erosion_stage in
     // include/noize_hip.h).  Owns its work planes like FlowMapStage; once the handle completes, Water holds the final water
     // depth of the last payload (count * resolution^2 floats), a river and lake mask.
+    // border = Open lets water and sediment run off the tile; rainMap / hardness are planes of the payload's size the caller
+    // supplies and keeps alive (rain * rainMap, dissolve * (1 - hardness)); recordMasks makes the stage own Wear and Deposits.
+    // With all four at their defaults the stage calls the plain entries.
+    public enum HydraulicBorder { Closed = 0, Open = 1 }                                            // enum nz_hydraulic_border
+
     public class HydraulicErosionStage : PipelineStage {
         public int iterations = 200;
         public float initialWater = 1e-4f, rain = 1e-4f, evaporation = 0.01f, capacity = 1f, dissolve = 0.3f, deposit = 0.3f, minTilt = 0.01f;
+        public HydraulicBorder border = HydraulicBorder.Closed;
+        public DeviceTile rainMap = null;
+        public DeviceTile hardness = null;
+        public bool recordMasks = false;
         DeviceTile work;                         // nz_hydraulic_erosion_work_floats planes; the first count * resolution^2 floats: the water
+        DeviceTile masks;                        // recordMasks: wear, then deposits, count * resolution^2 floats each
         int resolution, count = 1;
         public HydraulicErosionStage(GpuContext ctx) : base(ctx) {}
-        public DeviceTile Water => work?.Offset(0, count * resolution * resolution);
+        int Cells => count * resolution * resolution;
+        public DeviceTile Water => work?.Offset(0, Cells);
+        public DeviceTile Wear => masks?.Offset(0, Cells);
+        public DeviceTile Deposits => masks?.Offset(Cells, Cells);
         public override void ResizeNativeContainers(int size) {
             work?.Dispose();
             work = ctx.Alloc((int) (ulong) Native.nz_hydraulic_erosion_work_floats(resolution, count));
+            masks?.Dispose();
+            masks = recordMasks ? ctx.Alloc(2 * Cells) : null;
         }
         public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
             if (requirements.data is GeneratorData g) {
@@ -268,6 +283,27 @@ namespace xshazwar.noize.hip {
             CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
             GeneratorData d = (GeneratorData) requirements.data;
             ulong h;
+            if (border != HydraulicBorder.Closed || rainMap != null || hardness != null || recordMasks) {
+                foreach (DeviceTile m in new[] { rainMap, hardness })   // before any launch
+                    if (m != null && m.Length != Cells) throw new Exception($"HydraulicErosionStage: a map of {m.Length} floats does not fit the payload's {Cells}");
+                if (recordMasks && (masks == null || masks.Length != 2 * Cells)) ResizeNativeContainers(Cells);
+                NzHydraulicDesc desc = new NzHydraulicDesc {
+                    iterations = iterations, initialWater = initialWater, rain = rain, evaporation = evaporation, capacity = capacity,
+                    dissolve = dissolve, deposit = deposit, minTilt = minTilt, border = (int) border,
+                    rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero, hardness = hardness != null ? hardness.Ptr : IntPtr.Zero,
+                    wear = recordMasks ? Wear.Ptr : IntPtr.Zero, deposits = recordMasks ? Deposits.Ptr : IntPtr.Zero };
+                if (d.write != null) {
+                    NzRwTile t = new NzRwTile { read = d.data.Ptr, write = d.write.Ptr, resolution = d.resolution, count = count };
+                    Native.Check(Native.nz_hydraulic_erosion_ex_rw(ctx.Handle, ref t, work.Ptr, ref desc, dependency.id, out h), "nz_hydraulic_erosion_ex_rw");
+                    Adopt(d, t);
+                } else if (d is GeneratorDataBatch eb) {
+                    Native.Check(Native.nz_hydraulic_erosion_ex_batch(ctx.Handle, eb.data.Ptr, work.Ptr, ref desc, eb.resolution, eb.count, dependency.id, out h), "nz_hydraulic_erosion_ex_batch");
+                } else {
+                    Native.Check(Native.nz_hydraulic_erosion_ex(ctx.Handle, d.data.Ptr, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_hydraulic_erosion_ex");
+                }
+                jobHandle = Done(h);
+                return;
+            }
             if (d.write != null) {
                 NzRwTile t = new NzRwTile { read = d.data.Ptr, write = d.write.Ptr, resolution = d.resolution, count = count };
                 Native.Check(Native.nz_hydraulic_erosion_stage_rw(ctx.Handle, ref t, work.Ptr, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, dependency.id, out h), "nz_hydraulic_erosion_stage_rw");
@@ -279,7 +315,7 @@ namespace xshazwar.noize.hip {
             }
             jobHandle = Done(h);
         }
-        public override void OnDestroy() { work?.Dispose(); work = null; }
+        public override void OnDestroy() { work?.Dispose(); work = null; masks?.Dispose(); masks = null; }
     }
 
     public class MeshTileStage : PipelineStage {

@@ -373,6 +373,49 @@ int32_t nz_hydraulic_erosion_stage_batch(nz_ctx *ctx, float *src, float *work, i
                                          float rain, float evaporation, float capacity, float dissolve, float deposit,
                                          float minTilt, int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
 
+/* The same model opened up: four independent options.  With all four off the arithmetic is the one above, operation for
+ * operation, and the _ex entries give the entries above bit for bit (which are the _ex entries with everything off).
+ *   a. border: NZ_HYDRAULIC_BORDER_CLOSED is the model above.  NZ_HYDRAULIC_BORDER_OPEN differs in two places; every other
+ *      clamped read (the discharge of step 4, the gradient of step 5, bmin4 of step 7) stays a clamp-to-edge read:
+ *      step 2: a neighbour beyond the border has the total height b of the border cell itself -- its bed with no water on
+ *              it -- instead of the clamped b + d1, so dX = (b + d1) - b: the cell's own water column is its head towards
+ *              the outside, and the outflow over the border is scaled by the same K as the other three;
+ *      step 3: the in-term of a neighbour beyond the border is +0 instead of the clamped read.
+ *      Step 8 takes 0 from beyond the border and counts every a_X in `out` in both modes, so with an open border the
+ *      sediment leaves with the water.  A corner cell has two neighbours outside; both rules apply per direction.
+ *   b. rainMap (plane like the heights, every value finite and >= 0): step 1 is d1 = d + rain * rainMap[c], one multiply
+ *      and one add, no contraction.  A plane of ones gives the no-map result bit for bit.
+ *   c. hardness (plane, values in [0, 1]; 1 = cannot be eroded): in the erosion branch of step 7 `dissolve` is replaced by
+ *      kd = dissolve * (1 - hardness[c]).  Deposition is not affected.  A plane of zeros gives the no-map result bit for
+ *      bit.
+ *   d. wear, deposits (output planes, either or both): wear[c] is the sum of e over the iterations in which cell c took the
+ *      erosion branch of step 7, deposits[c] the sum of e over the iterations in which it took the other branch, plus the
+ *      sediment s that settles on the cell after the last iteration: float32 running sums in iteration order, starting
+ *      from +0, every iteration adding e to the mask of the branch taken and +0 to the other.  The planes need not be
+ *      cleared by the caller; iterations == 0 writes zeros.  result = input - wear + deposits cell by cell up to rounding.
+ * nz_hydraulic_desc carries the eight scalars of the entries above (same ranges), `border`, and the four planes; a NULL
+ * plane is an option left off.  Each plane holds count * resolution^2 floats, the tiles of a batch back to back like `src`.
+ * The masks may not overlap `src` (either plane of an _rw pair), the maps, each other or `work`; the maps are read-only and
+ * may alias each other.  A NULL desc, a border mode other than the two, or an overlapping mask is NZ_ERR_INVALID, the
+ * message names the argument, and nothing is written.  The CONTENTS of the maps are not validated on the device: values
+ * outside the ranges above are the caller's.  `work` keeps its size and layout; the maps and masks are the caller's planes. */
+enum nz_hydraulic_border { NZ_HYDRAULIC_BORDER_CLOSED = 0, NZ_HYDRAULIC_BORDER_OPEN = 1 };
+typedef struct nz_hydraulic_desc {
+    int32_t iterations;
+    float initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt;
+    int32_t border;          /* enum nz_hydraulic_border */
+    const float *rainMap;    /* NULL: rain everywhere */
+    const float *hardness;   /* NULL: dissolve everywhere */
+    float *wear;             /* NULL: not recorded */
+    float *deposits;         /* NULL: not recorded */
+} nz_hydraulic_desc;
+int32_t nz_hydraulic_erosion_ex(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc, int32_t resolution,
+                                nz_handle dep, nz_handle *out);
+int32_t nz_hydraulic_erosion_ex_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_hydraulic_desc *desc, nz_handle dep,
+                                   nz_handle *out);
+int32_t nz_hydraulic_erosion_ex_batch(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc,
+                                      int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
+
 /* ---- batched stage bodies (new-framework feature) ------------------------------------------------
  * `count` independent tiles of resolution^2 cells stored back to back (tile k at data + k * resolution^2) go
  * through one launch sequence: the reference runs one BasePipeline per tile request

@@ -8,7 +8,7 @@ from . import _native
 from ._native import NoizeError, Stripe
 from .runtime import Context, DeviceTile, JobHandle
 from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DownsampleData, ErosionStage, FlowMapStage, FractalNoise, FractalShape, GaussSigma,
-                       GeneratorData, GeneratorDataBatch, HydraulicErosionStage, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
+                       GeneratorData, GeneratorDataBatch, HydraulicBorder, HydraulicErosionStage, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
                        ReducePipeline, ReduceStage, ShapedNoiseStage, Upstream, WarpedNoiseStage,
                        ReductionType, StageGaussianBlur, StageThermalErosion,

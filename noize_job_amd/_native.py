@@ -71,6 +71,16 @@ class ShardedDesc(C.Structure):
                 ("asRank", C.c_int32), ("asWorld", C.c_int32)]
 
 
+class HydraulicDesc(C.Structure):
+    """nz_hydraulic_desc (include/noize_hip.h): the scalars of grid hydraulic erosion, the border mode and the four optional
+    planes (device addresses; None = the option is off)."""
+    _fields_ = ([("iterations", C.c_int32)] +
+                [(n, C.c_float) for n in ("initialWater", "rain", "evaporation", "capacity", "dissolve", "deposit", "minTilt")] +
+                [("border", C.c_int32), ("rainMap", C.c_void_p), ("hardness", C.c_void_p), ("wear", C.c_void_p),
+                 ("deposits", C.c_void_p)])
+
+
+hd_p = C.POINTER(HydraulicDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -78,6 +88,7 @@ NZ_OK, NZ_ERR_INVALID, NZ_ERR_UNSUPPORTED, NZ_ERR_HIP, NZ_ERR_NOMEM, NZ_ERR_NO_D
 NZ_COMM_ID_BYTES = 128
 NZ_HALO_RECOMPUTE, NZ_HALO_EXCHANGE, NZ_HALO_EXCHANGE_ONCE = 0, 1, 2
 NZ_FLOAT_STRICT, NZ_FLOAT_FAST, NZ_FLOAT_RELAXED = 0, 1, 2
+NZ_HYDRAULIC_BORDER_CLOSED, NZ_HYDRAULIC_BORDER_OPEN = 0, 1
 
 _i, _f, _sz = C.c_int32, C.c_float, C.c_size_t
 _tail = [handle_t, handle_p]  # (dep, out)
@@ -152,6 +163,9 @@ SIGNATURES = {
     "nz_hydraulic_erosion_stage": (_i, [ctx_p, dev_ptr, dev_ptr, _i] + [_f] * 7 + [_i] + _tail),
     "nz_hydraulic_erosion_stage_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, _i] + [_f] * 7 + _tail),
     "nz_hydraulic_erosion_stage_batch": (_i, [ctx_p, dev_ptr, dev_ptr, _i] + [_f] * 7 + [_i, _i] + _tail),
+    "nz_hydraulic_erosion_ex": (_i, [ctx_p, dev_ptr, dev_ptr, hd_p, _i] + _tail),
+    "nz_hydraulic_erosion_ex_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, hd_p] + _tail),
+    "nz_hydraulic_erosion_ex_batch": (_i, [ctx_p, dev_ptr, dev_ptr, hd_p, _i, _i] + _tail),
     "nz_constant_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, _f, _i] + _tail),
     "nz_reduction_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, dev_ptr, _i] + _tail),
     "nz_update_flow_from_track": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, _f, _f, _f, _i] + _tail),

@@ -13,6 +13,18 @@
 // radius -- so the clamp-to-edge reads are the flow map's.  The sediment's in-flow alone reads unclamped neighbours (0
 // beyond the border).  Strict IEEE binary32 in every float mode, no contraction (-ffp-contract=off, Makefile); every step
 // is a radius-1 stencil with no atomics, so the result is independent of the launch shape.
+//
+// The _ex entries' options are compile-time flags of the same kernel (OPT = NZ_HYD_OPEN | NZ_HYD_MAPS | NZ_HYD_MASKS); with
+// all of them off it is the kernel above with the same arguments, and keeps its own four instantiations:
+//   OPEN   open border: a neighbour beyond the border stands at the border cell's bed height in the flux (phase A) and
+//          sends nothing back in the water update (phase C).  "Beyond the border" is a test on the plane coordinate of
+//          the cell an LDS cell stands for, so the halo copies of a border cell compute the border cell's own flux
+//   MAPS   rain map (read in the fill, radius 3, clamped coordinates like b) and hardness map.  The hardness scales the
+//          erosion of every cell whose sediment the tile reads -- radius 1 -- so it is read straight from the plane at the
+//          clamped coordinate in phase B, next to the cell's sediment, and takes no LDS.  A NULL map of the pair reads
+//          as ones / zeros, which is the no-map arithmetic bit for bit (rain * 1, dissolve * (1 - 0))
+//   MASKS  wear / deposits: phase B leaves the tile cell's e of this iteration in LDS (WE / DE, +0 in the branch not
+//          taken), phase C's owner of the cell adds it to the plane: a read-modify-write of one element by one thread
 #include "nz_internal.hpp"
 #include "nz_flow_common.hpp"
 
@@ -29,13 +41,18 @@ __device__ __forceinline__ float smin(float a, float c) { return c < a ? c : a; 
 
 // FIRST: the state is the start state (water initialWater, no sediment, no flux) and `in` is not read.
 // LAST: the launch writes b + s to h_out and the water to out[0] only.
-template <bool FIRST, bool LAST>
+// OPT: the _ex options (above).  X: one nz_hydraulic_ex with the options' planes when OPT != 0, no argument otherwise.
+template <bool FIRST, bool LAST, int OPT = 0, class... X>
 __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__ h_in, float *__restrict__ h_out,
-                                                       nz_hydraulic_planes p, nz_hydraulic_params k, int res) {
+                                                       nz_hydraulic_planes p, nz_hydraulic_params k, int res, X... xs) {
+    static_assert(sizeof...(X) == (OPT ? 1 : 0), "the options' planes travel with OPT != 0 only");
+    constexpr bool OPEN = (OPT & NZ_HYD_OPEN) != 0, MAPS = (OPT & NZ_HYD_MAPS) != 0, MASKS = (OPT & NZ_HYD_MASKS) != 0;
+    const nz_hydraulic_ex x{xs...};
     __shared__ float B[LN], D1[LN];           // radius 3
     __shared__ float FN[LN], FS[LN], FE[LN], FW[LN];  // radius 2 (same layout)
     __shared__ float AN[LN], AS[LN], AE[LN], AW[LN];  // radius 1 (same layout)
     __shared__ float BN[HX * HZ], PS[HX * HZ];        // the tile: eroded height, s - out
+    __shared__ float WE[MASKS ? HX * HZ : 1], DE[MASKS ? HX * HZ : 1];  // the tile: this iteration's wear, deposit
 
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * HX, z0 = blockIdx.y * HZ;
@@ -51,7 +68,8 @@ __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__
         const int px = clampi(x0 - HR + lx, 0, hi), pz = clampi(z0 - HR + lz, 0, hi);
         const size_t c = base + (size_t)pz * res + px;
         B[i] = h_in[c];
-        D1[i] = (FIRST ? k.initial_water : p.in[0][c]) + k.rain;
+        if (MAPS) D1[i] = (FIRST ? k.initial_water : p.in[0][c]) + k.rain * (x.rain_map ? x.rain_map[c] : 1.0f);
+        else D1[i] = (FIRST ? k.initial_water : p.in[0][c]) + k.rain;
     }
     __syncthreads();
 
@@ -71,8 +89,14 @@ __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__
             old.n = p.in[2][c];
         }
         // totalHt = water + height, as nzo_flow_step / flow_step_kernel add them
-        const flux4 f = compute_flow(D1[l] + B[l], D1[l], D1[lW] + B[lW], D1[lE] + B[lE], D1[lS] + B[lS],
-                                     D1[lN] + B[lN], old);
+        flux4 f;
+        if (OPEN) {  // beyond the border: the border cell's own bed with no water on it
+            const float b = B[l];
+            f = compute_flow(D1[l] + b, D1[l], px - 1 < 0 ? b : D1[lW] + B[lW], px + 1 > hi ? b : D1[lE] + B[lE],
+                             pz - 1 < 0 ? b : D1[lS] + B[lS], pz + 1 > hi ? b : D1[lN] + B[lN], old);
+        } else {
+            f = compute_flow(D1[l] + B[l], D1[l], D1[lW] + B[lW], D1[lE] + B[lE], D1[lS] + B[lS], D1[lN] + B[lN], old);
+        }
         FW[l] = f.w;
         FE[l] = f.e;
         FS[l] = f.s;
@@ -98,16 +122,20 @@ __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__
         const float S = smax(k.min_tilt, sqrtf(g2 / (1.0f + g2)));
         const float C = (k.capacity * q) * S;
         float s = FIRST ? 0.0f : p.in[1][base + (size_t)pz * res + px];
-        float bb;
+        float kd = k.dissolve;
+        if (MAPS) kd = k.dissolve * (1.0f - (x.hardness ? x.hardness[base + (size_t)pz * res + px] : 0.0f));
+        float bb, we = 0.0f, de = 0.0f;  // this iteration's wear / deposit of the cell: e in the branch taken
         if (C > s) {
             const float bmin4 = smin(smin(smin(bW, bE), bS), bN);
-            const float e = smin(k.dissolve * (C - s), smax(0.0f, b - bmin4));
+            const float e = smin(kd * (C - s), smax(0.0f, b - bmin4));
             bb = b - e;
             s = s + e;
+            we = e;
         } else {
             const float e = k.deposit * (s - C);
             bb = b + e;
             s = s - e;
+            de = e;
         }
         const float d1 = D1[l];
         const float r = d1 >= 0x1p-126f ? TIMESTEP / d1 : 0.0f;  // the smallest normal: DT / d1 stays finite
@@ -120,6 +148,10 @@ __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__
         if (tx >= 0 && tx < HX && tz >= 0 && tz < HZ) {
             BN[tz * HX + tx] = bb;
             PS[tz * HX + tx] = s - (((aW + aE) + aS) + aN);
+            if (MASKS) {
+                WE[tz * HX + tx] = we;
+                DE[tz * HX + tx] = de;
+            }
         }
     }
     __syncthreads();
@@ -134,8 +166,12 @@ __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__
         const int lW = lz * LW + lx_of(clampi(px - 1, 0, hi)), lE = lz * LW + lx_of(clampi(px + 1, 0, hi));
         const int lS = lz_of(clampi(pz - 1, 0, hi)) * LW + lx, lN = lz_of(clampi(pz + 1, 0, hi)) * LW + lx;
         const flux4 own{FW[l], FE[l], FS[l], FN[l]};
-        const float d2 = update_water(D1[l], own, FE[lW], FW[lE], FN[lS], FS[lN]);
-        // in-flow: 0 from beyond the border (no flux leaves the tile, so the sediment is conserved)
+        float d2;
+        if (OPEN)  // nothing comes back from beyond the border
+            d2 = update_water(D1[l], own, px > 0 ? FE[lW] : 0.0f, px < hi ? FW[lE] : 0.0f, pz > 0 ? FN[lS] : 0.0f,
+                              pz < hi ? FS[lN] : 0.0f);
+        else d2 = update_water(D1[l], own, FE[lW], FW[lE], FN[lS], FS[lN]);
+        // in-flow: 0 from beyond the border (with a closed border no flux leaves the tile, so the sediment is conserved)
         const float inW = px > 0 ? AE[l - 1] : 0.0f;
         const float inE = px < hi ? AW[l + 1] : 0.0f;
         const float inS = pz > 0 ? AN[l - LW] : 0.0f;
@@ -155,16 +191,42 @@ __global__ __launch_bounds__(HT) void hydraulic_kernel(const float *__restrict__
             p.out[4][c] = own.e;
             p.out[5][c] = own.w;
         }
+        if (MASKS) {  // running sums in iteration order from +0; the settled sediment joins the deposits last
+            if (x.wear) x.wear[c] = (FIRST ? 0.0f : x.wear[c]) + WE[i];
+            if (x.deposits) {
+                const float dep = (FIRST ? 0.0f : x.deposits[c]) + DE[i];
+                x.deposits[c] = LAST ? dep + s : dep;
+            }
+        }
+    }
+}
+
+// launches hydraulic_kernel<FIRST, LAST, opt> for opt in 1 .. 7
+template <bool FIRST, bool LAST, int OPT = 7>
+void launch_ex(int opt, dim3 grid, hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
+               const nz_hydraulic_params &k, int res, const nz_hydraulic_ex &x) {
+    if constexpr (OPT > 0) {
+        if (opt == OPT) NZ_LAUNCH((hydraulic_kernel<FIRST, LAST, OPT, nz_hydraulic_ex>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res, x);
+        else launch_ex<FIRST, LAST, OPT - 1>(opt, grid, s, h_in, h_out, p, k, res, x);
     }
 }
 
 }  // namespace
 
 int32_t nz_launch_hydraulic(hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
-                            const nz_hydraulic_params &k, int res, int count, int first, int last) {
+                            const nz_hydraulic_params &k, int res, int count, int first, int last,
+                            const nz_hydraulic_ex *ex) {
     if (res <= 0 || count <= 0) return NZ_OK;
     const dim3 grid((res + HX - 1) / HX, (res + HZ - 1) / HZ, count);
-    if (first && last) NZ_LAUNCH((hydraulic_kernel<true, true>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
+    const int opt = !ex ? 0
+                        : (ex->open ? NZ_HYD_OPEN : 0) | (ex->rain_map || ex->hardness ? NZ_HYD_MAPS : 0) |
+                              (ex->wear || ex->deposits ? NZ_HYD_MASKS : 0);
+    if (opt) {
+        if (first && last) launch_ex<true, true>(opt, grid, s, h_in, h_out, p, k, res, *ex);
+        else if (first) launch_ex<true, false>(opt, grid, s, h_in, h_out, p, k, res, *ex);
+        else if (last) launch_ex<false, true>(opt, grid, s, h_in, h_out, p, k, res, *ex);
+        else launch_ex<false, false>(opt, grid, s, h_in, h_out, p, k, res, *ex);
+    } else if (first && last) NZ_LAUNCH((hydraulic_kernel<true, true>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
     else if (first) NZ_LAUNCH((hydraulic_kernel<true, false>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
     else if (last) NZ_LAUNCH((hydraulic_kernel<false, true>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);
     else NZ_LAUNCH((hydraulic_kernel<false, false>), grid, dim3(HT), 0, s, h_in, h_out, p, k, res);

@@ -318,8 +318,18 @@ struct nz_hydraulic_params {
     float initial_water, rain, keep;  // keep = 1 - evaporation
     float capacity, dissolve, deposit, min_tilt;
 };
+// the _ex entries' options (include/noize_hip.h): open border, the two read-only maps, the two running-sum masks; a NULL
+// plane is an option left off.  Planes of count * res^2 floats like the heights
+struct nz_hydraulic_ex {
+    int open = 0;
+    const float *rain_map = nullptr, *hardness = nullptr;
+    float *wear = nullptr, *deposits = nullptr;
+};
+enum { NZ_HYD_OPEN = 1, NZ_HYD_MAPS = 2, NZ_HYD_MASKS = 4 };  // the kernel's compile-time option groups
+// ex: NULL or all off -> the default kernels
 int32_t nz_launch_hydraulic(hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
-                            const nz_hydraulic_params &k, int res, int count, int first, int last);
+                            const nz_hydraulic_params &k, int res, int count, int first, int last,
+                            const nz_hydraulic_ex *ex = nullptr);
 
 int32_t nz_launch_mesh_planar(hipStream_t s, void *vertices, uint32_t *indices, int res);
 int32_t nz_launch_mesh(hipStream_t s, int meshType, void *vertices, uint32_t *indices, int res, int in_res,

@@ -1016,15 +1016,40 @@ static int32_t check_hydraulic(int32_t iterations, float initialWater, float rai
     return NZ_OK;
 }
 
+// the options of a nz_hydraulic_desc as the launches take them.  h0 / h1: the height plane(s) the call reads or writes
+// (h1 may be NULL), n floats each like every plane of the desc; the masks may overlap none of them, nor the maps, each
+// other or `work`
+static int32_t check_hydraulic_planes(const nz_hydraulic_desc &d, const float *h0, const float *h1, const float *work,
+                                      size_t n, nz_hydraulic_ex *ex) {
+    NZ_REQUIRE(d.border == NZ_HYDRAULIC_BORDER_CLOSED || d.border == NZ_HYDRAULIC_BORDER_OPEN, "border %d is not a mode",
+               d.border);
+    auto overlap = [](const float *a, size_t na, const float *b, size_t nb) {
+        return a && b && (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+    };
+    const struct { const char *name; const float *p; } masks[] = {{"wear", d.wear}, {"deposits", d.deposits}};
+    for (const auto &m : masks) {
+        const struct { const char *name; const float *p; size_t n; } others[] = {
+            {"src", h0, n}, {"the write plane", h1, n}, {"work", work, (size_t)HYD_PLANES * n},
+            {"rainMap", d.rainMap, n}, {"hardness", d.hardness, n}};
+        for (const auto &o : others) NZ_REQUIRE(!overlap(m.p, n, o.p, o.n), "%s overlaps %s", m.name, o.name);
+    }
+    NZ_REQUIRE(!overlap(d.wear, n, d.deposits, n), "wear overlaps deposits");
+    *ex = nz_hydraulic_ex{d.border == NZ_HYDRAULIC_BORDER_OPEN, d.rainMap, d.hardness, d.wear, d.deposits};
+    return NZ_OK;
+}
+
 // `iterations` launches on `count` tiles; the height ping-pongs between h0 (which holds the input) and h1, the state
 // between the two sets of `work`.  The result lands in h0 when `iterations` is even and in h1 when it is odd (*in_h1);
 // keep_h0: the caller wants it in h0 whatever the count, and an odd count copies h0 to h1 first.  Ends with the final
-// water in work plane 0 (initialWater itself when there is no iteration).
+// water in work plane 0 (initialWater itself when there is no iteration).  ex: the _ex options (all off: the default
+// kernels); its masks are written by the first launch, or cleared here when there is none.
 static int32_t hydraulic_series(nz_ctx *ctx, float *h0, float *h1, float *work, int res, int count, int32_t iterations,
-                                const nz_hydraulic_params &k, bool keep_h0, bool *in_h1) {
+                                const nz_hydraulic_params &k, const nz_hydraulic_ex &ex, bool keep_h0, bool *in_h1) {
     const size_t n = (size_t)res * res * count;
     *in_h1 = false;
     if (iterations == 0) {
+        if (ex.wear) NZ_TRY(nz_launch_fill(ctx->stream, ex.wear, n, 0.0f));
+        if (ex.deposits) NZ_TRY(nz_launch_fill(ctx->stream, ex.deposits, n, 0.0f));
         nz_ctx_arm_last_launch(ctx);
         return nz_launch_fill(ctx->stream, work, n, k.initial_water);
     }
@@ -1044,57 +1069,97 @@ static int32_t hydraulic_series(nz_ctx *ctx, float *h0, float *h1, float *work, 
             p.out[i] = last ? (i == 0 ? work : nullptr) : sets[(it + 1) & 1].out[i];
         }
         if (last) nz_ctx_arm_last_launch(ctx);
-        NZ_TRY(nz_launch_hydraulic(ctx->stream, cur, nxt, p, k, res, count, first, last));
+        NZ_TRY(nz_launch_hydraulic(ctx->stream, cur, nxt, p, k, res, count, first, last, &ex));
         std::swap(cur, nxt);
     }
     *in_h1 = cur == h1;
     return NZ_OK;
 }
 
-static int32_t hydraulic_stage_impl(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater,
-                                    float rain, float evaporation, float capacity, float dissolve, float deposit,
-                                    float minTilt, int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+// every in-place entry: the old ones come with a desc of their scalars and every option off
+static int32_t hydraulic_stage_impl(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc, int32_t resolution,
+                                    int32_t count, nz_handle dep, nz_handle *out) {
     NZ_BEGIN(ctx, dep);
     NZ_TRY(check_batch(resolution, count));
     NZ_REQUIRE(src && work, "src/work is NULL");
+    NZ_REQUIRE(desc, "desc is NULL");
     nz_hydraulic_params k;
-    NZ_TRY(check_hydraulic(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, &k));
+    NZ_TRY(check_hydraulic(desc->iterations, desc->initialWater, desc->rain, desc->evaporation, desc->capacity, desc->dissolve,
+                           desc->deposit, desc->minTilt, &k));
+    nz_hydraulic_ex ex;
+    NZ_TRY(check_hydraulic_planes(*desc, src, nullptr, work, (size_t)resolution * resolution * count, &ex));
     float *h1 = work + (size_t)(HYD_PLANES - 1) * resolution * resolution * count;
     bool in_h1;
     nz_ctx_handle_rides(ctx, out != nullptr);  // (hydraulic_series arms its last launch)
-    NZ_TRY(hydraulic_series(ctx, src, h1, work, resolution, count, iterations, k, true, &in_h1));
+    NZ_TRY(hydraulic_series(ctx, src, h1, work, resolution, count, desc->iterations, k, ex, true, &in_h1));
     return nz_ctx_finish(ctx, out);
+}
+
+static int32_t hydraulic_rw_impl(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_hydraulic_desc *desc, nz_handle dep,
+                                 nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(desc, "desc is NULL");
+    nz_hydraulic_params k;
+    NZ_TRY(check_hydraulic(desc->iterations, desc->initialWater, desc->rain, desc->evaporation, desc->capacity, desc->dissolve,
+                           desc->deposit, desc->minTilt, &k));
+    nz_hydraulic_ex ex;
+    NZ_TRY(check_hydraulic_planes(*desc, tile->read, tile->write, work,
+                                  (size_t)tile->resolution * tile->resolution * tile->count, &ex));
+    bool in_h1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (hydraulic_series arms its last launch)
+    NZ_TRY(hydraulic_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, desc->iterations, k, ex, false,
+                            &in_h1));
+    rw_swap(tile, in_h1);
+    return nz_ctx_finish(ctx, out);
+}
+
+static nz_hydraulic_desc hydraulic_plain_desc(int32_t iterations, float initialWater, float rain, float evaporation,
+                                              float capacity, float dissolve, float deposit, float minTilt) {
+    return nz_hydraulic_desc{iterations, initialWater, rain,    evaporation, capacity, dissolve, deposit,
+                             minTilt,    NZ_HYDRAULIC_BORDER_CLOSED, nullptr, nullptr, nullptr, nullptr};
 }
 
 extern "C" int32_t nz_hydraulic_erosion_stage(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater,
                                               float rain, float evaporation, float capacity, float dissolve, float deposit,
                                               float minTilt, int32_t resolution, nz_handle dep, nz_handle *out) {
-    return hydraulic_stage_impl(ctx, src, work, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit,
-                                minTilt, resolution, 1, dep, out);
+    const nz_hydraulic_desc d =
+        hydraulic_plain_desc(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt);
+    return hydraulic_stage_impl(ctx, src, work, &d, resolution, 1, dep, out);
 }
 
 extern "C" int32_t nz_hydraulic_erosion_stage_batch(nz_ctx *ctx, float *src, float *work, int32_t iterations,
                                                     float initialWater, float rain, float evaporation, float capacity,
                                                     float dissolve, float deposit, float minTilt, int32_t resolution,
                                                     int32_t count, nz_handle dep, nz_handle *out) {
-    return hydraulic_stage_impl(ctx, src, work, iterations, initialWater, rain, evaporation, capacity, dissolve, deposit,
-                                minTilt, resolution, count, dep, out);
+    const nz_hydraulic_desc d =
+        hydraulic_plain_desc(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt);
+    return hydraulic_stage_impl(ctx, src, work, &d, resolution, count, dep, out);
 }
 
 extern "C" int32_t nz_hydraulic_erosion_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, int32_t iterations,
                                                  float initialWater, float rain, float evaporation, float capacity,
                                                  float dissolve, float deposit, float minTilt, nz_handle dep,
                                                  nz_handle *out) {
-    NZ_BEGIN(ctx, dep);
-    NZ_TRY(check_rw(tile));
-    NZ_REQUIRE(work, "work is NULL");
-    nz_hydraulic_params k;
-    NZ_TRY(check_hydraulic(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, &k));
-    bool in_h1;
-    nz_ctx_handle_rides(ctx, out != nullptr);  // (hydraulic_series arms its last launch)
-    NZ_TRY(hydraulic_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, iterations, k, false, &in_h1));
-    rw_swap(tile, in_h1);
-    return nz_ctx_finish(ctx, out);
+    const nz_hydraulic_desc d =
+        hydraulic_plain_desc(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt);
+    return hydraulic_rw_impl(ctx, tile, work, &d, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_ex(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc,
+                                           int32_t resolution, nz_handle dep, nz_handle *out) {
+    return hydraulic_stage_impl(ctx, src, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_ex_batch(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc,
+                                                 int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    return hydraulic_stage_impl(ctx, src, work, desc, resolution, count, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_ex_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_hydraulic_desc *desc,
+                                              nz_handle dep, nz_handle *out) {
+    return hydraulic_rw_impl(ctx, tile, work, desc, dep, out);
 }
 
 // ---------------------------------------------------------------------------------------------

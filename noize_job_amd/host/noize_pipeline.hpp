@@ -540,14 +540,23 @@ class FlowMapStage : public PipelineStage {
 // Grid hydraulic erosion with sediment transport (new-framework feature; the model: nz_hydraulic_erosion_stage in
 // include/noize_hip.h).  Owns its work planes like FlowMapStage; once the handle completes, water() holds the final water
 // depth of the last payload (waterLength() floats: count * resolution^2), a river and lake mask.
+// border = Open lets water and sediment run off the tile; rainMap / hardness are planes of the payload's size the caller
+// supplies and keeps alive (rain * rainMap, dissolve * (1 - hardness)); recordMasks makes the stage own wear() and
+// deposits(), waterLength() floats each.  With all four at their defaults the stage calls the plain entries.
+enum class HydraulicBorder { Closed, Open };
+
 class HydraulicErosionStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;
     int iterations = 200;
     float initialWater = 1e-4f, rain = 1e-4f, evaporation = .01f, capacity = 1.f, dissolve = .3f, deposit = .3f,
           minTilt = .01f;
+    HydraulicBorder border = HydraulicBorder::Closed;
+    const DeviceTile *rainMap = nullptr, *hardness = nullptr;
+    bool recordMasks = false;
     void ResizeNativeContainers(size_t) override {
         work.reset(new DeviceTile(ctx, nz_hydraulic_erosion_work_floats(resolution, count)));
+        masks.reset(recordMasks ? new DeviceTile(ctx, 2 * waterLength()) : nullptr);
     }
     void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
         auto *g = dynamic_cast<GeneratorData *>(requirements.data);
@@ -556,6 +565,28 @@ class HydraulicErosionStage : public PipelineStage {
         count = tile_count(g);
         auto *d = CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
         nz_handle h = 0;
+        if (border != HydraulicBorder::Closed || rainMap || hardness || recordMasks) {
+            for (const DeviceTile *m : {rainMap, hardness})  // before any launch
+                if (m && m->Length != waterLength()) throw std::runtime_error("HydraulicErosionStage: a map does not fit the payload");
+            if (recordMasks && (!masks || masks->Length != 2 * waterLength())) ResizeNativeContainers(0);
+            const nz_hydraulic_desc desc{iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt,
+                                         (int32_t)border, rainMap ? rainMap->ptr : nullptr,
+                                         hardness ? hardness->ptr : nullptr, recordMasks ? masks->ptr : nullptr,
+                                         recordMasks ? masks->ptr + waterLength() : nullptr};
+            if (d->write) {
+                nz_rw_tile t = rw_pair(d, count);
+                check(nz_hydraulic_erosion_ex_rw(ctx, &t, work->ptr, &desc, dependency.id, &h), "nz_hydraulic_erosion_ex_rw");
+                rw_adopt(d, t);
+            } else if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+                check(nz_hydraulic_erosion_ex_batch(ctx, b->data->ptr, work->ptr, &desc, b->resolution, b->count,
+                                                    dependency.id, &h), "nz_hydraulic_erosion_ex_batch");
+            } else {
+                check(nz_hydraulic_erosion_ex(ctx, d->data->ptr, work->ptr, &desc, d->resolution, dependency.id, &h),
+                      "nz_hydraulic_erosion_ex");
+            }
+            jobHandle = done(h);
+            return;
+        }
         if (d->write) {
             nz_rw_tile t = rw_pair(d, count);
             check(nz_hydraulic_erosion_stage_rw(ctx, &t, work->ptr, iterations, initialWater, rain, evaporation, capacity,
@@ -580,11 +611,16 @@ class HydraulicErosionStage : public PipelineStage {
     }
     const float *water() const { return work ? work->ptr : nullptr; }
     size_t waterLength() const { return (size_t)count * resolution * resolution; }
-    void OnDestroy() override { work.reset(); }
+    const float *wear() const { return masks ? masks->ptr : nullptr; }  // recordMasks: waterLength() floats each
+    const float *deposits() const { return masks ? masks->ptr + waterLength() : nullptr; }
+    void OnDestroy() override {
+        work.reset();
+        masks.reset();
+    }
 
   private:
     int resolution = 0, count = 1;
-    std::unique_ptr<DeviceTile> work;
+    std::unique_ptr<DeviceTile> work, masks;  // masks: wear, then deposits
 };
 
 class MeshTileStage : public PipelineStage {

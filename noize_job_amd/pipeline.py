@@ -40,6 +40,11 @@ class FractalShape(enum.IntEnum):  # new-framework: the octave shape of ShapedNo
     Ridged = 2
 
 
+class HydraulicBorder(enum.IntEnum):  # new-framework: the tile border of HydraulicErosionStage (enum nz_hydraulic_border)
+    Closed = 0  # clamp to edge: no water and no sediment leave the tile
+    Open = 1    # the tile is cut out of a larger world: water and sediment run off the map
+
+
 class KernelFilterType(enum.IntEnum):  # Filter/Kernel/KernelJob.cs:79-94
     Gauss9_S1 = 0
     Gauss7_S1 = 1
@@ -644,10 +649,16 @@ class HydraulicErosionStage(PipelineStage):
     """Grid hydraulic erosion with sediment transport (new-framework feature; the model is the comment block of
     nz_hydraulic_erosion_stage in include/noize_hip.h): carves channels where water runs fast and steep and fills hollows
     where it slows.  Like FlowMapStage it owns its work planes; after the stage's handle completes, `water` holds the final
-    water depth (a river and lake mask) of the last payload, `count` tiles of resolution^2 cells."""
+    water depth (a river and lake mask) of the last payload, `count` tiles of resolution^2 cells.
+
+    border=Open lets water and sediment run off the tile.  rainMap / hardness: device planes of the payload's size
+    (count * resolution^2 floats) the caller supplies and keeps alive -- rain is multiplied by rainMap, dissolve by
+    1 - hardness.  recordMasks: the stage also owns `wear` and `deposits`, what every cell lost and what was laid down on
+    it (result = input - wear + deposits up to rounding).  With all four at their defaults the stage calls the plain
+    entries."""
 
     def __init__(self, ctx, iterations=200, initialWater=1e-4, rain=1e-4, evaporation=0.01, capacity=1.0, dissolve=0.3,
-                 deposit=0.3, minTilt=0.01):
+                 deposit=0.3, minTilt=0.01, border=HydraulicBorder.Closed, rainMap=None, hardness=None, recordMasks=False):
         super().__init__(ctx)
         self.iterations = iterations
         self.initialWater = initialWater
@@ -657,18 +668,26 @@ class HydraulicErosionStage(PipelineStage):
         self.dissolve = dissolve
         self.deposit = deposit
         self.minTilt = minTilt
+        self.border = border
+        self.rainMap = rainMap
+        self.hardness = hardness
+        self.recordMasks = recordMasks
         self.resolution = 0
         self.count = 0
         self.work = None  # nz_hydraulic_erosion_work_floats planes; the first count * resolution^2 floats: the water
+        self.masks = None  # recordMasks: wear, then deposits, count * resolution^2 floats each
 
     def DisposeArrays(self):
-        if self.work is not None and self.work.IsCreated:
-            self.work.Dispose()
-        self.work = None
+        for t in (self.work, self.masks):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.work = self.masks = None
 
     def ResizeNativeContainers(self, size):
         self.DisposeArrays()
         self.work = self.ctx.alloc(N.lib.nz_hydraulic_erosion_work_floats(self.resolution, self.count))
+        if self.recordMasks:
+            self.masks = self.ctx.alloc(2 * self.count * self.resolution * self.resolution)
 
     def _params(self):
         return (self.iterations, self.initialWater, self.rain, self.evaporation, self.capacity, self.dissolve, self.deposit,
@@ -679,6 +698,33 @@ class HydraulicErosionStage(PipelineStage):
         """The water plane(s) of the last run: a view of the first count * resolution^2 floats of the work planes."""
         return self.work.offset(0, self.count * self.resolution * self.resolution)
 
+    @property
+    def wear(self):
+        """recordMasks: what every cell of the last run lost to erosion (count * resolution^2 floats)."""
+        n = self.count * self.resolution * self.resolution
+        return self.masks.offset(0, n) if self.masks is not None else None
+
+    @property
+    def deposits(self):
+        """recordMasks: what was laid down on every cell of the last run, the settled sediment included."""
+        n = self.count * self.resolution * self.resolution
+        return self.masks.offset(n, n) if self.masks is not None else None
+
+    def _desc(self):
+        """The nz_hydraulic_desc of the extended entries, or None when every option is at its default."""
+        if (int(self.border) == HydraulicBorder.Closed and self.rainMap is None and self.hardness is None
+                and not self.recordMasks):
+            return None
+        n = self.count * self.resolution * self.resolution
+        for name, m in (("rainMap", self.rainMap), ("hardness", self.hardness)):
+            if m is not None and m.Length != n:
+                raise ValueError("HydraulicErosionStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
+        if self.recordMasks and (self.masks is None or self.masks.Length != 2 * n):  # (switched on after the first payload)
+            self.ResizeNativeContainers(n)
+        ptr = lambda t: t.ptr if t is not None else None  # noqa: E731
+        return N.HydraulicDesc(*self._params(), int(self.border), ptr(self.rainMap), ptr(self.hardness), ptr(self.wear),
+                               ptr(self.deposits))
+
     def Schedule(self, requirements, dependency):
         d = requirements.data
         if not isinstance(d, GeneratorData):
@@ -686,6 +732,18 @@ class HydraulicErosionStage(PipelineStage):
         # the work planes are sized on the payload's cell count (count * resolution^2), as CheckRequirements tracks it
         self.resolution, self.count = d.resolution, getattr(d, "count", 1)
         self.CheckRequirements(GeneratorData, requirements)
+        desc = self._desc()  # raises before any launch when a map does not fit the payload
+        if desc is not None:
+            if d.write is not None:
+                self.jobHandle = _call_rw(self.ctx, "nz_hydraulic_erosion_ex_rw", d, self.work.ptr, C.byref(desc),
+                                          dep=dependency)
+            elif isinstance(d, GeneratorDataBatch):
+                self.jobHandle = self.ctx.call("nz_hydraulic_erosion_ex_batch", d.data.ptr, self.work.ptr, C.byref(desc),
+                                               d.resolution, d.count, dep=dependency)
+            else:
+                self.jobHandle = self.ctx.call("nz_hydraulic_erosion_ex", d.data.ptr, self.work.ptr, C.byref(desc),
+                                               d.resolution, dep=dependency)
+            return
         if d.write is not None:
             self.jobHandle = _call_rw(self.ctx, "nz_hydraulic_erosion_stage_rw", d, self.work.ptr, *self._params(),
                                       dep=dependency)
