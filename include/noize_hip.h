@@ -7,6 +7,12 @@
  *   - `NativeSlice<float>` / `NativeArray<float>`  ->  `float*` DEVICE pointer (nz_tile_alloc, or any
  *     hipMalloc'd / torch allocation on the ctx's device); planes are row-major, index z*res + x
  *     (Pipeline/Tiles/TileData.cs:72-77).
+ *   - ALIGNMENT: a plane, map, mask, scratch (`tmp`, `work`) or argument array may be any 4-byte-aligned device pointer -- a
+ *     NativeSlice(start, length) of a larger allocation, tile k of a batch of odd resolution.  The launchers take their
+ *     16-byte paths where base and row pitch allow it and their scalar paths otherwise; results are the same bits, and no
+ *     entry reads or writes outside the planes it is given.  16-bit index streams need 2-byte alignment, RGBA32 textures
+ *     none.  The one exception: VERTEX STREAMS MUST BE 16-BYTE ALIGNED (48-byte records stored as float4); the mesh entries
+ *     refuse another address with NZ_ERR_INVALID ("vertex buffer must be 16-byte aligned") before any launch.
  *   - `JobHandle dependency` -> `nz_handle dep` (0 = default(JobHandle)); the returned JobHandle ->
  *     `nz_handle* out` (may be NULL: no handle, stream order only).  Work is enqueued asynchronously on the ctx's HIP stream;
  *     where an entry ends in a kernel launch its handle is that launch's completion event (no event record of its own).
@@ -456,7 +462,10 @@ int32_t nz_heightmap_mesh_batch(nz_ctx *ctx, int32_t meshType, void *vertices, u
 /* (Mesh, MeshData) -> device vertex stream of (resolution+1)^2 records
  * {float3 position; float3 normal; float4 tangent; float2 texCoord0} = 48 B
  * (PositionStream32.Stream0, Mesh/Streams/PositionStream.cs:77-82) and device index buffer of
- * 6*resolution^2 uint32 (TriangleUInt32, Mesh/Streams/Triangle.cs:19-27). */
+ * 6*resolution^2 uint32 (TriangleUInt32, Mesh/Streams/Triangle.cs:19-27).
+ * `vertices` must be 16-byte aligned (NZ_ERR_INVALID otherwise, nothing written; the same for nz_heightmap_mesh16,
+ * nz_heightmap_mesh_batch and nz_square_grid_mesh); `heights` and `indices` may be any 4-byte-aligned (uint16 indices:
+ * 2-byte-aligned) device pointer. */
 size_t nz_mesh_vertex_count(int32_t resolution);
 size_t nz_mesh_index_count(int32_t resolution);
 int32_t nz_heightmap_mesh(nz_ctx *ctx, int32_t meshType, void *vertices, uint32_t *indices,
