@@ -315,6 +315,20 @@ namespace xshazwar.noize.hip {
             }
             jobHandle = Done(h);
         }
+        // The stage on one row stripe of a larger grid (nz_hydraulic_stripe): `n` iterations with this stage's scalars and border in
+        // one call; the planes -- all of the stripe's shape -- are the caller's, and so is the exchange of 3 * n ghost rows before
+        // the call (Native.nz_halo_exchange on heightIn and, unless `first`, the six stateIn planes).  `maps`: {rainMap, hardness},
+        // `masks`: {wear, deposits}, IntPtr.Zero for an option left off.
+        public GpuJobHandle ScheduleStripe(IntPtr heightIn, IntPtr heightOut, IntPtr[] stateIn, IntPtr[] stateOut, IntPtr stripeWork,
+                                           ref NzStripe st, int n, bool first, bool last, IntPtr[] maps, IntPtr[] masks, GpuJobHandle dependency) {
+            NzHydraulicDesc desc = new NzHydraulicDesc {
+                iterations = n, initialWater = initialWater, rain = rain, evaporation = evaporation, capacity = capacity,
+                dissolve = dissolve, deposit = deposit, minTilt = minTilt, border = (int) border,
+                rainMap = maps[0], hardness = maps[1], wear = masks[0], deposits = masks[1] };
+            ulong h;
+            Native.Check(Native.nz_hydraulic_stripe(ctx.Handle, heightIn, heightOut, stateIn, stateOut, stripeWork, ref st, ref desc, first ? 1 : 0, last ? 1 : 0, dependency.id, out h), "nz_hydraulic_stripe");
+            return Done(h);
+        }
         public override void OnDestroy() { work?.Dispose(); work = null; masks?.Dispose(); masks = null; }
     }
 

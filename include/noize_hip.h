@@ -422,6 +422,41 @@ int32_t nz_hydraulic_erosion_ex_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, c
 int32_t nz_hydraulic_erosion_ex_batch(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc,
                                       int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
 
+/* The same model on a row stripe of a larger grid (nz_stripe; sharded runs and grids that are not square).  All planes --
+ * the heights, the six state planes {d, s, fN, fS, fE, fW}, the maps and the masks -- have the stripe's shape and pitch.
+ * The result on the owned rows equals the monolithic model on the grows x cols grid bit for bit: the only clamps and the
+ * only open border are at the global border (global rows 0 and grows-1, columns 0 and cols-1).
+ *   Launches.  desc->iterations = n >= 1 iterations of this call, one launch each.  An iteration reads heights and state
+ *     3 rows beyond the rows it produces (nz_hydraulic_stripe_halo_rows(n) = 3 * n for the call).  Launch j (from 0)
+ *     produces the owned rows widened by 3 * (n-1-j) rows on each side, clipped to the global grid: the ghost rows the
+ *     later launches need are recomputed, and the last launch produces exactly [own0, own1).
+ *   Ghost rows.  Every input plane must be valid up to 3 * n rows beyond the owned rows, or up to the global border
+ *     (checked against the buffer: too few rows in the buffer is NZ_ERR_INVALID).
+ *   first != 0: the start state is implied (d = initialWater, s = 0, flux 0); state_in is not read and may be NULL, so only
+ *     height_in needs ghost rows.
+ *   last != 0: the last launch writes b + s to height_out and the water to state_out[0], on the owned rows;
+ *     state_out[1..5] may be NULL when n == 1.  Without `last` the owned rows of height_out and of all six state_out planes
+ *     hold the state, to be handed to the next call as height_in / state_in once their ghost rows are exchanged.
+ *   Rows of the output planes inside the first launch's widened window but not owned hold unspecified values; rows outside
+ *     it, and the floats between cols and pitch, are not written.
+ *   `work` = nz_hydraulic_stripe_work_floats(st, n) floats: nothing for n == 1 (may be NULL), otherwise a second set of the
+ *     seven planes the launches ping-pong through.  The inputs are not modified.  No plane the call writes (height_out,
+ *     state_out, work, wear, deposits) may overlap any other plane of the call; planes that are only read may alias.
+ *   Maps.  rainMap is read on 3 * n rows beyond the owned ones, hardness on 3 * (n-1) + 1.
+ *   Masks.  wear and deposits are touched on the owned rows only (a ghost row is recomputed by two ranks and belongs to
+ *     one).  With `first` they are written instead of added to; with `last` the settled sediment joins deposits.
+ *   One stripe {cols, rows, 0, rows, 0, rows, 0} with first and last set is the monolithic model on a rows x cols grid,
+ *     square or not; on a square grid it equals nz_hydraulic_erosion_ex bit for bit.
+ * NZ_ERR_INVALID, the message naming the argument, and nothing written: the scalar ranges above; n < 1; a NULL state_in
+ * without `first`; a NULL plane that is required; too few ghost rows; any overlap. */
+/* ghost rows on each side a call of `iterations` iterations reads beyond the owned rows: 3 * iterations */
+int32_t nz_hydraulic_stripe_halo_rows(int32_t iterations);
+/* floats of `work`: 0 for one iteration, otherwise a second set of the seven planes of the stripe's shape */
+size_t nz_hydraulic_stripe_work_floats(const nz_stripe *st, int32_t iterations);
+int32_t nz_hydraulic_stripe(nz_ctx *ctx, const float *height_in, float *height_out, const float *const *state_in,
+                            float *const *state_out, float *work, const nz_stripe *st, const nz_hydraulic_desc *desc,
+                            int32_t first, int32_t last, nz_handle dep, nz_handle *out);
+
 /* ---- batched stage bodies (new-framework feature) ------------------------------------------------
  * `count` independent tiles of resolution^2 cells stored back to back (tile k at data + k * resolution^2) go
  * through one launch sequence: the reference runs one BasePipeline per tile request

@@ -166,6 +166,10 @@ SIGNATURES = {
     "nz_hydraulic_erosion_ex": (_i, [ctx_p, dev_ptr, dev_ptr, hd_p, _i] + _tail),
     "nz_hydraulic_erosion_ex_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, hd_p] + _tail),
     "nz_hydraulic_erosion_ex_batch": (_i, [ctx_p, dev_ptr, dev_ptr, hd_p, _i, _i] + _tail),
+    "nz_hydraulic_stripe_halo_rows": (_i, [_i]),
+    "nz_hydraulic_stripe_work_floats": (_sz, [stripe_p, _i]),
+    "nz_hydraulic_stripe": (_i, [ctx_p, dev_ptr, dev_ptr, C.POINTER(dev_ptr), C.POINTER(dev_ptr), dev_ptr, stripe_p, hd_p,
+                                 _i, _i] + _tail),
     "nz_constant_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, _f, _i] + _tail),
     "nz_reduction_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, dev_ptr, _i] + _tail),
     "nz_update_flow_from_track": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, _f, _f, _f, _i] + _tail),

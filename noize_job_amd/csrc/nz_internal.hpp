@@ -330,6 +330,12 @@ enum { NZ_HYD_OPEN = 1, NZ_HYD_MAPS = 2, NZ_HYD_MASKS = 4 };  // the kernel's co
 int32_t nz_launch_hydraulic(hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
                             const nz_hydraulic_params &k, int res, int count, int first, int last,
                             const nz_hydraulic_ex *ex = nullptr);
+// the stripe form: one iteration on rows [g.or0, g.or1) of one stripe-shaped plane set (g: nz_geom_from_stripe with the
+// launch's window as its produced rows); the clamps and the open border are at g's clamp range, the masks are updated on
+// rows [own0, own1) only
+int32_t nz_launch_hydraulic_stripe(hipStream_t s, const float *h_in, float *h_out, const nz_hydraulic_planes &p,
+                                   const nz_hydraulic_params &k, const nz_geom &g, int own0, int own1, int first, int last,
+                                   const nz_hydraulic_ex &ex);
 
 int32_t nz_launch_mesh_planar(hipStream_t s, void *vertices, uint32_t *indices, int res);
 int32_t nz_launch_mesh(hipStream_t s, int meshType, void *vertices, uint32_t *indices, int res, int in_res,

@@ -1162,6 +1162,92 @@ extern "C" int32_t nz_hydraulic_erosion_ex_rw(nz_ctx *ctx, nz_rw_tile *tile, flo
     return hydraulic_rw_impl(ctx, tile, work, desc, dep, out);
 }
 
+// ---- the stripe form (include/noize_hip.h): n iterations of one call on a row stripe, one launch each ----
+constexpr int HYD_STRIPE_RADIUS = 3;  // ghost rows one iteration reads beyond the rows it produces (nz_hydraulic.hip's HR)
+constexpr int HYD_STRIPE_PLANES = 7;  // the height and the six state planes
+
+extern "C" int32_t nz_hydraulic_stripe_halo_rows(int32_t iterations) {
+    return iterations > 0 ? HYD_STRIPE_RADIUS * iterations : 0;
+}
+
+static size_t stripe_plane_floats(const nz_stripe &st) { return (size_t)st.rows * (st.pitch > 0 ? st.pitch : st.cols); }
+
+extern "C" size_t nz_hydraulic_stripe_work_floats(const nz_stripe *st, int32_t iterations) {
+    if (!st || st->rows <= 0 || st->cols <= 0 || st->pitch < 0 || iterations <= 1) return 0;
+    return (size_t)HYD_STRIPE_PLANES * stripe_plane_floats(*st);
+}
+
+extern "C" int32_t nz_hydraulic_stripe(nz_ctx *ctx, const float *height_in, float *height_out, const float *const *state_in,
+                                       float *const *state_out, float *work, const nz_stripe *st,
+                                       const nz_hydraulic_desc *desc, int32_t first, int32_t last, nz_handle dep,
+                                       nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(desc, "desc is NULL");
+    const int n = desc->iterations;
+    NZ_REQUIRE(n >= 1, "iterations %d < 1", n);
+    nz_hydraulic_params k;
+    NZ_TRY(check_hydraulic(n, desc->initialWater, desc->rain, desc->evaporation, desc->capacity, desc->dissolve,
+                           desc->deposit, desc->minTilt, &k));
+    NZ_REQUIRE(desc->border == NZ_HYDRAULIC_BORDER_CLOSED || desc->border == NZ_HYDRAULIC_BORDER_OPEN,
+               "border %d is not a mode", desc->border);
+    NZ_REQUIRE(n <= INT32_MAX / HYD_STRIPE_RADIUS, "iterations %d out of range", n);
+    NZ_TRY(nz_check_stripe(st, HYD_STRIPE_RADIUS * n));
+    NZ_REQUIRE(height_in && height_out, "height_in/height_out is NULL");
+    NZ_REQUIRE(first || state_in, "state_in is NULL");
+    NZ_REQUIRE(state_out, "state_out is NULL");
+    NZ_REQUIRE(n == 1 || work, "work is NULL");
+    for (int i = 0; i < 6; i++) {
+        NZ_REQUIRE(first || state_in[i], "state_in[%d] is NULL", i);
+        // the last launch of a `last` call writes the water only; the launches before it ping-pong through all six
+        NZ_REQUIRE(state_out[i] || (last && n == 1 && i > 0), "state_out[%d] is NULL", i);
+    }
+    // every plane the call writes lies apart from every other plane of the call; planes that are only read may alias
+    const nz_geom g0 = nz_geom_from_stripe(*st);
+    const size_t span = (size_t)(st->rows - 1) * g0.pitch + st->cols, plane = stripe_plane_floats(*st);
+    struct named { const char *name; const float *p; size_t n; };
+    std::vector<named> reads{{"height_in", height_in, span}, {"rainMap", desc->rainMap, span}, {"hardness", desc->hardness, span}};
+    std::vector<named> writes{{"height_out", height_out, span}, {"wear", desc->wear, span}, {"deposits", desc->deposits, span}};
+    if (n > 1) writes.push_back({"work", work, HYD_STRIPE_PLANES * plane});
+    for (int i = 0; i < 6; i++) {
+        if (!first) reads.push_back({"state_in", state_in[i], span});
+        writes.push_back({"state_out", state_out[i], span});
+    }
+    auto overlap = [](const named &a, const named &b) {
+        return a.p && b.p && (uintptr_t)a.p < (uintptr_t)(b.p + b.n) && (uintptr_t)b.p < (uintptr_t)(a.p + a.n);
+    };
+    for (size_t i = 0; i < writes.size(); i++) {
+        for (const auto &r : reads) NZ_REQUIRE(!overlap(writes[i], r), "%s overlaps %s", writes[i].name, r.name);
+        for (size_t j = i + 1; j < writes.size(); j++)
+            NZ_REQUIRE(!overlap(writes[i], writes[j]), "%s overlaps %s", writes[i].name, writes[j].name);
+    }
+    const nz_hydraulic_ex ex{desc->border == NZ_HYDRAULIC_BORDER_OPEN, desc->rainMap, desc->hardness, desc->wear,
+                             desc->deposits};
+    // launch j writes set (n-1-j) & 1: 0 = the caller's output planes, where the last launch lands; 1 = `work`
+    nz_hydraulic_planes sets[2];
+    float *hs[2] = {height_out, work};
+    for (int i = 0; i < 6; i++) {
+        sets[0].in[i] = sets[0].out[i] = state_out[i];
+        sets[1].in[i] = sets[1].out[i] = n > 1 ? work + (size_t)(1 + i) * plane : nullptr;
+    }
+    const int glo = g0.zc0 > -st->grow0 ? g0.zc0 : -st->grow0, ghi = st->grows - st->grow0;  // the global grid in buffer rows
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int j = 0; j < n; j++) {
+        const int to = (n - 1 - j) & 1, widen = HYD_STRIPE_RADIUS * (n - 1 - j);
+        nz_geom g = g0;
+        g.or0 = st->own0 - widen > glo ? st->own0 - widen : glo;
+        g.or1 = st->own1 + widen < ghi ? st->own1 + widen : ghi;
+        nz_hydraulic_planes p;
+        for (int i = 0; i < 6; i++) {
+            p.in[i] = j == 0 ? (first ? nullptr : state_in[i]) : sets[to ^ 1].in[i];
+            p.out[i] = sets[to].out[i];
+        }
+        if (j == n - 1) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_hydraulic_stripe(ctx->stream, j == 0 ? height_in : hs[to ^ 1], hs[to], p, k, g, st->own0, st->own1,
+                                          first && j == 0, last && j == n - 1, ex));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
 // ---------------------------------------------------------------------------------------------
 // mesh
 // ---------------------------------------------------------------------------------------------

@@ -609,6 +609,20 @@ class HydraulicErosionStage : public PipelineStage {
               "nz_hydraulic_erosion_stage");
         jobHandle = done(h);
     }
+    // The stage on one row stripe of a larger grid (nz_hydraulic_stripe): `n` iterations with this stage's scalars and border
+    // in one call.  The planes -- all of the stripe's shape -- are the caller's, and so is the exchange of 3 * n ghost rows
+    // before the call (nz_halo_exchange on heightIn and, unless `first`, the six stateIn planes); a NULL map or mask is an
+    // option left off.
+    JobHandle ScheduleStripe(const float *heightIn, float *heightOut, const float *const *stateIn, float *const *stateOut,
+                             float *stripeWork, const nz_stripe &st, int n, bool first, bool last, const float *rainMapRows,
+                             const float *hardnessRows, float *wearRows, float *depositRows, JobHandle dependency) {
+        const nz_hydraulic_desc desc{n, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt, (int32_t)border,
+                                     rainMapRows, hardnessRows, wearRows, depositRows};
+        nz_handle h = 0;
+        check(nz_hydraulic_stripe(ctx, heightIn, heightOut, stateIn, stateOut, stripeWork, &st, &desc, first, last,
+                                  dependency.id, &h), "nz_hydraulic_stripe");
+        return done(h);
+    }
     const float *water() const { return work ? work->ptr : nullptr; }
     size_t waterLength() const { return (size_t)count * resolution * resolution; }
     const float *wear() const { return masks ? masks->ptr : nullptr; }  // recordMasks: waterLength() floats each

@@ -238,6 +238,20 @@ def run_pipeline(ops, comm, plan, p, bufs, on_stage=None):
     return result[0]
 
 
+def _copy_ghost_rows(reqs, plans, copy_rows):
+    """One exchange of a lockstep rehearsal: every rank's request (planes, up_rows, down_rows) served by direct copies
+    from its neighbours' planes."""
+    for r, (planes, up_rows, down_rows) in enumerate(reqs):
+        pl = plans[r]
+        for i, t in enumerate(planes):
+            if up_rows > 0 and pl.up is not None:
+                q = plans[pl.up]
+                copy_rows(t, pl.own0 - up_rows, reqs[pl.up][0][i], q.own1 - up_rows, up_rows)
+            if down_rows > 0 and pl.down is not None:
+                q = plans[pl.down]
+                copy_rows(t, pl.own1, reqs[pl.down][0][i], q.own0, down_rows)
+
+
 def run_pipeline_lockstep(ops_list, plans, p, bufs_list, copy_rows):
     """All ranks of a grid inside ONE process (tests, single-GPU rehearsal): the per-rank generators
     advance in lockstep and ghost rows are copied directly, copy_rows(dst_plane, d0, src_plane, s0, n)."""
@@ -253,16 +267,91 @@ def run_pipeline_lockstep(ops_list, plans, p, bufs_list, copy_rows):
         if all(r is None for r in reqs):
             break
         assert all(r is not None for r in reqs), "ranks left the schedule at different points"
-        for r, (planes, up_rows, down_rows) in enumerate(reqs):
-            pl = plans[r]
-            for i, t in enumerate(planes):
-                if up_rows > 0 and pl.up is not None:
-                    q = plans[pl.up]
-                    copy_rows(t, pl.own0 - up_rows, reqs[pl.up][0][i], q.own1 - up_rows, up_rows)
-                if down_rows > 0 and pl.down is not None:
-                    q = plans[pl.down]
-                    copy_rows(t, pl.own1, reqs[pl.down][0][i], q.own0, down_rows)
+        _copy_ghost_rows(reqs, plans, copy_rows)
     return [r[0] for r in results]
+
+
+# ---- grid hydraulic erosion on row stripes (nz_hydraulic_stripe) ---------------------------------------------------------
+HYDRAULIC_STATE = 6  # d, s, fN, fS, fE, fW: state buffers are [6, rows, cols]
+HYDRAULIC_SCALARS = ("initialWater", "rain", "evaporation", "capacity", "dissolve", "deposit", "minTilt")
+HYDRAULIC_DEFAULTS = dict(iterations=200, initialWater=1e-4, rain=1e-4, evaporation=0.01, capacity=1.0, dissolve=0.3,
+                          deposit=0.3, minTilt=0.01, border=N.NZ_HYDRAULIC_BORDER_CLOSED)
+HYDRAULIC_PLANES = ("rainMap", "hardness", "wear", "deposits")
+
+
+def hydraulic_halo_rows(k):
+    """Ghost rows on each side that k iterations without an exchange read beyond the owned rows: heights and water at
+    radius 3 per iteration."""
+    return 3 * k
+
+
+def hydraulic_params(params=None, **kw):
+    """The scalar fields of nz_hydraulic_desc (and `border`) from a dict and / or keyword arguments, the hosts' stage
+    defaults for the rest.  The four planes of the desc are per-rank buffers and travel in `bufs`."""
+    prm = dict(HYDRAULIC_DEFAULTS)
+    for src in (params or {}, kw):
+        for name, v in src.items():
+            assert name in prm, "%s is not a scalar field of nz_hydraulic_desc" % name
+            prm[name] = v
+    return prm
+
+
+def hydraulic_steps(ops, plan, params, bufs, exchange_every=1):
+    """Grid hydraulic erosion on one rank's stripe as a generator in the style of pipeline_steps: the iterations run in
+    blocks of at most `exchange_every` (split_iterations), every block one ops.hydraulic call that recomputes the ghost
+    rows its later iterations need, and before every block it yields (planes, up_rows, down_rows) for the exchange:
+      before the first block   the height plane, and the rain and hardness maps when given, 3 * n rows of block n
+      before each later block  the height plane and the six state planes, 3 * n rows
+    bufs: dict with the height planes "A" (holds the input on its owned rows) and "B", the state buffers "S0" and "S1"
+    ([6, rows, cols]), "work" ([7, rows, cols]; needed when exchange_every > 1) and, optionally, the planes "rainMap",
+    "hardness" (owned rows filled), "wear", "deposits"; every plane has plan.rows rows with plan.halo >= 3 * exchange_every.
+    Returns (height plane, water plane) whose owned rows hold the result."""
+    prm = hydraulic_params(params)
+    blocks = split_iterations(prm["iterations"], exchange_every)
+    planes = {k: bufs.get(k) for k in HYDRAULIC_PLANES}
+    cur, nxt = bufs["A"], bufs["B"]
+    s_cur, s_nxt = bufs["S0"], bufs["S1"]
+    for i, n in enumerate(blocks):
+        first, last = i == 0, i == len(blocks) - 1
+        rows = hydraulic_halo_rows(n)
+        if first:
+            yield [cur] + [planes[k] for k in ("rainMap", "hardness") if planes[k] is not None], rows, rows
+        else:
+            yield [cur] + [s_cur[j] for j in range(HYDRAULIC_STATE)], rows, rows
+        ops.hydraulic(cur, nxt, None if first else s_cur, s_nxt, bufs.get("work"), plan, prm, n, first, last, **planes)
+        cur, nxt = nxt, cur
+        s_cur, s_nxt = s_nxt, s_cur
+    return cur, s_cur[0]
+
+
+def run_hydraulic(ops, comm, plan, params, bufs, exchange_every=1):
+    """hydraulic_steps on this rank, every exchange completed before the block that reads it (TorchComm, NativeComm,
+    NoComm); returns (height plane, water plane)."""
+    gen = hydraulic_steps(ops, plan, params, bufs, exchange_every)
+    try:
+        while True:
+            planes, up_rows, down_rows = next(gen)
+            comm.exchange(planes, plan, up_rows, down_rows)
+    except StopIteration as done:
+        return done.value
+
+
+def run_hydraulic_lockstep(ops_list, plans, params, bufs_list, copy_rows, exchange_every=1):
+    """All ranks inside one process, as run_pipeline_lockstep; returns every rank's (height plane, water plane)."""
+    gens = [hydraulic_steps(o, pl, params, b, exchange_every) for o, pl, b in zip(ops_list, plans, bufs_list)]
+    results = [None] * len(gens)
+    while True:
+        reqs = []
+        for r, g in enumerate(gens):
+            try:
+                reqs.append(next(g))
+            except StopIteration as done:
+                results[r] = done.value
+                reqs.append(None)
+        if all(r is None for r in reqs):
+            return results
+        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
+        _copy_ghost_rows(reqs, plans, copy_rows)
 
 
 class HipStripeOps:
@@ -309,6 +398,19 @@ class HipStripeOps:
         self._call("nz_flow_fused_stripe", h.data_ptr(), pin, pout, dst.data_ptr(), C.byref(st), n, int(first),
                    int(last), normMin, normMax)
 
+
+    def hydraulic(self, h_in, h_out, S_in, S_out, work, plan, prm, n, first, last, rainMap=None, hardness=None, wear=None,
+                  deposits=None, pitch=0):
+        """nz_hydraulic_stripe: n iterations of `prm` (hydraulic_params) in one call.  S_in may be None with `first`."""
+        st = plan.stripe(pitch)
+        arr = N.dev_ptr * HYDRAULIC_STATE
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        pin = arr(*[S_in[i].data_ptr() for i in range(HYDRAULIC_STATE)]) if S_in is not None else None
+        pout = arr(*[ptr(S_out[i]) for i in range(HYDRAULIC_STATE)])
+        desc = N.HydraulicDesc(n, *[prm[k] for k in HYDRAULIC_SCALARS], prm["border"], ptr(rainMap), ptr(hardness),
+                               ptr(wear), ptr(deposits))
+        self._call("nz_hydraulic_stripe", h_in.data_ptr(), h_out.data_ptr(), pin, pout, ptr(work), C.byref(st),
+                   C.byref(desc), int(first), int(last))
 
     def map_range(self, buf, n, res, lim_min=float("inf"), lim_max=float("-inf")):
         """GetMapRangeJob over the first n floats of `buf` into the 3-float device buffer `res`."""
