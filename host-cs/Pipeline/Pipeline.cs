@@ -30,6 +30,7 @@ namespace xshazwar.noize.hip {
     // one at a time cannot fill 256 CUs.)
     public class GeneratorDataBatch : GeneratorData {
         public DeviceTile positions;
+        public int[] hostPositions;              // the same pairs on the host (optional): for a stage that rescales them
         public int count = 1;
 
         public static GeneratorDataBatch Create(GpuContext ctx, string uuid, int resolution, int[] positionsXZ) {
@@ -37,6 +38,7 @@ namespace xshazwar.noize.hip {
             GeneratorDataBatch b = new GeneratorDataBatch { uuid = uuid, resolution = resolution, count = n,
                                                             data = ctx.Alloc(n * resolution * resolution), positions = ctx.Alloc(2 * n) };
             b.positions.CopyFrom(positionsXZ);
+            b.hostPositions = (int[]) positionsXZ.Clone();
             return b;
         }
         public DeviceTile tile(int k) => data.Offset(k * resolution * resolution, resolution * resolution);

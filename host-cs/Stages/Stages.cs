@@ -383,6 +383,89 @@ namespace xshazwar.noize.hip {
         }
     }
 
+    // ---- upsample / downsample (new-framework; include/noize_hip.h): resolution R -> R * factor / R / factor.  The stage owns
+    //      its output plane, resized when the input size changes, and hands downstream a GeneratorData(Batch) of the new
+    //      resolution whose plane it is (ReduceStage.TransformData is the model); xpos / zpos scale with the resolution ----
+    public enum ResampleFilter { Nearest = 0, Bilinear = 1, CatmullRom = 2 }                        // enum nz_resample_filter
+
+    public abstract class ResampleStage : PipelineStage {
+        public int factor = 2;
+        public DeviceTile output;
+        DeviceTile outPositions;
+        int[] outHostPositions;
+        protected ResampleStage(GpuContext ctx) : base(ctx) {}
+        protected abstract int OutLength(int size);
+        protected abstract int OutPosition(int v);
+        public override void ResizeNativeContainers(int size) {
+            output?.Dispose();
+            output = ctx.Alloc(OutLength(size));
+        }
+        public override void TransformData(PipelineWorkItem inputData) {
+            GeneratorData d = (GeneratorData) inputData.data;
+            int res = OutPosition(d.resolution);                                                     // a resolution scales as a position does
+            if (d is GeneratorDataBatch b) {
+                // rescaled on the host from the payload's host copy: no wait on the device in the scheduling path, one upload
+                // per new set of positions.  A payload without a host copy is read back once
+                int[] pos;
+                if (b.hostPositions != null) {
+                    pos = (int[]) b.hostPositions.Clone();
+                } else {
+                    float[] raw = b.positions.ToArray();                                             // int32 pairs, four-byte elements
+                    pos = new int[raw.Length];
+                    Buffer.BlockCopy(raw, 0, pos, 0, 4 * raw.Length);
+                }
+                for (int i = 0; i < pos.Length; i++) pos[i] = OutPosition(pos[i]);
+                if (outPositions == null || outHostPositions == null || !System.Linq.Enumerable.SequenceEqual(pos, outHostPositions)) {
+                    outPositions?.Dispose();
+                    outPositions = ctx.Alloc(pos.Length);
+                    outPositions.CopyFrom(pos);
+                    outHostPositions = pos;
+                }
+                inputData.data = new GeneratorDataBatch { uuid = d.uuid, data = output, resolution = res, positions = outPositions, hostPositions = pos, count = b.count };
+            } else {
+                inputData.data = new GeneratorData { uuid = d.uuid, data = output, resolution = res, xpos = OutPosition(d.xpos), zpos = OutPosition(d.zpos) };
+            }
+        }
+        public override void OnDestroy() { output?.Dispose(); output = null; outPositions?.Dispose(); outPositions = null; outHostPositions = null; }
+    }
+
+    public class UpsampleStage : ResampleStage {
+        public ResampleFilter filter = ResampleFilter.CatmullRom;
+        public DeviceTile baseData;   // optional, of the OUTPUT's size: added to the upsampled plane (detail transfer)
+        public UpsampleStage(GpuContext ctx) : base(ctx) {}
+        protected override int OutLength(int size) => size * factor * factor;
+        protected override int OutPosition(int v) => v * factor;
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            IntPtr b = baseData != null ? baseData.Ptr : IntPtr.Zero;
+            ulong h;
+            if (d is GeneratorDataBatch gb) {
+                Native.Check(Native.nz_upsample_batch(ctx.Handle, d.data.Ptr, d.resolution, output.Ptr, factor, (int) filter, b, gb.count, dependency.id, out h), "nz_upsample_batch");
+            } else {
+                Native.Check(Native.nz_upsample(ctx.Handle, d.data.Ptr, d.resolution, output.Ptr, factor, (int) filter, b, dependency.id, out h), "nz_upsample");
+            }
+            jobHandle = Done(h);
+        }
+    }
+
+    public class DownsampleStage : ResampleStage {
+        public DownsampleStage(GpuContext ctx) : base(ctx) {}
+        protected override int OutLength(int size) => size / (factor * factor);
+        protected override int OutPosition(int v) => v >= 0 ? v / factor : -((-v + factor - 1) / factor);   // floor
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            ulong h;
+            if (d is GeneratorDataBatch gb) {
+                Native.Check(Native.nz_downsample_batch(ctx.Handle, d.data.Ptr, d.resolution, output.Ptr, factor, gb.count, dependency.id, out h), "nz_downsample_batch");
+            } else {
+                Native.Check(Native.nz_downsample(ctx.Handle, d.data.Ptr, d.resolution, output.Ptr, factor, dependency.id, out h), "nz_downsample");
+            }
+            jobHandle = Done(h);
+        }
+    }
+
     public class CurveStage : TmpStage {
         public Func<float, float> unityCurve = t => t;   // stands in for UnityEngine.AnimationCurve.Evaluate
         public int samples = 256;

@@ -673,6 +673,61 @@ int32_t nz_debug_chain_delay(int32_t item, int32_t sleeps);
  * default (2^21: seconds).  With a small limit and a long nz_debug_chain_delay the time-out path can be exercised. */
 int32_t nz_debug_chain_poll_limit(int32_t polls);
 
+/* ---- upsample and downsample: coarse-to-fine terrain (new-framework feature) ------------------------------------------
+ * The two changes of resolution the stage list lacks: erode a reduced copy of a tile, carry the change back up and add it
+ * to the full-size detail (nz_downsample, nz_hydraulic_erosion_stage, nz_reduction_job SUBTRACT, nz_upsample with `base`).
+ *
+ * THE MODEL (tests/resample_ref.py restates it in numpy; the kernels, nz_resample.hip, follow it bit for bit):
+ *   - float32 arithmetic in the order given, no contraction; identical in every float mode (nz_ctx_set_float_mode does not
+ *     apply).  Factor f in {2, 4, 8}; R = the source resolution.
+ *   - samples are cell-centred: fine cell j = i f + p (0 <= p < f) lies at coarse coordinate i + (2p+1)/(2f) - 1/2.
+ *   UPSAMPLE, R^2 -> (R f)^2, separable.  The X pass runs on every source row needed and each result is rounded to float32;
+ *   the Z pass runs over those row results with the weights of the row's phase.  Per axis:
+ *       p <  f/2:  i0 = i - 1,  t = (2p+1)/(2f) + 1/2
+ *       p >= f/2:  i0 = i,      t = (2p+1)/(2f) - 1/2
+ *     source indices clamp to [0, R-1] (clamp to edge, as everywhere else).
+ *       NZ_RESAMPLE_NEAREST      the value at i, copied with its bits
+ *       NZ_RESAMPLE_BILINEAR     taps i0, i0+1, weights 1-t, t
+ *       NZ_RESAMPLE_CATMULL_ROM  taps i0-1 .. i0+2, weights (-t^3+2t^2-t)/2, (3t^3-5t^2+2)/2, (-3t^3+4t^2+t)/2, (t^3-t^2)/2
+ *     a tap sum is s = +0; s += v w in ascending tap order.  Every weight at these phases is a dyadic rational, exact in
+ *     float32, and each tap set sums to exactly 1 (f = 2: -3/128, 29/128, 111/128, -9/128): the weights are compile-time
+ *     constants per phase.  Seeded with +0, a sum never returns -0; NEAREST does.
+ *     `base` (optional, fine-sized): out = base[c] + s, one add -- the detail-transfer form.  base may be dst itself (in
+ *     place) or lie apart from dst.
+ *   DOWNSAMPLE, R^2 -> (R/f)^2, f | R: the mean of the f x f block.  Per block row r = ((v0 + v1) + v2) + ... left to right,
+ *     then m = ((r0 + r1) + r2) + ... top to bottom, then m (1/f^2), an exact power of two.
+ *   - a NaN produced by this arithmetic (a tap sum, the base add, the mean) is stored as the canonical quiet NaN
+ *     0x7FC00000: sign and payload of an arithmetic NaN differ between processors, and the model is one set of bits.
+ *     NEAREST without base moves bits and keeps whatever NaN it is given.
+ *   - each tile of a batch clamps at its own border; a stripe clamps at the global border only.
+ *
+ * Refused with NZ_ERR_INVALID, the argument named and nothing written: a factor outside {2, 4, 8}, an unknown filter, a
+ * resolution < 1, for downsample a resolution the factor does not divide, an output of 2^31 cells or more, NULL planes,
+ * dst overlapping src, base partly overlapping dst, mismatched stripe geometry.
+ *
+ * _batch: `count` tiles stored back to back in src, dst and base, like every _batch entry.
+ * _stripe: srcSt describes the source buffer, dstSt the output buffer; the fine stripe's cols and grows are f times the
+ *   coarse stripe's (the grid may be non-square), pitch is honoured on both and pad floats are not written; only the owned
+ *   rows of dstSt are written.  Upsampling the owned fine global rows [g0, g1) reads the coarse global rows
+ *   floor(g0/f) - halo .. floor((g1-1)/f) + halo clipped to the grid, halo = nz_upsample_stripe_halo_rows(filter) = 0
+ *   nearest, 1 bilinear, 2 Catmull-Rom; downsampling output rows [g0, g1) reads fine rows [f g0, f g1).  A row that is not
+ *   in the source buffer means NZ_ERR_INVALID.  `base` has dstSt's shape.  The owned rows of any split equal the
+ *   monolithic result bit for bit. */
+enum nz_resample_filter { NZ_RESAMPLE_NEAREST = 0, NZ_RESAMPLE_BILINEAR = 1, NZ_RESAMPLE_CATMULL_ROM = 2 };
+int32_t nz_upsample(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor, int32_t filter,
+                    const float *base /* NULL */, nz_handle dep, nz_handle *out);
+int32_t nz_upsample_batch(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor, int32_t filter,
+                          const float *base /* NULL */, int32_t count, nz_handle dep, nz_handle *out);
+int32_t nz_downsample(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor, nz_handle dep,
+                      nz_handle *out);
+int32_t nz_downsample_batch(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor, int32_t count,
+                            nz_handle dep, nz_handle *out);
+int32_t nz_upsample_stripe_halo_rows(int32_t filter);
+int32_t nz_upsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst, const nz_stripe *dstSt,
+                           int32_t factor, int32_t filter, const float *base /* NULL */, nz_handle dep, nz_handle *out);
+int32_t nz_downsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst, const nz_stripe *dstSt,
+                             int32_t factor, nz_handle dep, nz_handle *out);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

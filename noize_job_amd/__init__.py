@@ -7,11 +7,11 @@ it is missing: there is no CPU or PyTorch fallback in the product path.
 from . import _native
 from ._native import NoizeError, Stripe
 from .runtime import Context, DeviceTile, JobHandle
-from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DownsampleData, ErosionStage, FlowMapStage, FractalNoise, FractalShape, GaussSigma,
+from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DownsampleData, DownsampleStage, ErosionStage, FlowMapStage, FractalNoise, FractalShape, GaussSigma,
                        GeneratorData, GeneratorDataBatch, HydraulicBorder, HydraulicErosionStage, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
-                       ReducePipeline, ReduceStage, ShapedNoiseStage, Upstream, WarpedNoiseStage,
-                       ReductionType, StageGaussianBlur, StageThermalErosion,
+                       ReducePipeline, ReduceStage, ShapedNoiseStage, UpsampleStage, Upstream, WarpedNoiseStage,
+                       ReductionType, ResampleFilter, StageGaussianBlur, StageThermalErosion,
                        StageIO, StageSmoothBlur)
 
 from .pipeline_state import (HandleLock, MeshTileReferenceDataStage, PipelineStateManager, ReadGeneratorContextStage,

@@ -89,6 +89,7 @@ NZ_COMM_ID_BYTES = 128
 NZ_HALO_RECOMPUTE, NZ_HALO_EXCHANGE, NZ_HALO_EXCHANGE_ONCE = 0, 1, 2
 NZ_FLOAT_STRICT, NZ_FLOAT_FAST, NZ_FLOAT_RELAXED = 0, 1, 2
 NZ_HYDRAULIC_BORDER_CLOSED, NZ_HYDRAULIC_BORDER_OPEN = 0, 1
+NZ_RESAMPLE_NEAREST, NZ_RESAMPLE_BILINEAR, NZ_RESAMPLE_CATMULL_ROM = 0, 1, 2
 
 _i, _f, _sz = C.c_int32, C.c_float, C.c_size_t
 _tail = [handle_t, handle_p]  # (dep, out)
@@ -170,6 +171,13 @@ SIGNATURES = {
     "nz_hydraulic_stripe_work_floats": (_sz, [stripe_p, _i]),
     "nz_hydraulic_stripe": (_i, [ctx_p, dev_ptr, dev_ptr, C.POINTER(dev_ptr), C.POINTER(dev_ptr), dev_ptr, stripe_p, hd_p,
                                  _i, _i] + _tail),
+    "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
+    "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
+    "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),
+    "nz_downsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i] + _tail),
+    "nz_upsample_stripe_halo_rows": (_i, [_i]),
+    "nz_upsample_stripe": (_i, [ctx_p, dev_ptr, stripe_p, dev_ptr, stripe_p, _i, _i, dev_ptr] + _tail),
+    "nz_downsample_stripe": (_i, [ctx_p, dev_ptr, stripe_p, dev_ptr, stripe_p, _i] + _tail),
     "nz_constant_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, _f, _i] + _tail),
     "nz_reduction_job": (_i, [ctx_p, _i, dev_ptr, dev_ptr, dev_ptr, _i] + _tail),
     "nz_update_flow_from_track": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, _f, _f, _f, _i] + _tail),

@@ -337,6 +337,30 @@ int32_t nz_launch_hydraulic_stripe(hipStream_t s, const float *h_in, float *h_ou
                                    const nz_hydraulic_params &k, const nz_geom &g, int own0, int own1, int first, int last,
                                    const nz_hydraulic_ex &ex);
 
+// resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
+// one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
+struct nz_up_geom {
+    int ccols, cpitch, crows;  // the coarse buffer
+    int cgrow0, cgrows;        // its first global row, the coarse grid's rows (the clamp range of row reads)
+    int fcols, fpitch;         // the fine buffer
+    int fgrow0;                // its first global row
+    int w0, w1;                // fine buffer rows to produce [w0, w1)
+    size_t cstride, fstride;   // floats between the planes of a batch
+    int cz_first, cz_last;     // (set by the launcher) global coarse rows of the window
+    int rd0, rd1;              // (set by the launcher) coarse buffer rows the window's taps read, inclusive
+};
+struct nz_down_geom {
+    int ccols, cpitch, cgrow0;  // the coarse (output) buffer
+    int fpitch, fgrow0;         // the fine (input) buffer
+    int w0, w1;                 // coarse buffer rows to produce [w0, w1)
+    size_t cstride, fstride;
+};
+int nz_resample_halo(int filter);  // coarse rows an upsampled row reads beyond its own: 0 nearest, 1 bilinear, 2 Catmull-Rom
+// base: NULL, dst itself or a plane apart from dst.  NZ_ERR_INVALID when a coarse row the window reads is not in the buffer
+int32_t nz_launch_upsample(hipStream_t s, const float *src, float *dst, const float *base, nz_up_geom g, int factor,
+                           int filter, int count);
+int32_t nz_launch_downsample(hipStream_t s, const float *src, float *dst, const nz_down_geom &g, int factor, int count);
+
 int32_t nz_launch_mesh_planar(hipStream_t s, void *vertices, uint32_t *indices, int res);
 int32_t nz_launch_mesh(hipStream_t s, int meshType, void *vertices, uint32_t *indices, int res, int in_res,
                        float tile_height, float tile_size, const float *heights, int count = 1, int index16 = 0);

@@ -1249,6 +1249,170 @@ extern "C" int32_t nz_hydraulic_stripe(nz_ctx *ctx, const float *height_in, floa
 }
 
 // ---------------------------------------------------------------------------------------------
+// upsample / downsample (new-framework feature, include/noize_hip.h, nz_resample.hip)
+// ---------------------------------------------------------------------------------------------
+static bool planes_overlap(const float *a, size_t na, const float *b, size_t nb) {
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
+
+static int32_t check_resample(int32_t factor, int32_t filter) {
+    NZ_REQUIRE(factor == 2 || factor == 4 || factor == 8, "factor %d is not 2, 4 or 8", factor);
+    NZ_REQUIRE(filter >= NZ_RESAMPLE_NEAREST && filter <= NZ_RESAMPLE_CATMULL_ROM, "filter %d is not a resample filter",
+               filter);
+    return NZ_OK;
+}
+
+// the planes of a call: src read, dst written (fine_n / coarse_n floats each way round), base NULL, dst or apart from dst
+static int32_t check_resample_planes(const float *src, size_t src_n, const float *dst, size_t dst_n, const float *base) {
+    NZ_REQUIRE(src, "src is NULL");
+    NZ_REQUIRE(dst, "dst is NULL");
+    NZ_REQUIRE(dst_n < ((size_t)1 << 31), "dst: an output of %zu cells (2^31 or more)", dst_n);
+    NZ_REQUIRE(!planes_overlap(dst, dst_n, src, src_n), "dst overlaps src");
+    NZ_REQUIRE(!base || base == dst || !planes_overlap(dst, dst_n, base, dst_n), "base partly overlaps dst");
+    return NZ_OK;
+}
+
+static int32_t upsample_impl(nz_ctx *ctx, const float *src, int32_t res, float *dst, int32_t factor, int32_t filter,
+                             const float *base, int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, filter));
+    NZ_REQUIRE(res >= 1, "srcResolution %d < 1", res);
+    NZ_REQUIRE(count >= 1 && count <= 65535, "count %d out of range [1,65535]", count);
+    // 46340^2 < 2^31 <= 46341^2: bounding the side first keeps every product below from wrapping
+    NZ_REQUIRE(res <= 46340 / factor, "dst: an output of 2^31 cells or more (srcResolution %d x factor %d)", res, factor);
+    const size_t fine = (size_t)res * factor;
+    NZ_TRY(check_resample_planes(src, (size_t)count * res * res, dst, (size_t)count * fine * fine, base));
+    nz_up_geom g{};
+    g.ccols = g.cpitch = g.crows = g.cgrows = res;
+    g.fcols = g.fpitch = g.w1 = (int)fine;
+    g.cstride = (size_t)res * res;
+    g.fstride = fine * fine;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_upsample(ctx->stream, src, dst, base, g, factor, filter, count));
+    return nz_ctx_finish(ctx, out);
+}
+
+static int32_t downsample_impl(nz_ctx *ctx, const float *src, int32_t res, float *dst, int32_t factor, int32_t count,
+                               nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, NZ_RESAMPLE_NEAREST));
+    NZ_REQUIRE(res >= 1, "srcResolution %d < 1", res);
+    NZ_REQUIRE(res % factor == 0, "srcResolution %d is not divisible by factor %d", res, factor);
+    NZ_REQUIRE(count >= 1 && count <= 65535, "count %d out of range [1,65535]", count);
+    const size_t coarse = (size_t)(res / factor);
+    NZ_REQUIRE(res <= 46340 && (size_t)count * res * res < ((size_t)1 << 31), "src: an input of 2^31 cells or more");
+    NZ_TRY(check_resample_planes(src, (size_t)count * res * res, dst, (size_t)count * coarse * coarse, nullptr));
+    nz_down_geom g{};
+    g.ccols = g.cpitch = g.w1 = (int)coarse;
+    g.fpitch = res;
+    g.cstride = coarse * coarse;
+    g.fstride = (size_t)res * res;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_downsample(ctx->stream, src, dst, g, factor, count));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_upsample(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                               int32_t filter, const float *base, nz_handle dep, nz_handle *out) {
+    return upsample_impl(ctx, src, srcResolution, dst, factor, filter, base, 1, dep, out);
+}
+
+extern "C" int32_t nz_upsample_batch(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                                     int32_t filter, const float *base, int32_t count, nz_handle dep, nz_handle *out) {
+    return upsample_impl(ctx, src, srcResolution, dst, factor, filter, base, count, dep, out);
+}
+
+extern "C" int32_t nz_downsample(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                                 nz_handle dep, nz_handle *out) {
+    return downsample_impl(ctx, src, srcResolution, dst, factor, 1, dep, out);
+}
+
+extern "C" int32_t nz_downsample_batch(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                                       int32_t count, nz_handle dep, nz_handle *out) {
+    return downsample_impl(ctx, src, srcResolution, dst, factor, count, dep, out);
+}
+
+extern "C" int32_t nz_upsample_stripe_halo_rows(int32_t filter) {
+    return filter >= NZ_RESAMPLE_NEAREST && filter <= NZ_RESAMPLE_CATMULL_ROM ? nz_resample_halo(filter) : 0;
+}
+
+// the two stripes of a resampling call: each a valid stripe of its own grid (no ghost rows demanded of the output), the
+// fine grid f times the coarse one
+static int32_t check_resample_stripes(const nz_stripe *coarse, const char *cname, const nz_stripe *fine, const char *fname,
+                                      int factor) {
+    NZ_REQUIRE(coarse, "%s is NULL", cname);
+    NZ_REQUIRE(fine, "%s is NULL", fname);
+    NZ_TRY(nz_check_stripe(coarse, 0));
+    NZ_TRY(nz_check_stripe(fine, 0));
+    NZ_REQUIRE((int64_t)coarse->cols * factor == fine->cols && (int64_t)coarse->grows * factor == fine->grows,
+               "%s / %s: the fine grid %d x %d is not %d times the coarse grid %d x %d", cname, fname, fine->grows,
+               fine->cols, factor, coarse->grows, coarse->cols);
+    return NZ_OK;
+}
+
+static size_t stripe_span(const nz_stripe &st) { return (size_t)(st.rows - 1) * (st.pitch > 0 ? st.pitch : st.cols) + st.cols; }
+
+extern "C" int32_t nz_upsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst,
+                                      const nz_stripe *dstSt, int32_t factor, int32_t filter, const float *base,
+                                      nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, filter));
+    NZ_TRY(check_resample_stripes(srcSt, "srcSt", dstSt, "dstSt", factor));
+    NZ_REQUIRE(src, "src is NULL");
+    NZ_REQUIRE(dst, "dst is NULL");
+    NZ_REQUIRE(stripe_plane_floats(*dstSt) < ((size_t)1 << 31), "dst: an output of 2^31 cells or more");
+    NZ_REQUIRE(!planes_overlap(dst, stripe_span(*dstSt), src, stripe_span(*srcSt)), "dst overlaps src");
+    NZ_REQUIRE(!base || base == dst || !planes_overlap(dst, stripe_span(*dstSt), base, stripe_span(*dstSt)),
+               "base partly overlaps dst");
+    nz_up_geom g{};
+    g.ccols = srcSt->cols;
+    g.cpitch = srcSt->pitch > 0 ? srcSt->pitch : srcSt->cols;
+    g.crows = srcSt->rows;
+    g.cgrow0 = srcSt->grow0;
+    g.cgrows = srcSt->grows;
+    g.fcols = dstSt->cols;
+    g.fpitch = dstSt->pitch > 0 ? dstSt->pitch : dstSt->cols;
+    g.fgrow0 = dstSt->grow0;
+    g.w0 = dstSt->own0;
+    g.w1 = dstSt->own1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_upsample(ctx->stream, src, dst, base, g, factor, filter, 1));  // refuses a missing ghost row
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_downsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst,
+                                        const nz_stripe *dstSt, int32_t factor, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, NZ_RESAMPLE_NEAREST));
+    NZ_TRY(check_resample_stripes(dstSt, "dstSt", srcSt, "srcSt", factor));
+    NZ_REQUIRE(src, "src is NULL");
+    NZ_REQUIRE(dst, "dst is NULL");
+    NZ_REQUIRE(stripe_plane_floats(*srcSt) < ((size_t)1 << 31), "src: an input of 2^31 cells or more");
+    NZ_REQUIRE(!planes_overlap(dst, stripe_span(*dstSt), src, stripe_span(*srcSt)), "dst overlaps src");
+    // output global rows [g0, g1) read fine global rows [f g0, f g1): all of them in the source buffer
+    const int64_t f0 = (int64_t)(dstSt->own0 + dstSt->grow0) * factor - srcSt->grow0;
+    const int64_t f1 = (int64_t)(dstSt->own1 + dstSt->grow0) * factor - srcSt->grow0;
+    NZ_REQUIRE(dstSt->own1 == dstSt->own0 || (f0 >= 0 && f1 <= srcSt->rows),
+               "srcSt: fine rows [%lld, %lld) of the buffer are required, it holds %d", (long long)f0, (long long)f1,
+               srcSt->rows);
+    nz_down_geom g{};
+    g.ccols = dstSt->cols;
+    g.cpitch = dstSt->pitch > 0 ? dstSt->pitch : dstSt->cols;
+    g.cgrow0 = dstSt->grow0;
+    g.fpitch = srcSt->pitch > 0 ? srcSt->pitch : srcSt->cols;
+    g.fgrow0 = srcSt->grow0;
+    g.w0 = dstSt->own0;
+    g.w1 = dstSt->own1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_downsample(ctx->stream, src, dst, g, factor, 1));
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
 // mesh
 // ---------------------------------------------------------------------------------------------
 extern "C" size_t nz_mesh_vertex_count(int32_t resolution) {  // VertexCount, Overshoot :26

@@ -105,6 +105,7 @@ inline void rw_adopt(GeneratorData *d, const nz_rw_tile &t) {
 struct GeneratorDataBatch : GeneratorData {
     int count = 1;
     const int32_t *positions = nullptr;
+    std::vector<int32_t> hostPositions;  // the same pairs on the host (optional): for a stage that rescales them
 };
 
 inline int tile_count(GeneratorData *d) {
@@ -454,6 +455,107 @@ class ReduceStage : public TmpStage {
 
   private:
     GeneratorData out;
+};
+
+// ---- upsample / downsample (new-framework; include/noize_hip.h): resolution R -> R * factor / R / factor.  The stage owns
+//      its output plane, resized when the input size changes, and hands downstream a GeneratorData(Batch) of the new
+//      resolution whose plane it is (ReduceStage::TransformData is the model); xpos / zpos scale with the resolution ----
+enum class ResampleFilter { Nearest, Bilinear, CatmullRom };
+
+class ResampleStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    int factor = 2;
+    DeviceTile *output() { return out_tile.get(); }
+    void ResizeNativeContainers(size_t n) override { out_tile.reset(new DeviceTile(ctx, out_length(n))); }
+    void TransformData(PipelineWorkItem &inputData) override {
+        auto *d = static_cast<GeneratorData *>(inputData.data);
+        GeneratorData *o = &out;
+        if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            // rescaled on the host from the payload's host copy: no wait on the device in the scheduling path, one upload
+            // per new set of positions.  A payload without a host copy is read back once
+            std::vector<int32_t> pos = b->hostPositions;
+            if (pos.size() != 2 * (size_t)b->count) {
+                pos.resize(2 * (size_t)b->count);
+                check(nz_tile_download(ctx, reinterpret_cast<float *>(const_cast<int32_t *>(b->positions)),
+                                       reinterpret_cast<float *>(pos.data()), pos.size(), 0, nullptr), "nz_tile_download");
+                check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+            }
+            for (auto &v : pos) v = out_position(v);
+            if (!out_positions || pos != out_batch.hostPositions) {
+                out_positions.reset(new DeviceTile(ctx, pos.size()));
+                out_positions->CopyFrom(reinterpret_cast<const float *>(pos.data()));
+                out_batch.hostPositions = pos;
+            }
+            out_batch.count = b->count;
+            out_batch.positions = reinterpret_cast<const int32_t *>(out_positions->ptr);
+            o = &out_batch;
+        } else {
+            o->xpos = out_position(d->xpos);
+            o->zpos = out_position(d->zpos);
+        }
+        o->uuid = d->uuid;
+        o->data = out_tile.get();
+        o->resolution = out_position(d->resolution);  // a resolution scales as a position does
+        inputData.data = o;
+    }
+    void OnDestroy() override {
+        out_tile.reset();
+        out_positions.reset();
+    }
+
+  protected:
+    virtual size_t out_length(size_t n) const = 0;
+    virtual int out_position(int v) const = 0;
+    std::unique_ptr<DeviceTile> out_tile, out_positions;
+
+  private:
+    GeneratorData out;
+    GeneratorDataBatch out_batch;
+};
+
+class UpsampleStage : public ResampleStage {
+  public:
+    using ResampleStage::ResampleStage;
+    ResampleFilter filter = ResampleFilter::CatmullRom;
+    DeviceTile *base = nullptr;  // optional, of the OUTPUT's size: added to the upsampled plane (detail transfer)
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        nz_handle h = 0;
+        const float *b = base ? base->ptr : nullptr;
+        if (auto *gb = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_upsample_batch(ctx, d->data->ptr, d->resolution, out_tile->ptr, factor, (int)filter, b, gb->count,
+                                    dependency.id, &h), "nz_upsample_batch");
+        } else {
+            check(nz_upsample(ctx, d->data->ptr, d->resolution, out_tile->ptr, factor, (int)filter, b, dependency.id, &h),
+                  "nz_upsample");
+        }
+        jobHandle = done(h);
+    }
+
+  protected:
+    size_t out_length(size_t n) const override { return n * factor * factor; }
+    int out_position(int v) const override { return v * factor; }
+};
+
+class DownsampleStage : public ResampleStage {
+  public:
+    using ResampleStage::ResampleStage;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        nz_handle h = 0;
+        if (auto *gb = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_downsample_batch(ctx, d->data->ptr, d->resolution, out_tile->ptr, factor, gb->count, dependency.id, &h),
+                  "nz_downsample_batch");
+        } else {
+            check(nz_downsample(ctx, d->data->ptr, d->resolution, out_tile->ptr, factor, dependency.id, &h), "nz_downsample");
+        }
+        jobHandle = done(h);
+    }
+
+  protected:
+    size_t out_length(size_t n) const override { return n / ((size_t)factor * factor); }
+    int out_position(int v) const override { return v >= 0 ? v / factor : -((-v + factor - 1) / factor); }  // floor
 };
 
 class CurveStage : public TmpStage {

@@ -45,6 +45,12 @@ class HydraulicBorder(enum.IntEnum):  # new-framework: the tile border of Hydrau
     Open = 1    # the tile is cut out of a larger world: water and sediment run off the map
 
 
+class ResampleFilter(enum.IntEnum):  # new-framework: the filter of UpsampleStage (enum nz_resample_filter)
+    Nearest = 0
+    Bilinear = 1
+    CatmullRom = 2
+
+
 class KernelFilterType(enum.IntEnum):  # Filter/Kernel/KernelJob.cs:79-94
     Gauss9_S1 = 0
     Gauss7_S1 = 1
@@ -154,16 +160,18 @@ class GeneratorDataBatch(GeneratorData):
     tile).  The noise / filter / blur / erosion / flow-map stages run such a batch through one launch
     sequence (nz_*_batch); every tile comes out exactly as it would alone."""
 
-    def __init__(self, uuid="", data=None, resolution=512, positions=None, count=1, write=None):
+    def __init__(self, uuid="", data=None, resolution=512, positions=None, count=1, write=None, hostPositions=None):
         super().__init__(uuid, data, resolution, 0, 0, write)
         self.positions = positions
         self.count = count
+        self.hostPositions = hostPositions  # the same pairs on the host (int32, count x 2), for a stage that rescales them
 
     @classmethod
     def create(cls, ctx, uuid, resolution, positions):
         """positions: sequence of (xpos, zpos); allocates the stacked planes and uploads the positions."""
         pos = np.ascontiguousarray(positions, np.int32).reshape(-1, 2)
-        return cls(uuid, ctx.alloc(len(pos) * resolution * resolution), resolution, ctx.from_host(pos), len(pos))
+        return cls(uuid, ctx.alloc(len(pos) * resolution * resolution), resolution, ctx.from_host(pos), len(pos),
+                   hostPositions=pos)
 
     def tile(self, k):
         n = self.resolution * self.resolution
@@ -585,6 +593,104 @@ class CropStage(PipelineStage):  # Filter/Sample/CropStage.cs:11-19
             raise Exception("Unhandled stageio %s" % type(d).__name__)
         self.jobHandle = self.ctx.call("nz_crop_job", d.inputData.ptr, d.inputResolution, d.data.ptr, d.resolution,
                                        dep=dependency)
+
+
+class _ResampleStage(PipelineStage):
+    """What UpsampleStage and DownsampleStage share: the stage owns its output plane (resized when the input size changes)
+    and hands downstream a GeneratorData -- or GeneratorDataBatch -- of the new resolution whose plane it is, as
+    ReduceStage.TransformData hands on a GeneratorData."""
+
+    def __init__(self, ctx, factor):
+        super().__init__(ctx)
+        self.factor = factor
+        self.out = None
+        self.outPositions = self.outHostPositions = None
+
+    def _out_length(self, size):
+        raise NotImplementedError
+
+    def _out_position(self, v):
+        raise NotImplementedError
+
+    def ResizeNativeContainers(self, size):
+        if self.out is not None and self.out.IsCreated:
+            self.out.Dispose()
+        self.out = self.ctx.alloc(self._out_length(size))
+
+    def TransformData(self, inputData):
+        d = inputData.data
+        res = self._out_position(d.resolution)  # a resolution scales as a position does
+        if isinstance(d, GeneratorDataBatch):
+            # the positions are rescaled on the host from the payload's host copy (GeneratorDataBatch.create keeps one): no
+            # wait on the device in the scheduling path, and one upload per new set of positions.  A payload built without
+            # a host copy is read back once
+            pos = d.hostPositions if d.hostPositions is not None else d.positions.ToArray()
+            pos = np.array([self._out_position(int(v)) for v in np.asarray(pos).reshape(-1)], np.int32).reshape(-1, 2)
+            if self.outHostPositions is None or not np.array_equal(pos, self.outHostPositions):
+                if self.outPositions is not None and self.outPositions.IsCreated:
+                    self.outPositions.Dispose()
+                self.outPositions, self.outHostPositions = self.ctx.from_host(pos), pos
+            inputData.data = GeneratorDataBatch(d.uuid, self.out, res, self.outPositions, d.count, hostPositions=pos)
+        else:
+            inputData.data = GeneratorData(d.uuid, self.out, res, self._out_position(d.xpos), self._out_position(d.zpos))
+
+    def OnDestroy(self):
+        for t in (self.out, self.outPositions):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.out = self.outPositions = self.outHostPositions = None
+
+
+class UpsampleStage(_ResampleStage):
+    """New-framework stage: resolution R -> R * factor (2, 4 or 8) with nz_upsample: cell-centred nearest, bilinear or
+    Catmull-Rom (include/noize_hip.h).  `base` (optional): a DeviceTile of the OUTPUT's size -- one tile, or `count` tiles
+    for a batch -- that is added to the upsampled plane: the detail-transfer step of a coarse-to-fine pass.  xpos / zpos
+    are multiplied by the factor."""
+
+    def __init__(self, ctx, factor=2, filter=ResampleFilter.CatmullRom, base=None):
+        super().__init__(ctx, factor)
+        self.filter = filter
+        self.base = base
+
+    def _out_length(self, size):
+        return size * self.factor * self.factor
+
+    def _out_position(self, v):
+        return v * self.factor
+
+    def Schedule(self, requirements, dependency):
+        self.CheckRequirements(GeneratorData, requirements)
+        d = requirements.data
+        base = self.base.ptr if self.base is not None else None
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_upsample_batch", d.data.ptr, d.resolution, self.out.ptr, self.factor,
+                                           int(self.filter), base, d.count, dep=dependency)
+            return
+        self.jobHandle = self.ctx.call("nz_upsample", d.data.ptr, d.resolution, self.out.ptr, self.factor, int(self.filter),
+                                       base, dep=dependency)
+
+
+class DownsampleStage(_ResampleStage):
+    """New-framework stage: resolution R -> R / factor (2, 4 or 8; the factor divides R) with nz_downsample, the mean of
+    every factor x factor block.  xpos / zpos are floor-divided by the factor."""
+
+    def __init__(self, ctx, factor=2):
+        super().__init__(ctx, factor)
+
+    def _out_length(self, size):
+        return size // (self.factor * self.factor)
+
+    def _out_position(self, v):
+        return v // self.factor
+
+    def Schedule(self, requirements, dependency):
+        self.CheckRequirements(GeneratorData, requirements)
+        d = requirements.data
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_downsample_batch", d.data.ptr, d.resolution, self.out.ptr, self.factor,
+                                           d.count, dep=dependency)
+            return
+        self.jobHandle = self.ctx.call("nz_downsample", d.data.ptr, d.resolution, self.out.ptr, self.factor, dep=dependency)
 
 
 class StageThermalErosion(PipelineStage):  # Filter/Kernel/Blur/StageThermalErosion.cs:12-29

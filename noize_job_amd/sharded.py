@@ -412,6 +412,19 @@ class HipStripeOps:
         self._call("nz_hydraulic_stripe", h_in.data_ptr(), h_out.data_ptr(), pin, pout, ptr(work), C.byref(st),
                    C.byref(desc), int(first), int(last))
 
+    def upsample_halo_rows(self, filter):
+        return self.lib.nz_upsample_stripe_halo_rows(int(filter))
+
+    def upsample(self, src, src_st, dst, dst_st, factor, filter, base=None):
+        """nz_upsample_stripe: the owned rows of the fine stripe `dst_st` from the coarse stripe `src_st` (nz_stripe
+        structs; the fine grid is `factor` times the coarse one).  base: None, dst itself or a plane apart from it."""
+        self._call("nz_upsample_stripe", src.data_ptr(), C.byref(src_st), dst.data_ptr(), C.byref(dst_st), int(factor),
+                   int(filter), base.data_ptr() if base is not None else None)
+
+    def downsample(self, src, src_st, dst, dst_st, factor):
+        """nz_downsample_stripe: the owned rows of the coarse stripe `dst_st` from the fine stripe `src_st`."""
+        self._call("nz_downsample_stripe", src.data_ptr(), C.byref(src_st), dst.data_ptr(), C.byref(dst_st), int(factor))
+
     def map_range(self, buf, n, res, lim_min=float("inf"), lim_max=float("-inf")):
         """GetMapRangeJob over the first n floats of `buf` into the 3-float device buffer `res`."""
         self._call("nz_get_map_range", buf.data_ptr(), n, res.data_ptr(), lim_min, lim_max)
