@@ -49,6 +49,14 @@ namespace xshazwar.noize.hip {
         public IntPtr rainMap, hardness, wear, deposits;
     }
 
+    // stream-power fluvial erosion's scalars and optional read-only planes (nz_fluvial_erosion*); IntPtr.Zero = option off
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzFluvialDesc {                                                                    // nz_fluvial_desc
+        public int iterations;
+        public float erodibility, uplift, dt, rain, seaLevel;
+        public IntPtr rainMap, hardness, upliftMap, drainageIn;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

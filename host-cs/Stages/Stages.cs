@@ -332,6 +332,56 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; masks?.Dispose(); masks = null; }
     }
 
+    // Stream-power fluvial erosion with drainage area (new-framework feature; the model: nz_fluvial_erosion in
+    // include/noize_hip.h): dendritic valleys that run from the ridges to the tile's border.  Owns its work planes like
+    // HydraulicErosionStage; once the handle completes, Drainage holds the drainage area of the last payload (count *
+    // resolution^2 floats), the river map.  seaLevel: cells at or below it are outlets like the border (-float.MaxValue: off).
+    // rainMap / hardness / upliftMap / drainageIn are planes of the payload's size the caller supplies and keeps alive
+    // (rain * rainMap, erodibility * (1 - hardness), uplift * upliftMap, the drainage to start from).
+    public class FluvialErosionStage : PipelineStage {
+        public int iterations = 200;
+        public float erodibility = 0.05f, uplift = 0.002f, dt = 1f, rain = 1f, seaLevel = -float.MaxValue;
+        public DeviceTile rainMap = null;
+        public DeviceTile hardness = null;
+        public DeviceTile upliftMap = null;
+        public DeviceTile drainageIn = null;
+        DeviceTile work;                         // nz_fluvial_erosion_work_floats planes; the first count * resolution^2 floats: the drainage
+        int resolution, count = 1;
+        public FluvialErosionStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Drainage => work?.Offset(0, Cells);
+        public override void ResizeNativeContainers(int size) {
+            work?.Dispose();
+            work = ctx.Alloc((int) (ulong) Native.nz_fluvial_erosion_work_floats(resolution, count));
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
+            GeneratorData d = (GeneratorData) requirements.data;
+            foreach (DeviceTile m in new[] { rainMap, hardness, upliftMap, drainageIn })   // before any launch
+                if (m != null && m.Length != Cells) throw new Exception($"FluvialErosionStage: a plane of {m.Length} floats does not fit the payload's {Cells}");
+            NzFluvialDesc desc = new NzFluvialDesc {
+                iterations = iterations, erodibility = erodibility, uplift = uplift, dt = dt, rain = rain, seaLevel = seaLevel,
+                rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero, hardness = hardness != null ? hardness.Ptr : IntPtr.Zero,
+                upliftMap = upliftMap != null ? upliftMap.Ptr : IntPtr.Zero, drainageIn = drainageIn != null ? drainageIn.Ptr : IntPtr.Zero };
+            ulong h;
+            if (d.write != null) {
+                NzRwTile t = new NzRwTile { read = d.data.Ptr, write = d.write.Ptr, resolution = d.resolution, count = count };
+                Native.Check(Native.nz_fluvial_erosion_rw(ctx.Handle, ref t, work.Ptr, ref desc, dependency.id, out h), "nz_fluvial_erosion_rw");
+                Adopt(d, t);
+            } else if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_fluvial_erosion_batch(ctx.Handle, b.data.Ptr, work.Ptr, ref desc, b.resolution, b.count, dependency.id, out h), "nz_fluvial_erosion_batch");
+            } else {
+                Native.Check(Native.nz_fluvial_erosion(ctx.Handle, d.data.Ptr, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_fluvial_erosion");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() { work?.Dispose(); work = null; }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

@@ -728,6 +728,66 @@ int32_t nz_upsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt
 int32_t nz_downsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst, const nz_stripe *dstSt,
                              int32_t factor, nz_handle dep, nz_handle *out);
 
+/* ---- stream-power fluvial erosion with drainage area (new-framework feature) --------------------------------------------
+ * A connected river network: every cell drains to its steepest-descent neighbour of eight, the drainage area A is
+ * accumulated down that tree, and the bed is lowered by k sqrt(A) slope against an uplift (the parallel form of Schott et al.
+ * 2023, "Large-scale terrain authoring through interactive erosion simulation").  Besides the heights it yields the
+ * drainage plane, the river map.
+ *
+ * THE MODEL (tests/fluvial_ref.py restates it in numpy; the kernel, nz_fluvial.hip, follows it operation for operation):
+ *   Square tile res x res, row-major z * res + x, float32 throughout, no contraction, the same in every float mode
+ *   (nz_ctx_set_float_mode does not apply).  State: height h, drainage A.  Start: A = drainageIn[c] when that plane is
+ *   given, otherwise A = rain_c.  rain_c = rain * rainMap[c] (one multiply), without a map rain.
+ *   Neighbours k = 0..7 as (dx, dz): W(-1,0) E(+1,0) S(0,-1) N(0,+1) SW(-1,-1) SE(+1,-1) NW(-1,+1) NE(+1,+1).  A neighbour
+ *   outside the tile does not exist; nothing is clamped.
+ *   Outlets: a cell on the tile's border (x or z is 0 or res-1), or with h[c] <= seaLevel.  An outlet has no receiver and
+ *   keeps its height; it does accumulate drainage.
+ *   One iteration reads h, A and writes h', A':
+ *   1. receiver r(c) and slope S(c): best = +0, r = none, drop = +0; for k ascending over the existing neighbours:
+ *      d = h[c] - h[k]; s = d for k < 4, otherwise s = d * 0x1.6a09e6p-1f (0.70710678f, bits 0x3F3504F3); if s > best
+ *      then best = s, r = k, drop = d.  The comparison is strict: a tie keeps the earlier k.  S = best.  For an outlet
+ *      r = none and S = drop = 0.
+ *   2. A'[c] = rain_c; then, for k ascending over the existing neighbours whose receiver (step 1, same h) is c -- the
+ *      direction opposite to k -- A'[c] = A'[c] + A[k].
+ *   3. an outlet keeps h' = h.  Otherwise kc = erodibility * (1 - hardness[c]) (without a map erodibility);
+ *      e = ((kc * sqrt(A'[c])) * S) * dt; lim = drop * 0.5f; e = lim < e ? lim : e; du = (dt * uplift) * upliftMap[c]
+ *      (without a map dt * uplift); h' = (h - e) + du.  sqrt is the correctly rounded float32 square root.
+ *   After the last iteration the heights are the result and A is the drainage plane.  iterations == 0 leaves the heights
+ *   unchanged; the drainage is then the start state.
+ * What follows from it: the receiver is strictly lower, so the drainage tree has no cycles.  The half-drop limit keeps
+ * h' >= the old height of the receiver (a limit of the whole drop lands cells on their receiver's old height and breeds
+ * flats), so no height ever falls below the input's minimum, and none rises by more than iterations * dt * uplift *
+ * max(upliftMap) plus rounding.  With rain == 1 and no map the drainage values are integers, exact in float32 below 2^24.
+ * With erodibility = uplift = 0 the drainage reaches, after as many iterations as the longest flow path has cells, the
+ * exact accumulation over the receiver tree, and its sum over the receiver-less cells is res^2.
+ * Defaults of the hosts' FluvialErosionStage: erodibility 0.05, uplift 0.002, dt 1, rain 1, seaLevel -FLT_MAX (off).
+ *
+ * nz_fluvial_desc carries the scalars and four optional read-only planes of count * resolution^2 floats each (NULL: the
+ * option is off).  The maps are read at the cell itself only; their contents are the caller's.  A rainMap of ones, a
+ * hardness of zeros and an upliftMap of ones each give the no-map result bit for bit.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: a scalar that is not finite;
+ * erodibility, uplift, dt or rain < 0; iterations < 0; a NULL desc; drainageIn overlapping src (either plane of an _rw
+ * pair) or work; a map overlapping a plane that is written (the same planes).
+ * `work` = nz_fluvial_erosion_work_floats(resolution, count) floats, stage-owned.  After the call completes, its first
+ * count * resolution^2 floats hold the drainage.  The result lands in `src`; the _rw form reads tile->read, ping-pongs
+ * between the pair and returns with tile->read holding the result; the _batch form runs `count` tiles stored back to back,
+ * each with its own border.  The three forms and every batch position agree bit for bit. */
+typedef struct nz_fluvial_desc {
+    int32_t iterations;
+    float erodibility, uplift, dt, rain, seaLevel;
+    const float *rainMap;     /* NULL: rain everywhere */
+    const float *hardness;    /* NULL: erodibility everywhere */
+    const float *upliftMap;   /* NULL: uplift everywhere */
+    const float *drainageIn;  /* NULL: the drainage starts at rain_c */
+} nz_fluvial_desc;
+size_t nz_fluvial_erosion_work_floats(int32_t resolution, int32_t count);
+int32_t nz_fluvial_erosion(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
+                           nz_handle dep, nz_handle *out);
+int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_fluvial_desc *desc, nz_handle dep,
+                              nz_handle *out);
+int32_t nz_fluvial_erosion_batch(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
+                                 int32_t count, nz_handle dep, nz_handle *out);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

@@ -80,7 +80,16 @@ class HydraulicDesc(C.Structure):
                  ("deposits", C.c_void_p)])
 
 
+class FluvialDesc(C.Structure):
+    """nz_fluvial_desc (include/noize_hip.h): the scalars of stream-power fluvial erosion and the four optional read-only
+    planes (device addresses; None = the option is off)."""
+    _fields_ = ([("iterations", C.c_int32)] +
+                [(n, C.c_float) for n in ("erodibility", "uplift", "dt", "rain", "seaLevel")] +
+                [(n, C.c_void_p) for n in ("rainMap", "hardness", "upliftMap", "drainageIn")])
+
+
 hd_p = C.POINTER(HydraulicDesc)
+fd_p = C.POINTER(FluvialDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -171,6 +180,10 @@ SIGNATURES = {
     "nz_hydraulic_stripe_work_floats": (_sz, [stripe_p, _i]),
     "nz_hydraulic_stripe": (_i, [ctx_p, dev_ptr, dev_ptr, C.POINTER(dev_ptr), C.POINTER(dev_ptr), dev_ptr, stripe_p, hd_p,
                                  _i, _i] + _tail),
+    "nz_fluvial_erosion_work_floats": (_sz, [_i, _i]),
+    "nz_fluvial_erosion": (_i, [ctx_p, dev_ptr, dev_ptr, fd_p, _i] + _tail),
+    "nz_fluvial_erosion_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, fd_p] + _tail),
+    "nz_fluvial_erosion_batch": (_i, [ctx_p, dev_ptr, dev_ptr, fd_p, _i, _i] + _tail),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

@@ -337,6 +337,18 @@ int32_t nz_launch_hydraulic_stripe(hipStream_t s, const float *h_in, float *h_ou
                                    const nz_hydraulic_params &k, const nz_geom &g, int own0, int own1, int first, int last,
                                    const nz_hydraulic_ex &ex);
 
+// stream-power fluvial erosion (nz_fluvial.hip): one iteration per launch on `count` tiles of res^2 cells stored back to
+// back, heights h_in -> h_out and drainage a_in -> a_out.  a_in NULL: the drainage read is the constant k.rain (the start
+// state without rain map and drainageIn).  A NULL map is an option left off
+struct nz_fluvial_params {
+    float erodibility, uplift, dt, rain, sea_level;
+};
+int32_t nz_launch_fluvial(hipStream_t s, const float *h_in, float *h_out, const float *a_in, float *a_out,
+                          const nz_fluvial_params &k, int res, int count, const float *rain_map, const float *hardness,
+                          const float *uplift_map);
+// the start state with a rain map: a[i] = rain * rain_map[i]
+int32_t nz_launch_fluvial_start(hipStream_t s, float *a, const float *rain_map, float rain, size_t n);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {

@@ -1249,6 +1249,119 @@ extern "C" int32_t nz_hydraulic_stripe(nz_ctx *ctx, const float *height_in, floa
 }
 
 // ---------------------------------------------------------------------------------------------
+// stream-power fluvial erosion with drainage area (new-framework feature, include/noize_hip.h, nz_fluvial.hip)
+// ---------------------------------------------------------------------------------------------
+// work planes of count * res^2 floats each: 0 and 1 the drainage planes the launches ping-pong between -- in such an order
+// that the last launch writes plane 0 -- and 2 the in-place forms' second height plane
+constexpr int FLU_PLANES = 3;
+
+extern "C" size_t nz_fluvial_erosion_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? (size_t)FLU_PLANES * resolution * resolution * count : 0;
+}
+
+// the scalars' ranges, and the read-only planes of the desc against the planes the call writes: h0 / h1 the height
+// plane(s) (h1 may be NULL), n floats each like every plane of the desc, and `work`
+static int32_t check_fluvial(const nz_fluvial_desc *d, const float *h0, const float *h1, const float *work, size_t n,
+                             nz_fluvial_params *k) {
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(d->iterations >= 0, "iterations %d < 0", d->iterations);
+    const struct { const char *name; float v; bool signed_; } args[] = {
+        {"erodibility", d->erodibility, false}, {"uplift", d->uplift, false}, {"dt", d->dt, false},
+        {"rain", d->rain, false},               {"seaLevel", d->seaLevel, true}};
+    for (const auto &a : args) {
+        NZ_REQUIRE(std::isfinite(a.v), "%s is not finite", a.name);
+        NZ_REQUIRE(a.signed_ || a.v >= 0.0f, "%s %g < 0", a.name, (double)a.v);
+    }
+    auto overlap = [](const float *a, size_t na, const float *b, size_t nb) {
+        return a && b && (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+    };
+    const struct { const char *name; const float *p; } reads[] = {
+        {"drainageIn", d->drainageIn}, {"rainMap", d->rainMap}, {"hardness", d->hardness}, {"upliftMap", d->upliftMap}};
+    const struct { const char *name; const float *p; size_t n; } writes[] = {
+        {"src", h0, n}, {"the write plane", h1, n}, {"work", work, (size_t)FLU_PLANES * n}};
+    for (const auto &r : reads)
+        for (const auto &w : writes) NZ_REQUIRE(!overlap(r.p, n, w.p, w.n), "%s overlaps %s", r.name, w.name);
+    *k = nz_fluvial_params{d->erodibility, d->uplift, d->dt, d->rain, d->seaLevel};
+    return NZ_OK;
+}
+
+// `iterations` launches on `count` tiles; the height ping-pongs between h0 (which holds the input) and h1 as in
+// hydraulic_series (*in_h1, keep_h0), the drainage between work planes 0 and 1: launch `it` writes plane (iterations-1-it)&1,
+// so the last one writes plane 0.  The first launch reads drainageIn, or the start state rain * rainMap written here into
+// the plane it does not write, or -- without either -- no drainage plane at all.  Without an iteration plane 0 receives
+// the start state.
+static int32_t fluvial_series(nz_ctx *ctx, float *h0, float *h1, float *work, int res, int count, const nz_fluvial_desc &d,
+                              const nz_fluvial_params &k, bool keep_h0, bool *in_h1) {
+    const size_t n = (size_t)res * res * count;
+    const int iterations = d.iterations;
+    float *planes[2] = {work, work + n};
+    *in_h1 = false;
+    if (iterations == 0) {
+        nz_ctx_arm_last_launch(ctx);
+        if (d.drainageIn) return nz_launch_copy(ctx->stream, work, d.drainageIn, n);
+        if (d.rainMap) return nz_launch_fluvial_start(ctx->stream, work, d.rainMap, k.rain, n);
+        return nz_launch_fill(ctx->stream, work, n, k.rain);
+    }
+    float *cur = h0, *nxt = h1;
+    if (keep_h0 && (iterations & 1)) {
+        NZ_TRY(nz_launch_copy(ctx->stream, h1, h0, n));
+        std::swap(cur, nxt);
+    }
+    const float *a_in = d.drainageIn;
+    if (!a_in && d.rainMap) {
+        NZ_TRY(nz_launch_fluvial_start(ctx->stream, planes[iterations & 1], d.rainMap, k.rain, n));
+        a_in = planes[iterations & 1];
+    }
+    for (int it = 0; it < iterations; it++) {
+        float *a_out = planes[(iterations - 1 - it) & 1];
+        if (it == iterations - 1) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fluvial(ctx->stream, cur, nxt, a_in, a_out, k, res, count, d.rainMap, d.hardness, d.upliftMap));
+        a_in = a_out;
+        std::swap(cur, nxt);
+    }
+    *in_h1 = cur == h1;
+    return NZ_OK;
+}
+
+static int32_t fluvial_stage_impl(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
+                                  int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    NZ_REQUIRE(src && work, "src/work is NULL");
+    const size_t n = (size_t)resolution * resolution * count;
+    nz_fluvial_params k;
+    NZ_TRY(check_fluvial(desc, src, nullptr, work, n, &k));
+    bool in_h1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (fluvial_series arms its last launch)
+    NZ_TRY(fluvial_series(ctx, src, work + (size_t)(FLU_PLANES - 1) * n, work, resolution, count, *desc, k, true, &in_h1));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fluvial_erosion(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
+                                      nz_handle dep, nz_handle *out) {
+    return fluvial_stage_impl(ctx, src, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_fluvial_erosion_batch(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc,
+                                            int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    return fluvial_stage_impl(ctx, src, work, desc, resolution, count, dep, out);
+}
+
+extern "C" int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_fluvial_desc *desc,
+                                         nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    NZ_REQUIRE(work, "work is NULL");
+    nz_fluvial_params k;
+    NZ_TRY(check_fluvial(desc, tile->read, tile->write, work, (size_t)tile->resolution * tile->resolution * tile->count, &k));
+    bool in_h1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (fluvial_series arms its last launch)
+    NZ_TRY(fluvial_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, *desc, k, false, &in_h1));
+    rw_swap(tile, in_h1);
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
 // upsample / downsample (new-framework feature, include/noize_hip.h, nz_resample.hip)
 // ---------------------------------------------------------------------------------------------
 static bool planes_overlap(const float *a, size_t na, const float *b, size_t nb) {

@@ -739,6 +739,55 @@ class HydraulicErosionStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, masks;  // masks: wear, then deposits
 };
 
+// Stream-power fluvial erosion with drainage area (new-framework feature; the model: nz_fluvial_erosion in
+// include/noize_hip.h): dendritic valleys that run from the ridges to the tile's border.  Owns its work planes like
+// HydraulicErosionStage; once the handle completes, drainage() holds the drainage area of the last payload
+// (drainageLength() floats: count * resolution^2), the river map.  seaLevel: cells at or below it are outlets like the
+// border (-FLT_MAX: off).  rainMap / hardness / upliftMap / drainageIn are planes of the payload's size the caller supplies
+// and keeps alive (rain * rainMap, erodibility * (1 - hardness), uplift * upliftMap, the drainage to start from).
+class FluvialErosionStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    int iterations = 200;
+    float erodibility = .05f, uplift = .002f, dt = 1.f, rain = 1.f, seaLevel = -3.402823466e+38f;
+    const DeviceTile *rainMap = nullptr, *hardness = nullptr, *upliftMap = nullptr, *drainageIn = nullptr;
+    void ResizeNativeContainers(size_t) override {
+        work.reset(new DeviceTile(ctx, nz_fluvial_erosion_work_floats(resolution, count)));
+    }
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
+        for (const DeviceTile *m : {rainMap, hardness, upliftMap, drainageIn})  // before any launch
+            if (m && m->Length != drainageLength()) throw std::runtime_error("FluvialErosionStage: a plane does not fit the payload");
+        const nz_fluvial_desc desc{iterations, erodibility, uplift, dt, rain, seaLevel,
+                                   rainMap ? rainMap->ptr : nullptr, hardness ? hardness->ptr : nullptr,
+                                   upliftMap ? upliftMap->ptr : nullptr, drainageIn ? drainageIn->ptr : nullptr};
+        nz_handle h = 0;
+        if (d->write) {
+            nz_rw_tile t = rw_pair(d, count);
+            check(nz_fluvial_erosion_rw(ctx, &t, work->ptr, &desc, dependency.id, &h), "nz_fluvial_erosion_rw");
+            rw_adopt(d, t);
+        } else if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_fluvial_erosion_batch(ctx, b->data->ptr, work->ptr, &desc, b->resolution, b->count, dependency.id, &h),
+                  "nz_fluvial_erosion_batch");
+        } else {
+            check(nz_fluvial_erosion(ctx, d->data->ptr, work->ptr, &desc, d->resolution, dependency.id, &h),
+                  "nz_fluvial_erosion");
+        }
+        jobHandle = done(h);
+    }
+    const float *drainage() const { return work ? work->ptr : nullptr; }
+    size_t drainageLength() const { return (size_t)count * resolution * resolution; }
+    void OnDestroy() override { work.reset(); }
+
+  private:
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

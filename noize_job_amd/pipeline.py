@@ -865,6 +865,87 @@ class HydraulicErosionStage(PipelineStage):
         self.DisposeArrays()
 
 
+class FluvialErosionStage(PipelineStage):
+    """Stream-power fluvial erosion with drainage area (new-framework feature; the model is the comment block of
+    nz_fluvial_erosion in include/noize_hip.h): every cell drains to its steepest-descent neighbour, the drainage area is
+    accumulated down that tree and the bed is lowered by erodibility * sqrt(area) * slope against the uplift -- dendritic
+    valleys that run from the ridges to the tile's border.  Like HydraulicErosionStage it owns its work planes; after the
+    stage's handle completes, `drainage` holds the drainage area (the river map) of the last payload, `count` tiles of
+    resolution^2 cells.
+
+    seaLevel: cells at or below it are outlets like the border cells (the default, -FLT_MAX, switches it off).  rainMap /
+    hardness / upliftMap / drainageIn: device planes of the payload's size (count * resolution^2 floats) the caller supplies
+    and keeps alive -- rain is multiplied by rainMap, erodibility by 1 - hardness, uplift by upliftMap, and drainageIn is
+    the drainage the accumulation starts from (the `drainage` of an earlier run, copied: it may not be the stage's own
+    plane)."""
+
+    SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+
+    def __init__(self, ctx, iterations=200, erodibility=0.05, uplift=0.002, dt=1.0, rain=1.0, seaLevel=SEA_OFF,
+                 rainMap=None, hardness=None, upliftMap=None, drainageIn=None):
+        super().__init__(ctx)
+        self.iterations = iterations
+        self.erodibility = erodibility
+        self.uplift = uplift
+        self.dt = dt
+        self.rain = rain
+        self.seaLevel = seaLevel
+        self.rainMap = rainMap
+        self.hardness = hardness
+        self.upliftMap = upliftMap
+        self.drainageIn = drainageIn
+        self.resolution = 0
+        self.count = 0
+        self.work = None  # nz_fluvial_erosion_work_floats planes; the first count * resolution^2 floats: the drainage
+
+    def DisposeArrays(self):
+        if self.work is not None and self.work.IsCreated:
+            self.work.Dispose()
+        self.work = None
+
+    def ResizeNativeContainers(self, size):
+        self.DisposeArrays()
+        self.work = self.ctx.alloc(N.lib.nz_fluvial_erosion_work_floats(self.resolution, self.count))
+
+    @property
+    def drainage(self):
+        """The drainage plane(s) of the last run: a view of the first count * resolution^2 floats of the work planes; None
+        before the first payload and after OnDestroy."""
+        if self.work is None:
+            return None
+        return self.work.offset(0, self.count * self.resolution * self.resolution)
+
+    def _desc(self):
+        n = self.count * self.resolution * self.resolution
+        planes = (("rainMap", self.rainMap), ("hardness", self.hardness), ("upliftMap", self.upliftMap),
+                  ("drainageIn", self.drainageIn))
+        for name, m in planes:
+            if m is not None and m.Length != n:
+                raise ValueError("FluvialErosionStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
+        return N.FluvialDesc(self.iterations, self.erodibility, self.uplift, self.dt, self.rain, self.seaLevel,
+                             *[m.ptr if m is not None else None for _, m in planes])
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        # the work planes are sized on the payload's cell count (count * resolution^2), as CheckRequirements tracks it
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        desc = self._desc()  # raises before any launch when a plane does not fit the payload
+        if d.write is not None:
+            self.jobHandle = _call_rw(self.ctx, "nz_fluvial_erosion_rw", d, self.work.ptr, C.byref(desc), dep=dependency)
+        elif isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_fluvial_erosion_batch", d.data.ptr, self.work.ptr, C.byref(desc),
+                                           d.resolution, d.count, dep=dependency)
+        else:
+            self.jobHandle = self.ctx.call("nz_fluvial_erosion", d.data.ptr, self.work.ptr, C.byref(desc), d.resolution,
+                                           dep=dependency)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
     def __init__(self, ctx, meshType=MeshType.SquareGridHeightMap):
         super().__init__(ctx)
