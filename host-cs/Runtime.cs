@@ -57,6 +57,14 @@ namespace xshazwar.noize.hip {
         public IntPtr rainMap, hardness, upliftMap, drainageIn;
     }
 
+    // depression filling's scalars and the optional lake-depth plane (nz_fill_depressions*); IntPtr.Zero = not wanted
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzFillDesc {                                                                       // nz_fill_desc
+        public float epsilon, seaLevel;
+        public int maxPasses;
+        public IntPtr depth;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

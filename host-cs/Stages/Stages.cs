@@ -382,6 +382,61 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; }
     }
 
+    // Depression filling (new-framework feature; the model: nz_fill_depressions in include/noize_hip.h): every closed hollow
+    // is raised to its spill level plus an epsilon gradient, so that FluvialErosionStage's river network reaches the border
+    // from its first iteration.  Owns its work planes like FluvialErosionStage.  With recordDepth, Depth holds the lake depth
+    // of the last payload (count * resolution^2 floats; zero where nothing was filled) once the handle completes; Passes and
+    // Converged wait for the handle and read the status words.  seaLevel: cells at or below it are outlets like the border
+    // (-float.MaxValue: off).  maxPasses null means the default, 64 + resolution / 4; a budget that runs out is no error:
+    // Converged is false, the heights are as they were and the depth is zero.
+    public class DepressionFillStage : PipelineStage {
+        public float epsilon = 1e-4f, seaLevel = -float.MaxValue;
+        public int? maxPasses = null;
+        public bool recordDepth = false;
+        DeviceTile work;                         // nz_fill_depressions_work_floats floats; its first two int32: {passes, converged}
+        DeviceTile lakes;
+        int resolution, count = 1;
+        public DepressionFillStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Depth => lakes;
+        public int? Passes => Status(0);
+        public bool? Converged => Status(1) is int c ? c == 1 : (bool?) null;
+        int? Status(int k) {
+            if (work == null) return null;
+            jobHandle.Complete();
+            return BitConverter.SingleToInt32Bits(work.Offset(0, 2).ToArray()[k]);
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            // sized on (resolution, count), not on the payload's cell count alone: the per-tile bytes depend on the number
+            // of 64 x 16 tiles, so two payloads of equal length can need different sizes
+            int need = (int) (ulong) Native.nz_fill_depressions_work_floats(resolution, count);
+            if (work == null || work.Length != need) { work?.Dispose(); work = ctx.Alloc(need); }
+            if (!recordDepth || (lakes != null && lakes.Length != Cells)) { lakes?.Dispose(); lakes = null; }
+            if (recordDepth && lakes == null) lakes = ctx.Alloc(Cells);
+            NzFillDesc desc = new NzFillDesc {
+                epsilon = epsilon, seaLevel = seaLevel, maxPasses = maxPasses ?? 64 + resolution / 4,
+                depth = lakes != null ? lakes.Ptr : IntPtr.Zero };
+            ulong h;
+            if (d.write != null) {
+                NzRwTile t = new NzRwTile { read = d.data.Ptr, write = d.write.Ptr, resolution = d.resolution, count = count };
+                Native.Check(Native.nz_fill_depressions_rw(ctx.Handle, ref t, work.Ptr, ref desc, dependency.id, out h), "nz_fill_depressions_rw");
+                Adopt(d, t);
+            } else if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_fill_depressions_batch(ctx.Handle, b.data.Ptr, work.Ptr, ref desc, b.resolution, b.count, dependency.id, out h), "nz_fill_depressions_batch");
+            } else {
+                Native.Check(Native.nz_fill_depressions(ctx.Handle, d.data.Ptr, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_fill_depressions");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() { work?.Dispose(); work = null; lakes?.Dispose(); lakes = null; }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

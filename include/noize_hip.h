@@ -788,6 +788,67 @@ int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const 
 int32_t nz_fluvial_erosion_batch(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
                                  int32_t count, nz_handle dep, nz_handle *out);
 
+/* ---- depression filling: lakes and pit-free drainage (new-framework feature) --------------------------------------------
+ * Raises every closed hollow of a tile to its spill level (Planchon & Darboux 2001, "A fast, simple and versatile algorithm
+ * to fill the depressions of digital elevation models"; Barnes et al. 2014, "Priority-flood"), so that the drainage network
+ * of nz_fluvial_erosion reaches the border from its first iteration.  Filled surface minus bed is the lake depth.
+ *
+ * THE MODEL (tests/fill_ref.py restates it in numpy; the kernel is nz_fill.hip):
+ *   Square tile res x res, row-major z * res + x, float32 throughout, no contraction, the same in every float mode
+ *   (nz_ctx_set_float_mode does not apply).  Neighbours k = 0..7 in the fluvial stage's order; a neighbour outside the tile
+ *   does not exist.
+ *   Outlets are exactly the fluvial stage's: border cells, and cells with h[c] <= seaLevel.  W[c] = h[c] for an outlet.
+ *   Operator for every other cell: m = +inf; for k ascending: t = W[k] + epsilon; m = t < m ? t : m;
+ *   F(W)[c] = h[c] > m ? h[c] : m.
+ *   Start: W = +inf at the non-outlets.  Result: the fixed point reached from that start.
+ *   With epsilon == 0 it is the spill elevation, the minimax path height to an outlet; flats remain.  With epsilon > 0 every
+ *   filled cell sits at least epsilon above some neighbour, so every non-outlet cell has a strictly lower neighbour and the
+ *   fluvial stage finds a receiver for it -- as long as epsilon is not absorbed by rounding at the tile's magnitudes.
+ * What follows from it: F is monotone and the start lies above every fixed point, so the result is the greatest fixed point
+ * and does not depend on the order of updates (Jacobi, tile-local sweeps and a priority flood give the same floats).
+ * W >= h; outlets are unchanged; filling a filled tile changes nothing; a tile without pits is returned bit for bit (with
+ * epsilon == 0; with epsilon > 0, a tile whose every non-outlet cell already lies epsilon above a neighbour); the result is
+ * never below the input's minimum.  Heights must be finite; otherwise the result is unspecified, but the call terminates,
+ * since the number of launches is fixed.
+ *
+ * The entry enqueues maxPasses pass launches and one finalise launch, stream-ordered like every other entry.  A pass sweeps
+ * every 64 x 16 tile on chip against its frozen ring, skips tiles whose neighbourhood was at rest in the pass before, and
+ * returns at once when the pass before changed nothing (a launch of that kind costs a few microseconds: tools/bench_fill.py
+ * measures it).  The result is ALL OR NOTHING: when the last pass that ran changed nothing, W lands in the heights and, where
+ * asked, W - h in `depth`; otherwise -- the budget was too small -- the heights stay as they were, `depth` is zero, and that
+ * is not an error.  After the call completes the first two int32 of `work` hold {passes that did work, converged 0/1}.
+ * Default of the hosts' DepressionFillStage: epsilon 1e-4, seaLevel -FLT_MAX (off), maxPasses 64 + resolution / 4.  The
+ * evidence (tools/bench_fill.py): an unfiltered 13-octave simplex fBm tile, 45 % of whose cells lie in
+ * hollows at 1024^2 and 68 % at 4096^2, converges in 50 and 152 passes; the defaults allow 320 and 1088.  As a rule of
+ * thumb, not a bound: a straight front crosses a tile (16 rows or 64 columns) per pass, so resolution / 16 passes cross the
+ * plane once and the default leaves four crossings; a winding spill path needs more passes per crossing.  A budget that
+ * runs out shows as converged == 0.  The unused launches cost 2 to 6 microseconds each.
+ *
+ * `work` = nz_fill_depressions_work_floats(resolution, count) floats, stage-owned; the size depends on the number of 64 x 16
+ * tiles, so two payloads of equal cell count may need different sizes.  The result lands in `src`, or in
+ * tile->read for the _rw form (the pair is not swapped; tile->write is left alone).  The _batch form runs `count` tiles stored
+ * back to back, each with its own border; the status words cover the whole batch.  The three forms and every batch position
+ * agree bit for bit.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: epsilon or seaLevel not finite
+ * (-FLT_MAX switches the sea off); epsilon < 0; maxPasses < 1; a NULL desc; depth overlapping src, either plane of an _rw
+ * pair, or work. */
+typedef struct nz_fill_desc {
+    float epsilon, seaLevel;
+    int32_t maxPasses;
+    float *depth;  /* NULL: not wanted */
+} nz_fill_desc;
+size_t nz_fill_depressions_work_floats(int32_t resolution, int32_t count);
+int32_t nz_fill_depressions(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc, int32_t resolution, nz_handle dep,
+                            nz_handle *out);
+int32_t nz_fill_depressions_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_fill_desc *desc, nz_handle dep,
+                               nz_handle *out);
+int32_t nz_fill_depressions_batch(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc, int32_t resolution,
+                                  int32_t count, nz_handle dep, nz_handle *out);
+/* Test hook: the cap on a pass's on-chip sweeps per tile (process-wide; <= 0 restores the default, 16).  Results must not
+ * change: the fixed point does not depend on the schedule.  Returns the cap that was in force.  Atomic: it may be called
+ * while entries run on other threads; a call that has begun keeps the cap it read. */
+int32_t nz_debug_fill_sweeps(int32_t sweeps);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

@@ -88,8 +88,15 @@ class FluvialDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("rainMap", "hardness", "upliftMap", "drainageIn")])
 
 
+class FillDesc(C.Structure):
+    """nz_fill_desc (include/noize_hip.h): the scalars of depression filling and the optional lake-depth plane (a device
+    address; None = not wanted)."""
+    _fields_ = [("epsilon", C.c_float), ("seaLevel", C.c_float), ("maxPasses", C.c_int32), ("depth", C.c_void_p)]
+
+
 hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
+fill_p = C.POINTER(FillDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -184,6 +191,11 @@ SIGNATURES = {
     "nz_fluvial_erosion": (_i, [ctx_p, dev_ptr, dev_ptr, fd_p, _i] + _tail),
     "nz_fluvial_erosion_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, fd_p] + _tail),
     "nz_fluvial_erosion_batch": (_i, [ctx_p, dev_ptr, dev_ptr, fd_p, _i, _i] + _tail),
+    "nz_fill_depressions_work_floats": (_sz, [_i, _i]),
+    "nz_fill_depressions": (_i, [ctx_p, dev_ptr, dev_ptr, fill_p, _i] + _tail),
+    "nz_fill_depressions_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, fill_p] + _tail),
+    "nz_fill_depressions_batch": (_i, [ctx_p, dev_ptr, dev_ptr, fill_p, _i, _i] + _tail),
+    "nz_debug_fill_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

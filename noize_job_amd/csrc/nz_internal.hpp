@@ -349,6 +349,15 @@ int32_t nz_launch_fluvial(hipStream_t s, const float *h_in, float *h_out, const 
 // the start state with a rain map: a[i] = rain * rain_map[i]
 int32_t nz_launch_fluvial_start(hipStream_t s, float *a, const float *rain_map, float rain, size_t n);
 
+// depression filling (nz_fill.hip): pass `pass` of the series on `count` tiles of res^2 cells stored back to back, W planes
+// w_in -> w_out (pass 0 reads none: it derives the start state from h), the per-tile "changed" bytes flags_in -> flags_out,
+// at most `sweeps` in-LDS sweeps per tile.  status: {passes, converged, changed[3]}, maintained by the launches themselves
+int32_t nz_launch_fill_pass(hipStream_t s, const float *h, const float *w_in, float *w_out, int *status,
+                            const unsigned char *flags_in, unsigned char *flags_out, float eps, float sea, int res, int count,
+                            int pass, int sweeps);
+// converged: h = w and (depth given) depth = w - h; otherwise h stays and depth = 0.  Sets status[1]
+int32_t nz_launch_fill_finalise(hipStream_t s, float *h, const float *w, float *depth, int *status, size_t n);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {

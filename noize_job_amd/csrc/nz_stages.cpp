@@ -1,5 +1,6 @@
 // nz_stages.cpp -- the extern "C" stage entry points of libnoize_hip.so (one per reference job delegate or
 // PipelineStage.Schedule body, include/noize_hip.h) and the launch planners behind them.
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1359,6 +1360,87 @@ extern "C" int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *w
     NZ_TRY(fluvial_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, *desc, k, false, &in_h1));
     rw_swap(tile, in_h1);
     return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
+// ---------------------------------------------------------------------------------------------
+// `work` in floats: 16 status words ({passes, converged, changed[3]}, the rest spare), two generations of per-tile bytes,
+// each rounded up to 16 bytes, and the two W planes of count * res^2 floats the passes alternate between.  One pass is one
+// launch whatever its depth, so the launch-series planner (nz_split_iterations) has nothing to split here.
+namespace {
+constexpr size_t FILL_STATUS = 16;
+constexpr int FILL_SWEEPS = 16;  // measured: DESIGN.md section 4
+std::atomic<int> fill_sweeps{FILL_SWEEPS};  // nz_debug_fill_sweeps may be called while another thread runs an entry
+struct fill_layout {
+    size_t gen_floats, n;  // one generation of tile bytes in floats, cells of the payload
+    size_t total() const { return FILL_STATUS + 2 * gen_floats + 2 * n; }
+};
+fill_layout fill_layout_of(int res, int count) {
+    const size_t tiles = (size_t)((res + 63) / 64) * ((res + 15) / 16) * count;
+    return fill_layout{(tiles + 15) / 16 * 4, (size_t)res * res * count};
+}
+}  // namespace
+
+extern "C" size_t nz_fill_depressions_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? fill_layout_of(resolution, count).total() : 0;
+}
+
+extern "C" int32_t nz_debug_fill_sweeps(int32_t sweeps) {
+    return fill_sweeps.exchange(sweeps > 0 ? sweeps : FILL_SWEEPS);
+}
+
+// h: the plane that holds the input and receives the result; other: the write plane of an _rw pair or NULL
+static int32_t fill_impl(nz_ctx *ctx, float *h, const float *other, float *work, const nz_fill_desc *d, int res, int count,
+                         nz_handle *out) {
+    NZ_REQUIRE(h && work, "src/work is NULL");
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(std::isfinite(d->epsilon), "epsilon is not finite");
+    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(d->epsilon >= 0.0f, "epsilon %g < 0", (double)d->epsilon);
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    const fill_layout L = fill_layout_of(res, count);
+    auto overlap = [](const float *a, size_t na, const float *b, size_t nb) {
+        return a && b && (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+    };
+    NZ_REQUIRE(!overlap(d->depth, L.n, h, L.n), "depth overlaps src");
+    NZ_REQUIRE(!overlap(d->depth, L.n, other, L.n), "depth overlaps the write plane");
+    NZ_REQUIRE(!overlap(d->depth, L.n, work, L.total()), "depth overlaps work");
+    int *status = reinterpret_cast<int *>(work);
+    unsigned char *flags[2] = {reinterpret_cast<unsigned char *>(work + FILL_STATUS),
+                               reinterpret_cast<unsigned char *>(work + FILL_STATUS + L.gen_floats)};
+    float *planes[2] = {work + FILL_STATUS + 2 * L.gen_floats, work + FILL_STATUS + 2 * L.gen_floats + L.n};
+    const float eps = d->epsilon + 0.0f;  // -0 -> +0
+    const int sweeps = fill_sweeps.load();  // one cap for the whole series
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int p = 0; p < d->maxPasses; p++)  // pass p writes plane p & 1 and byte generation p & 1
+        NZ_TRY(nz_launch_fill_pass(ctx->stream, h, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1], status,
+                                   flags[(p - 1) & 1], flags[p & 1], eps, d->seaLevel, res, count, p, sweeps));
+    nz_ctx_arm_last_launch(ctx);
+    // a converged series holds the fixed point in both planes, so either serves
+    NZ_TRY(nz_launch_fill_finalise(ctx->stream, h, planes[0], d->depth, status, L.n));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fill_depressions(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc, int32_t resolution,
+                                       nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, 1));
+    return fill_impl(ctx, src, nullptr, work, desc, resolution, 1, out);
+}
+
+extern "C" int32_t nz_fill_depressions_batch(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc,
+                                             int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    return fill_impl(ctx, src, nullptr, work, desc, resolution, count, out);
+}
+
+extern "C" int32_t nz_fill_depressions_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_fill_desc *desc, nz_handle dep,
+                                          nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    return fill_impl(ctx, tile->read, tile->write, work, desc, tile->resolution, tile->count, out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -4,6 +4,9 @@
 //          host_demo <resolution> <out.f32> reduce      (ReducePipeline: simplex x cellular, MULTIPLY)
 //          host_demo <resolution> <out.f32> context     (producer -> context buffer -> consumer, parked until written)
 //          host_demo <resolution> <out.f32> batch <n>   (n tiles at xpos = k * resolution through the batched stage bodies)
+//          host_demo <resolution> <out.f32> fill        (DepressionFillStage with recordDepth on a simplex tile, then the SAME
+//                            stage on a batch of 64 tiles of resolution / 8 -- equal length, more 64 x 16 tiles: heights,
+//                            depth, batch heights back to back; "passes converged" of either run on stdout)
 //          host_demo <resolution> <out.f32> live <particles> <cycles>   (cellular fBm -> LiveErosion, seeds 3, 14, 25, ...:
 //                                                                         height, pool, flow planes back to back)
 //          host_demo <resolution> <out.f32> sharded <stripes> [mode overlap]   (ShardedPipeline on ONE rank: the grid as
@@ -37,6 +40,7 @@ int main(int argc, char **argv) {
     int res = std::atoi(argv[1]);
     const bool reduce = argc > 3 && std::strcmp(argv[3], "reduce") == 0;
     const bool context = argc > 3 && std::strcmp(argv[3], "context") == 0;
+    const bool fill = argc > 3 && std::strcmp(argv[3], "fill") == 0;
     const int batch = argc > 4 && std::strcmp(argv[3], "batch") == 0 ? std::atoi(argv[4]) : 0;
     // `rw`: the tile is a READ / WRITE plane pair and the stencil stages swap it instead of flushing (nz_*_rw)
     const bool live = argc > 5 && std::strcmp(argv[3], "live") == 0;
@@ -183,6 +187,50 @@ int main(int argc, char **argv) {
             producer.Destroy();
             consumer.Destroy();
             mgr.OnDestroy();
+        } else if (fill) {
+            const size_t n = (size_t)res * res;
+            const int small = res / 8, many = 64;
+            if (small * 8 != res) throw std::runtime_error("fill: the resolution must be a multiple of 8");
+            DeviceTile tile(ctx, n), tiles(ctx, n);
+            std::vector<int32_t> pos(2 * many);
+            for (int k = 0; k < many; k++) pos[2 * k] = k * small, pos[2 * k + 1] = 7 * k;
+            DeviceTile dpos(ctx, (2 * many * sizeof(int32_t) + 3) / 4);
+            dpos.CopyFrom(reinterpret_cast<const float *>(pos.data()));
+            NoiseStage noise(ctx);
+            noise.noiseType = FractalNoise::Simplex;
+            noise.hurst = 0.4f;
+            noise.octaves = 6;
+            noise.noiseSize = 300;
+            DepressionFillStage lakes(ctx);
+            lakes.recordDepth = true;
+            BasePipeline pipe({&noise, &lakes});
+            std::vector<float> host(3 * n);
+            GeneratorData gd;
+            gd.uuid = "host-demo-fill";
+            gd.data = &tile;
+            gd.resolution = res;
+            gd.xpos = 37;
+            gd.zpos = 11;
+            pipe.Enqueue(&gd);
+            pipe.RunToCompletion();
+            std::printf("%d %d\n", lakes.passes(), lakes.converged() ? 1 : 0);
+            tile.CopyTo(host.data());
+            check(nz_tile_download(ctx, const_cast<float *>(lakes.depth()), host.data() + n, n, 0, nullptr), "nz_tile_download");
+            check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+            GeneratorDataBatch gb;
+            gb.uuid = "host-demo-fill-batch";
+            gb.data = &tiles;
+            gb.resolution = small;
+            gb.count = many;
+            gb.positions = reinterpret_cast<const int32_t *>(dpos.ptr);
+            pipe.Enqueue(&gb);
+            pipe.RunToCompletion();
+            std::printf("%d %d\n", lakes.passes(), lakes.converged() ? 1 : 0);
+            tiles.CopyTo(host.data() + 2 * n);
+            FILE *f = std::fopen(argv[2], "wb");
+            if (!f || std::fwrite(host.data(), sizeof(float), host.size(), f) != host.size()) throw std::runtime_error("write failed");
+            std::fclose(f);
+            pipe.Destroy();
         } else if (batch > 0) {
             const size_t n = (size_t)res * res;
             DeviceTile tiles(ctx, n * batch);

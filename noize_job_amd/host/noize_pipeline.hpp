@@ -788,6 +788,66 @@ class FluvialErosionStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work;
 };
 
+// Depression filling (new-framework feature; the model: nz_fill_depressions in include/noize_hip.h): every closed hollow
+// is raised to its spill level plus an epsilon gradient, so that FluvialErosionStage's river network reaches the border
+// from its first iteration.  Owns its work planes like FluvialErosionStage.  With recordDepth, depth() holds the lake depth
+// of the last payload (depthLength() floats; zero where nothing was filled) once the handle completes; passes() and
+// converged() wait for the handle and read the status words.  seaLevel: cells at or below it are outlets like the border
+// (-FLT_MAX: off).  maxPasses < 1 means the default, 64 + resolution / 4; a budget that runs out is no error: converged()
+// is false, the heights are as they were and the depth is zero.
+class DepressionFillStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    float epsilon = 1e-4f, seaLevel = -3.402823466e+38f;
+    int maxPasses = 0;  // < 1: 64 + resolution / 4
+    bool recordDepth = false;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        // sized on (resolution, count), not on the payload's cell count alone: the per-tile bytes depend on the number of
+        // 64 x 16 tiles, so two payloads of equal length can need different sizes
+        const size_t need = nz_fill_depressions_work_floats(resolution, count);
+        if (!work || work->Length != need) work.reset(new DeviceTile(ctx, need));
+        if (!recordDepth) lakes.reset();
+        else if (!lakes || lakes->Length != depthLength()) lakes.reset(new DeviceTile(ctx, depthLength()));
+        const nz_fill_desc desc{epsilon, seaLevel, maxPasses >= 1 ? maxPasses : 64 + resolution / 4,
+                                lakes ? lakes->ptr : nullptr};
+        nz_handle h = 0;
+        if (d->write) {
+            nz_rw_tile t = rw_pair(d, count);
+            check(nz_fill_depressions_rw(ctx, &t, work->ptr, &desc, dependency.id, &h), "nz_fill_depressions_rw");
+            rw_adopt(d, t);
+        } else if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_fill_depressions_batch(ctx, b->data->ptr, work->ptr, &desc, b->resolution, b->count, dependency.id, &h),
+                  "nz_fill_depressions_batch");
+        } else {
+            check(nz_fill_depressions(ctx, d->data->ptr, work->ptr, &desc, d->resolution, dependency.id, &h),
+                  "nz_fill_depressions");
+        }
+        jobHandle = done(h);
+    }
+    const float *depth() const { return lakes ? lakes->ptr : nullptr; }
+    size_t depthLength() const { return (size_t)count * resolution * resolution; }
+    int passes() const { return status(0); }                // -1 before the first run
+    bool converged() const { return status(1) == 1; }
+    void OnDestroy() override { work.reset(); lakes.reset(); }
+
+  private:
+    int status(int k) const {
+        if (!work) return -1;
+        jobHandle.Complete();
+        int32_t words[2];
+        check(nz_tile_download(ctx, work->ptr, reinterpret_cast<float *>(words), 2, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[k];
+    }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, lakes;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

@@ -946,6 +946,101 @@ class FluvialErosionStage(PipelineStage):
         self.DisposeArrays()
 
 
+class DepressionFillStage(PipelineStage):
+    """Depression filling (new-framework feature; the model is the comment block of nz_fill_depressions in
+    include/noize_hip.h): every closed hollow is raised to its spill level plus an epsilon gradient, so that every cell but
+    the outlets has a strictly lower neighbour and FluvialErosionStage's river network reaches the border from its first
+    iteration.  Like FluvialErosionStage it owns its work planes.  With recordDepth, `depth` holds the lake depth of the
+    last payload (filled surface minus bed, count * resolution^2 floats; zero where nothing was filled) once the stage's
+    handle completes; `passes` and `converged` are the status words of that run.
+
+    seaLevel: cells at or below it are outlets like the border cells (the default, -FLT_MAX, switches it off).  maxPasses:
+    the number of pass launches; None means 64 + resolution // 4.  A budget that runs out is no error: converged is False,
+    the heights are as they were and the depth is zero."""
+
+    SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+
+    def __init__(self, ctx, epsilon=1e-4, seaLevel=SEA_OFF, maxPasses=None, recordDepth=False):
+        super().__init__(ctx)
+        self.epsilon = epsilon
+        self.seaLevel = seaLevel
+        self.maxPasses = maxPasses
+        self.recordDepth = recordDepth
+        self.resolution = 0
+        self.count = 0
+        self.work = None    # nz_fill_depressions_work_floats floats; its first two int32: {passes, converged}
+        self._depth = None  # the lake-depth planes (recordDepth)
+
+    def DisposeArrays(self):
+        for t in (self.work, self._depth):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.work = self._depth = None
+
+    def _size_work(self):
+        """The work planes are sized on (resolution, count) -- the per-tile bytes depend on the number of 64 x 16 tiles --
+        and not on the payload's cell count alone, which is all CheckRequirements tracks: two payloads of equal length can
+        need different sizes."""
+        need = N.lib.nz_fill_depressions_work_floats(self.resolution, self.count)
+        if self.work is None or self.work.Length != need:
+            if self.work is not None and self.work.IsCreated:
+                self.work.Dispose()
+            self.work = self.ctx.alloc(need)
+
+    @property
+    def depth(self):
+        """The lake-depth plane(s) of the last run, or None: without recordDepth, before the first payload and after
+        OnDestroy."""
+        return self._depth
+
+    def _status(self):
+        if self.work is None:
+            return None
+        self.jobHandle.Complete()
+        return self.ctx.wrap(self.work.ptr, 2, dtype=np.int32).ToArray()
+
+    @property
+    def passes(self):
+        """Passes of the last run that did work (the launches after them returned at once); None before the first run."""
+        s = self._status()
+        return None if s is None else int(s[0])
+
+    @property
+    def converged(self):
+        """Whether the last run reached the fixed point within maxPasses; None before the first run."""
+        s = self._status()
+        return None if s is None else bool(s[1])
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        self._size_work()
+        n = self.count * self.resolution * self.resolution
+        if not self.recordDepth and self._depth is not None:
+            self._depth.Dispose()
+            self._depth = None
+        if self.recordDepth and (self._depth is None or self._depth.Length != n):
+            if self._depth is not None:
+                self._depth.Dispose()
+            self._depth = self.ctx.alloc(n)
+        budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
+        desc = N.FillDesc(self.epsilon, self.seaLevel, budget, self._depth.ptr if self._depth is not None else None)
+        if d.write is not None:
+            self.jobHandle = _call_rw(self.ctx, "nz_fill_depressions_rw", d, self.work.ptr, C.byref(desc), dep=dependency)
+        elif isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_fill_depressions_batch", d.data.ptr, self.work.ptr, C.byref(desc),
+                                           d.resolution, d.count, dep=dependency)
+        else:
+            self.jobHandle = self.ctx.call("nz_fill_depressions", d.data.ptr, self.work.ptr, C.byref(desc), d.resolution,
+                                           dep=dependency)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
     def __init__(self, ctx, meshType=MeshType.SquareGridHeightMap):
         super().__init__(ctx)
