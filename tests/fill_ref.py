@@ -12,7 +12,8 @@ Three schedules that must give the same floats:
                                                       the kernel's schedule: per pass every tile of `tile` = (columns, rows)
                                                       cells sweeps against the frozen ring of the pass before, until a sweep
                                                       changes nothing or `sweeps` of them are done
-`passes` counts the passes that changed a cell."""
+`passes` counts the passes that changed a cell.  tiled(..., record=[]) appends one bool array per pass, the last one
+included: which tiles [tile row, tile column] changed a cell in it."""
 import heapq
 
 import numpy as np
@@ -54,7 +55,7 @@ def jacobi(h, epsilon=1e-4, seaLevel=SEA_OFF, maxPasses=None):
     return W, passes
 
 
-def tiled(h, epsilon=1e-4, seaLevel=SEA_OFF, tile=(64, 16), sweeps=None):
+def tiled(h, epsilon=1e-4, seaLevel=SEA_OFF, tile=(64, 16), sweeps=None, record=None):
     h = np.ascontiguousarray(h, f32)
     rows, cols = h.shape
     out, eps = outlets(h, seaLevel), f32(epsilon)
@@ -62,6 +63,7 @@ def tiled(h, epsilon=1e-4, seaLevel=SEA_OFF, tile=(64, 16), sweeps=None):
     tx, tz = tile
     while True:
         nxt = W.copy()
+        moved = np.zeros((-(-rows // tz), -(-cols // tx)), bool)
         for z0 in range(0, rows, tz):
             for x0 in range(0, cols, tx):
                 z1, x1 = min(z0 + tz, rows), min(x0 + tx, cols)
@@ -79,6 +81,9 @@ def tiled(h, epsilon=1e-4, seaLevel=SEA_OFF, tile=(64, 16), sweeps=None):
                         break
                     w, s = n, s + 1
                 nxt[z0:z1, x0:x1] = w[own]
+                moved[z0 // tz, x0 // tx] = s > 0
+        if record is not None:
+            record.append(moved)
         if same(nxt, W):
             return W, passes
         W, passes = nxt, passes + 1
