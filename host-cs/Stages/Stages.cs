@@ -379,6 +379,20 @@ namespace xshazwar.noize.hip {
             }
             jobHandle = Done(h);
         }
+        // The stage on one row stripe of a larger grid (nz_fluvial_stripe): `n` iterations with this stage's scalars in one call;
+        // the planes -- all of the stripe's shape -- are the caller's, and so is the exchange of 2 * n ghost rows before the call
+        // (Native.nz_halo_exchange on heightIn and, when given, drainageInRows; the maps once, before the first call).
+        // IntPtr.Zero for a map is an option left off; drainageInRows Zero: the start state.
+        public GpuJobHandle ScheduleStripe(IntPtr heightIn, IntPtr heightOut, IntPtr drainageOut, IntPtr stripeWork, ref NzStripe st,
+                                           int n, IntPtr drainageInRows, IntPtr rainMapRows, IntPtr hardnessRows, IntPtr upliftMapRows,
+                                           GpuJobHandle dependency) {
+            NzFluvialDesc desc = new NzFluvialDesc {
+                iterations = n, erodibility = erodibility, uplift = uplift, dt = dt, rain = rain, seaLevel = seaLevel,
+                rainMap = rainMapRows, hardness = hardnessRows, upliftMap = upliftMapRows, drainageIn = drainageInRows };
+            ulong h;
+            Native.Check(Native.nz_fluvial_stripe(ctx.Handle, heightIn, heightOut, drainageOut, stripeWork, ref st, ref desc, dependency.id, out h), "nz_fluvial_stripe");
+            return Done(h);
+        }
         public override void OnDestroy() { work?.Dispose(); work = null; }
     }
 
@@ -433,6 +447,25 @@ namespace xshazwar.noize.hip {
                 Native.Check(Native.nz_fill_depressions(ctx.Handle, d.data.Ptr, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_fill_depressions");
             }
             jobHandle = Done(h);
+        }
+        // The stage on one row stripe of a larger grid, one round (nz_fill_stripe): at most `passes` passes with this stage's
+        // epsilon and sea level over the owned rows, against one frozen ghost row of W on each side.  The planes and words are
+        // the caller's (stripeWork: Native.nz_fill_stripe_work_floats), and so are the exchange of one row before the call -- of
+        // heightRows before the round with `first`, of wRows before every later one -- and the vote after it
+        // (Native.nz_comm_allreduce_max_i32 on `changed`, which the next round takes as its `proceed`; IntPtr.Zero in the first).
+        public GpuJobHandle ScheduleStripe(IntPtr heightRows, IntPtr wRows, IntPtr stripeWork, ref NzStripe st, int passes, bool first,
+                                           IntPtr proceed, IntPtr changed, GpuJobHandle dependency) {
+            NzFillDesc desc = new NzFillDesc { epsilon = epsilon, seaLevel = seaLevel, maxPasses = passes, depth = IntPtr.Zero };
+            ulong h;
+            Native.Check(Native.nz_fill_stripe(ctx.Handle, heightRows, wRows, stripeWork, ref st, ref desc, first ? 1 : 0, proceed, changed, dependency.id, out h), "nz_fill_stripe");
+            return Done(h);
+        }
+        // ... and the end of the rounds (nz_fill_stripe_finalise): all or nothing on the owned rows by the device word
+        // `converged`, the verdict "the last vote was 0"; depthRows may be IntPtr.Zero.
+        public GpuJobHandle FinaliseStripe(IntPtr heightRows, IntPtr wRows, IntPtr depthRows, ref NzStripe st, IntPtr converged, GpuJobHandle dependency) {
+            ulong h;
+            Native.Check(Native.nz_fill_stripe_finalise(ctx.Handle, heightRows, wRows, depthRows, ref st, converged, dependency.id, out h), "nz_fill_stripe_finalise");
+            return Done(h);
         }
         public override void OnDestroy() { work?.Dispose(); work = null; lakes?.Dispose(); lakes = null; }
     }

@@ -788,6 +788,39 @@ int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const 
 int32_t nz_fluvial_erosion_batch(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
                                  int32_t count, nz_handle dep, nz_handle *out);
 
+/* The same model on a row stripe of a larger grid (nz_stripe; sharded runs and grids that are not square).  All planes --
+ * the heights, the drainage, the three maps and desc->drainageIn -- have the stripe's shape and pitch.  The result on the
+ * owned rows equals the monolithic model on the grows x cols grid bit for bit, heights and drainage both: outlets are the
+ * cells of the global border (global rows 0 and grows-1, columns 0 and cols-1) and the cells with h <= seaLevel, a
+ * neighbour outside the global grid does not exist, and a cut that is not the global border is not a border.
+ *   Launches.  desc->iterations = n >= 1 iterations of this call, one launch each.  An iteration reads the receivers of the
+ *     cells 1 row beyond the rows it produces, and so the heights 2 rows beyond them (nz_fluvial_stripe_halo_rows(n) = 2 * n
+ *     for the call).  Launch j (from 0) produces the owned rows widened by 2 * (n-1-j) rows on each side, clipped to the
+ *     global grid: the ghost rows the later launches need are recomputed, and the last launch produces exactly [own0, own1).
+ *   Ghost rows.  Every input plane must be valid up to 2 * n rows beyond the owned rows, or up to the global border
+ *     (checked against the buffer: too few rows in the buffer is NZ_ERR_INVALID).
+ *   desc->drainageIn == NULL: the drainage starts at rain_c, as in the tile entry.  Otherwise it is the drainage carried
+ *     over from the previous call (its drainage_out, once the ghost rows are exchanged).
+ *   After the call the owned rows of height_out and drainage_out hold the result.  Rows of the output planes inside the
+ *     first launch's widened window but not owned hold unspecified values; rows outside it, and the floats between cols and
+ *     pitch, are not written.
+ *   `work` = nz_fluvial_stripe_work_floats(st, n) floats: nothing for n == 1 (may be NULL), otherwise a second height and
+ *     drainage plane the launches ping-pong through.  The inputs are not modified.  No plane the call writes (height_out,
+ *     drainage_out, work) may overlap any other plane of the call; planes that are only read may alias.
+ *   The 16-byte path runs when every plane is 16-byte aligned and cols and the pitch are multiples of 4; the 4-byte path
+ *     otherwise.  Both give the same bits.
+ *   One stripe {cols, rows, 0, rows, 0, rows, 0} is the model on a rows x cols grid, square or not; on a square grid it
+ *     equals nz_fluvial_erosion bit for bit.  The owned rows of any split, with any number of iterations per call, equal the
+ *     monolithic grid.
+ * NZ_ERR_INVALID, the message naming the argument, and nothing written: the scalar ranges above; n < 1; a NULL desc or a
+ * NULL plane that is required; too few ghost rows; any overlap. */
+/* ghost rows on each side a call of `iterations` iterations reads beyond the owned rows: 2 * iterations */
+int32_t nz_fluvial_stripe_halo_rows(int32_t iterations);
+/* floats of `work`: 0 for one iteration, otherwise a second height and drainage plane of the stripe's shape */
+size_t nz_fluvial_stripe_work_floats(const nz_stripe *st, int32_t iterations);
+int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float *height_out, float *drainage_out, float *work,
+                          const nz_stripe *st, const nz_fluvial_desc *desc, nz_handle dep, nz_handle *out);
+
 /* ---- depression filling: lakes and pit-free drainage (new-framework feature) --------------------------------------------
  * Raises every closed hollow of a tile to its spill level (Planchon & Darboux 2001, "A fast, simple and versatile algorithm
  * to fill the depressions of digital elevation models"; Barnes et al. 2014, "Priority-flood"), so that the drainage network
@@ -844,6 +877,36 @@ int32_t nz_fill_depressions_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const
                                nz_handle *out);
 int32_t nz_fill_depressions_batch(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc, int32_t resolution,
                                   int32_t count, nz_handle dep, nz_handle *out);
+/* The same model on a row stripe of a larger grid (nz_stripe), one ROUND per call; the rounds of all stripes, with one row
+ * of W exchanged between them, go down to the monolithic fixed point bit for bit, because the operator is monotone and its
+ * fixed point does not depend on the order of updates.  All planes have the stripe's shape and pitch.
+ *   nz_fill_stripe runs at most desc->maxPasses passes of the pass kernel's scheme (64 x 16 tiles swept on chip, quiet tiles
+ *     skipped, early return once a pass changed nothing) over the owned rows.  The one ghost row of `w` on each side is
+ *     FROZEN: read, never written.  Outlets, and neighbours that do not exist, follow the global grid (global rows 0 and
+ *     grows-1, columns 0 and cols-1; h <= seaLevel); a cut is no border.  Rows of the buffers beyond the one ghost row are
+ *     neither read nor written, nor are the floats between cols and pitch.
+ *   first != 0: the start state is derived from `height` on the owned rows and the ghost rows (outlets take h, every other
+ *     cell +inf); `height` needs one valid ghost row and `w` is not read.  Otherwise the current W is read from `w`, whose
+ *     ghost rows the caller has exchanged.
+ *   On return the owned rows of `w` hold the stripe's W.  `changed` (device) receives 1 with `first`, 1 if any owned cell of
+ *     `w` differs from its value at entry (a budget that ran out before rest included), otherwise 0.
+ *   proceed (device, may be NULL): a word of zero makes every launch of the call return at once -- `w` untouched, `changed`
+ *     0 -- so that a host can enqueue a fixed budget of rounds without reading anything back.
+ *   desc->depth is not used.  `work` = nz_fill_stripe_work_floats(st) floats: status words, tile bytes, a second W plane.
+ *   nz_fill_stripe_finalise, on the owned rows: where *converged != 0, height = w and depth = w - h; otherwise height stays
+ *     and depth = 0 -- all or nothing, no +inf ever reaches the caller.  `converged` is the caller's verdict: the vote over
+ *     all ranks after the last round was 0 (nz_comm_allreduce_max_i32).
+ *   One stripe over a square grid with `first`, followed by finalise with a word of 1, equals nz_fill_depressions bit for
+ *     bit, depth included, provided the budget suffices.
+ * NZ_ERR_INVALID, the message naming the argument, and nothing written: epsilon or seaLevel not finite; epsilon < 0;
+ * maxPasses < 1; a NULL desc, plane or word; a missing ghost row; height, w and work (finalise: height, w, depth)
+ * overlapping each other or the words. */
+int32_t nz_fill_stripe_halo_rows(void); /* 1 */
+size_t nz_fill_stripe_work_floats(const nz_stripe *st);
+int32_t nz_fill_stripe(nz_ctx *ctx, const float *height, float *w, float *work, const nz_stripe *st, const nz_fill_desc *desc,
+                       int32_t first, const int32_t *proceed, int32_t *changed, nz_handle dep, nz_handle *out);
+int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const float *w, float *depth, const nz_stripe *st,
+                                const int32_t *converged, nz_handle dep, nz_handle *out);
 /* Test hook: the cap on a pass's on-chip sweeps per tile (process-wide; <= 0 restores the default, 16).  Results must not
  * change: the fixed point does not depend on the schedule.  Returns the cap that was in force.  Atomic: it may be called
  * while entries run on other threads; a call that has begun keeps the cap it read. */
@@ -908,6 +971,10 @@ int32_t nz_halo_exchange(nz_ctx *ctx, nz_comm *comm, float *const *planes, int32
  * extreme.  The path's one collective.  comm == NULL: one rank. */
 int32_t nz_comm_allgather_range(nz_ctx *ctx, nz_comm *comm, const float *map, size_t n_floats, float *res, float lim_min,
                                 float lim_max, nz_handle dep, nz_handle *out);
+/* In-place maximum of `n` int32 words (device) over the ranks: ncclAllReduce(ncclMax, ncclInt32), stream-ordered like
+ * nz_comm_allgather_range.  The vote of the sharded depression fill: "did any rank change in this round".  comm NULL: one
+ * rank, the words stay. */
+int32_t nz_comm_allreduce_max_i32(nz_ctx *ctx, nz_comm *comm, int32_t *words, int32_t n, nz_handle dep, nz_handle *out);
 
 /* The stock stage list (nz_terrain_params) on a grows x cols grid cut into `stripes` row stripes over all ranks; rank r
  * holds stripes [r * S, (r + 1) * S), S = stripes / world.  The object owns the stripes' planes and the launch plan,

@@ -191,10 +191,17 @@ SIGNATURES = {
     "nz_fluvial_erosion": (_i, [ctx_p, dev_ptr, dev_ptr, fd_p, _i] + _tail),
     "nz_fluvial_erosion_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, fd_p] + _tail),
     "nz_fluvial_erosion_batch": (_i, [ctx_p, dev_ptr, dev_ptr, fd_p, _i, _i] + _tail),
+    "nz_fluvial_stripe_halo_rows": (_i, [_i]),
+    "nz_fluvial_stripe_work_floats": (_sz, [stripe_p, _i]),
+    "nz_fluvial_stripe": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, stripe_p, fd_p] + _tail),
     "nz_fill_depressions_work_floats": (_sz, [_i, _i]),
     "nz_fill_depressions": (_i, [ctx_p, dev_ptr, dev_ptr, fill_p, _i] + _tail),
     "nz_fill_depressions_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, fill_p] + _tail),
     "nz_fill_depressions_batch": (_i, [ctx_p, dev_ptr, dev_ptr, fill_p, _i, _i] + _tail),
+    "nz_fill_stripe_halo_rows": (_i, []),
+    "nz_fill_stripe_work_floats": (_sz, [stripe_p]),
+    "nz_fill_stripe": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, fill_p, _i, dev_ptr, dev_ptr] + _tail),
+    "nz_fill_stripe_finalise": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, dev_ptr] + _tail),
     "nz_debug_fill_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
@@ -260,6 +267,7 @@ SIGNATURES = {
     "nz_halo_exchange_begin": (_i, [ctx_p, C.c_void_p, C.POINTER(dev_ptr), _i, stripe_p, _i, _i, handle_t]),
     "nz_halo_exchange_finish": (_i, [ctx_p, C.c_void_p, handle_p]),
     "nz_halo_exchange": (_i, [ctx_p, C.c_void_p, C.POINTER(dev_ptr), _i, stripe_p, _i, _i] + _tail),
+    "nz_comm_allreduce_max_i32": (_i, [ctx_p, C.c_void_p, dev_ptr, _i] + _tail),
     "nz_comm_allgather_range": (_i, [ctx_p, C.c_void_p, dev_ptr, _sz, dev_ptr, _f, _f] + _tail),
     "nz_sharded_create": (_i, [ctx_p, C.c_void_p, sd_p, tp_p, C.POINTER(C.c_void_p)]),
     "nz_sharded_destroy": (_i, [C.c_void_p]),

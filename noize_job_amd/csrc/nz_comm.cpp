@@ -29,6 +29,7 @@ struct rccl_api {
     decltype(&ncclSend) Send = nullptr;
     decltype(&ncclRecv) Recv = nullptr;
     decltype(&ncclAllGather) AllGather = nullptr;
+    decltype(&ncclAllReduce) AllReduce = nullptr;
     decltype(&ncclGetErrorString) GetErrorString = nullptr;
     decltype(&ncclGetVersion) GetVersion = nullptr;
 };
@@ -72,6 +73,7 @@ int32_t rccl_load(const rccl_api **out) {
         NZ_SYM(Send, "ncclSend")
         NZ_SYM(Recv, "ncclRecv")
         NZ_SYM(AllGather, "ncclAllGather")
+        NZ_SYM(AllReduce, "ncclAllReduce")
         NZ_SYM(GetErrorString, "ncclGetErrorString")
         NZ_SYM(GetVersion, "ncclGetVersion")
 #undef NZ_SYM
@@ -343,6 +345,17 @@ extern "C" int32_t nz_comm_allgather_range(nz_ctx *ctx, nz_comm *comm, const flo
     float *triple = scratch + part, *work = triple + 3;
     NZ_TRY(nz_launch_map_range(ctx->stream, map, n_floats, __builtin_inff(), -__builtin_inff(), triple, scratch));
     NZ_TRY(gather_and_fold(ctx, comm, triple, 1, work, res, lim_min, lim_max));
+    return nz_ctx_finish(ctx, out);
+}
+
+// the vote of a sharded fixed-point iteration ("did any rank change in this round"): the maximum over the ranks, in place
+extern "C" int32_t nz_comm_allreduce_max_i32(nz_ctx *ctx, nz_comm *comm, int32_t *words, int32_t n, nz_handle dep,
+                                             nz_handle *out) {
+    NZ_TRY(nz_ctx_begin(ctx, dep));
+    NZ_REQUIRE(words, "words is NULL");
+    NZ_REQUIRE(n >= 1, "n %d < 1", n);
+    NZ_REQUIRE(!comm || comm->ctx == ctx, "the communicator belongs to another context");
+    if (comm) NZ_NCCL(comm->api, comm->api->AllReduce(words, words, (size_t)n, ncclInt32, ncclMax, comm->comm, ctx->stream));
     return nz_ctx_finish(ctx, out);
 }
 

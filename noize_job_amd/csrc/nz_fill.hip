@@ -34,6 +34,15 @@
 // The finalise launch looks at the word of the last pass that ran: zero -> W to the heights and W - h to the depth plane;
 // otherwise the heights stay and the depth is zero: all or nothing, a caller never sees +inf.
 //
+// WIN, the stripe form (nz_fill_stripe): one ROUND on the owned rows [r0, r1) of a stripe-shaped buffer with a pitch; the
+// workgroups tile the owned rows, the grid's bounds are the global grid's seen from the buffer.  The one row of W on each
+// side of the owned rows is FROZEN: read from the caller's plane in every pass (or, in a round that starts from the
+// heights, derived from them), never written, whichever of the two planes the pass alternates between.  When the owned
+// rows end inside a tile, the frozen row lies in a thread's own slot: it is loaded, marked fixed and not stored.  status[GO]
+// (written by fill_round_begin from the caller's `proceed` word) lets every launch of the round return at once; pass 0 of
+// a round that continues from W has no tile bytes to go by, so all of its tiles are live.  A pass 0 that moves a cell
+// stores 1 to the caller's `changed` word: W only ever falls, so a moved cell differs from its value at entry for good.
+//
 // The cap, `sweeps`, is 16 (nz_stages.cpp): enough to carry a value across the tile's 16 rows and 64 columns.  4 to 64 were
 // measured: DESIGN.md section 4, "depression filling".
 #include "nz_internal.hpp"
@@ -46,6 +55,19 @@ constexpr int LP = 72;           // LDS row pitch in cells; plane column x0 + i 
 constexpr int LC = 4;            // keeps a thread's four cells 16-byte aligned in LDS
 constexpr int NRING = 2 * (FX + 2) + 2 * FZ;  // cells at radius 1 around the tile
 constexpr int ST_PASSES = 0, ST_CONVERGED = 1, ST_CHANGED = 2;  // the status words: changed[3] from ST_CHANGED on
+constexpr int ST_GO = 5;                                          // stripe rounds: 0 = every launch returns at once
+
+// the plane a pass works on: tiles of res^2 cells back to back (pitch = res, the rest derived), or -- WIN -- the owned rows
+// of one stripe-shaped buffer, rows in buffer coordinates
+struct fill_win {
+    int pitch;           // floats between rows; without WIN the tile's resolution
+    int xhi;             // last column of the grid
+    int zlo, zhi;        // first and last row of the global grid
+    int r0, r1;          // owned rows [r0, r1)
+    int ghost_from_h;    // the frozen rows are the start state derived from h (a round with `first`), else w_ghost's
+    const float *w_ghost;  // the caller's W plane
+    int *changed_out;    // the caller's word
+};
 
 // the ring at radius 1 of the tile, cell i of NRING: its LDS row and column
 __device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {
@@ -60,18 +82,22 @@ __device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {
     }
 }
 
-template <bool FIRST, bool VEC>
+template <bool FIRST, bool VEC, bool WIN>
 __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__ h, const float *__restrict__ w_in,
                                                        float *__restrict__ w_out, int *status,
                                                        const unsigned char *__restrict__ flags_in,
-                                                       unsigned char *__restrict__ flags_out, float eps, float sea, int res,
-                                                       int pass, int sweeps) {
+                                                       unsigned char *__restrict__ flags_out, float eps, float sea,
+                                                       fill_win win, int pass, int sweeps) {
     __shared__ __attribute__((aligned(16))) float W[(FZ + 2) * LP];  // radius 1: LDS row = plane row - z0 + 1
     const int tid = threadIdx.x;
     int *changed = status + ST_CHANGED;
 
+    if constexpr (WIN) {
+        if (!status[ST_GO]) return;
+    }
+    const bool all_live = WIN && pass == 0;  // a round's first pass: nothing is known about the pass before
     // ---- did the pass before change anything at all? ----
-    const int prev = FIRST ? 1 : changed[(pass + 2) % 3];
+    const int prev = FIRST || all_live ? 1 : changed[(pass + 2) % 3];
     if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
         changed[(pass + 1) % 3] = 0;
         if (FIRST) changed[0] = 1;  // by decree; no workgroup bumps it
@@ -83,7 +109,7 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
     const int tnx = gridDim.x, tnz = gridDim.y;
     const size_t tile0 = (size_t)blockIdx.z * tnx * tnz;
     const size_t me = tile0 + (size_t)blockIdx.y * tnx + blockIdx.x;
-    if (!FIRST) {
+    if (!FIRST && !all_live) {
         int live = 0;
         if (tid < 9) {
             const int bx = (int)blockIdx.x + tid % 3 - 1, bz = (int)blockIdx.y + tid / 3 - 1;
@@ -95,19 +121,29 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
         }
     }
 
-    const int x0 = blockIdx.x * FX, z0 = blockIdx.y * FZ;
-    const size_t base = (size_t)blockIdx.z * res * res;
-    const int hi = res - 1;
-    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= 0 && pz <= hi; };
-    auto on_border = [&](int px, int pz) { return px == 0 || px == hi || pz == 0 || pz == hi; };
+    const int res = win.pitch;  // (the pitch; without WIN the resolution)
+    const int x0 = blockIdx.x * FX, z0 = (WIN ? win.r0 : 0) + blockIdx.y * FZ;
+    const size_t base = WIN ? 0 : (size_t)blockIdx.z * res * res;
+    const int hi = WIN ? win.xhi : res - 1;                                   // last column
+    const int zlo = WIN ? win.zlo : 0, zhi = WIN ? win.zhi : res - 1;         // the grid's rows
+    const int rlo = WIN ? (zlo > win.r0 - 1 ? zlo : win.r0 - 1) : 0, rhi = WIN ? (zhi < win.r1 ? zhi : win.r1) : hi;  // rows read
+    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= rlo && pz <= rhi; };
+    auto on_border = [&](int px, int pz) { return px == 0 || px == hi || pz == zlo || pz == zhi; };
     const float INF = __builtin_inff();
+    // WIN: W of a cell of a frozen row
+    auto ghost = [&](int qx, int qz) {
+        const size_t q = (size_t)qz * res + qx;
+        if (!win.ghost_from_h) return win.w_ghost[q];
+        const float hq = h[q];
+        return on_border(qx, qz) || hq <= sea ? hq : INF;
+    };
 
     // this thread's four cells
     const int tz = tid >> 4, tx = (tid & 15) * 4;
     const int px = x0 + tx, pz = z0 + tz;
     const size_t c0 = base + (size_t)pz * res + px;
-    const bool row_in = pz <= hi;
-    const bool quad = VEC && row_in && px + 3 <= hi;  // VEC: res % 4 == 0, so a quad lies inside or outside as a whole
+    const bool row_in = WIN ? pz < win.r1 : pz <= hi;
+    const bool quad = VEC && row_in && px + 3 <= hi;  // VEC: cols % 4 == 0, so a quad lies inside or outside as a whole
 
     // ---- fill ----
     float hc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, wc[4] = {INF, INF, INF, INF};
@@ -134,6 +170,13 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
         if (!in || outlet) fixed |= 1u << j;
         if (FIRST && outlet) wc[j] = hc[j];
     }
+    if constexpr (WIN) {
+        if (pz == win.r1 && pz <= zhi) {  // the frozen row below, inside the tile: fixed (row_in is false), and not stored
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (px + j <= hi) wc[j] = ghost(px + j, pz);
+        }
+    }
     *reinterpret_cast<float4 *>(&W[(tz + 1) * LP + LC + tx]) = make_float4(wc[0], wc[1], wc[2], wc[3]);
     if (tid < NRING) {
         int lz, lx;
@@ -142,7 +185,9 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
         float v = INF;
         if (inside(qx, qz)) {
             const size_t q = base + (size_t)qz * res + qx;
-            if constexpr (FIRST) {
+            if (WIN && (qz < win.r0 || qz >= win.r1)) {
+                v = ghost(qx, qz);
+            } else if constexpr (FIRST) {
                 const float hq = h[q];
                 if (on_border(qx, qz) || hq <= sea) v = hq;
             } else {
@@ -200,6 +245,43 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
     if (tid == 0) {
         flags_out[me] = moved ? 1 : 0;
         if (!FIRST && moved) atomicAdd(&changed[pass % 3], 1);
+        if (WIN && !FIRST && pass == 0 && moved) *win.changed_out = 1;
+    }
+}
+
+// a stripe round begins: go = the caller's proceed word (none: go), the status words of a fresh series, the caller's
+// `changed` word = go && first
+__global__ void fill_round_begin_kernel(int *status, const int *proceed, int *changed_out, int first) {
+    const int go = proceed ? *proceed != 0 : 1;
+    status[ST_GO] = go;
+    status[ST_PASSES] = 0;
+    status[ST_CHANGED] = status[ST_CHANGED + 1] = status[ST_CHANGED + 2] = 0;
+    *changed_out = go && first ? 1 : 0;
+}
+
+// a stripe round of an odd number of passes ends in the work plane: when every pass ran, its owned rows go to the caller's
+// plane (a round that came to rest earlier holds equal cells in both)
+__global__ __launch_bounds__(256) void fill_round_end_kernel(float *__restrict__ w, const float *__restrict__ w_work,
+                                                             const int *status, int passes, int pitch, int cols, int r0,
+                                                             int r1) {
+    if (!status[ST_GO] || status[ST_PASSES] != passes) return;
+    const int x = blockIdx.x * 256 + threadIdx.x, z = r0 + blockIdx.y;
+    if (x < cols && z < r1) w[(size_t)z * pitch + x] = w_work[(size_t)z * pitch + x];
+}
+
+// the stripe's all or nothing on the owned rows, by the caller's verdict
+__global__ __launch_bounds__(256) void fill_stripe_finalise_kernel(float *__restrict__ h, const float *__restrict__ w,
+                                                                   float *__restrict__ depth, const int *converged, int pitch,
+                                                                   int cols, int r0, int r1) {
+    const int x = blockIdx.x * 256 + threadIdx.x, z = r0 + blockIdx.y;
+    if (x >= cols || z >= r1) return;
+    const size_t i = (size_t)z * pitch + x;
+    if (*converged) {
+        const float hv = h[i], wv = w[i];
+        h[i] = wv;
+        if (depth) depth[i] = wv - hv;
+    } else if (depth) {
+        depth[i] = 0.0f;
     }
 }
 
@@ -229,13 +311,56 @@ int32_t nz_launch_fill_pass(hipStream_t s, const float *h, const float *w_in, fl
     const dim3 grid((res + FX - 1) / FX, (res + FZ - 1) / FZ, count);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w_in) | reinterpret_cast<uintptr_t>(w_out);
     const bool vec = (bits & 15) == 0 && res % 4 == 0;  // a row, and with it a tile of the batch, starts 16-byte aligned
+    const fill_win win{res, res - 1, 0, res - 1, 0, res, 0, nullptr, nullptr};
     if (pass == 0) {
-        if (vec) NZ_LAUNCH((fill_pass_kernel<true, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, res, pass, sweeps);
-        else NZ_LAUNCH((fill_pass_kernel<true, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, res, pass, sweeps);
+        if (vec) NZ_LAUNCH((fill_pass_kernel<true, true, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+        else NZ_LAUNCH((fill_pass_kernel<true, false, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
     } else {
-        if (vec) NZ_LAUNCH((fill_pass_kernel<false, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, res, pass, sweeps);
-        else NZ_LAUNCH((fill_pass_kernel<false, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, res, pass, sweeps);
+        if (vec) NZ_LAUNCH((fill_pass_kernel<false, true, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+        else NZ_LAUNCH((fill_pass_kernel<false, false, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
     }
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_fill_round_begin(hipStream_t s, int *status, const int *proceed, int *changed, int first) {
+    NZ_LAUNCH(fill_round_begin_kernel, dim3(1), dim3(1), 0, s, status, proceed, changed, first);
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_fill_stripe_pass(hipStream_t s, const float *h, const float *w_in, float *w_out, const float *w_ghost,
+                                   int *status, const unsigned char *flags_in, unsigned char *flags_out, int *changed,
+                                   float eps, float sea, const nz_geom &g, int zlo, int zhi, int first, int pass, int sweeps) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    const dim3 grid((g.cols + FX - 1) / FX, (g.or1 - g.or0 + FZ - 1) / FZ, 1);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w_in) | reinterpret_cast<uintptr_t>(w_out);
+    const bool vec = (bits & 15) == 0 && g.cols % 4 == 0 && g.pitch % 4 == 0;  // every row starts 16-byte aligned
+    const fill_win win{g.pitch, g.cols - 1, zlo, zhi, g.or0, g.or1, first, w_ghost, changed};
+    if (first && pass == 0) {
+        if (vec) NZ_LAUNCH((fill_pass_kernel<true, true, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+        else NZ_LAUNCH((fill_pass_kernel<true, false, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+    } else {
+        if (vec) NZ_LAUNCH((fill_pass_kernel<false, true, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+        else NZ_LAUNCH((fill_pass_kernel<false, false, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+    }
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_fill_round_end(hipStream_t s, float *w, const float *w_work, const int *status, int passes, const nz_geom &g) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    NZ_LAUNCH(fill_round_end_kernel, dim3((g.cols + 255) / 256, g.or1 - g.or0), dim3(256), 0, s, w, w_work, status, passes,
+              g.pitch, g.cols, g.or0, g.or1);
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_fill_stripe_finalise(hipStream_t s, float *h, const float *w, float *depth, const int *converged,
+                                       const nz_geom &g) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    NZ_LAUNCH(fill_stripe_finalise_kernel, dim3((g.cols + 255) / 256, g.or1 - g.or0), dim3(256), 0, s, h, w, depth, converged,
+              g.pitch, g.cols, g.or0, g.or1);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

@@ -17,7 +17,11 @@
 // "Outside the grid" never enters the arithmetic as a value: a border cell is an outlet and has no receiver, every other
 // cell has all eight neighbours, and a ring cell outside the grid carries the code NONE so that nothing is gathered from
 // it.  Every test is one on the cell's position (px, pz) against the grid's bounds [0, xhi] x [zlo, zhi], so a row stripe of
-// a larger grid is this kernel on a window.
+// a larger grid is this kernel on a window: WIN.  There the plane is one stripe-shaped buffer with a pitch, the bounds are
+// the global grid's seen from the buffer (they may lie outside it), the workgroups tile the rows [r0, r1) the launch produces
+// and a row is read when it lies within 2 rows of them and inside the grid -- the ghost rows the entry has checked for.  A
+// row of the tile at or beyond r1 is read, since the rows above it need its receivers, but not produced.  Without WIN the
+// window is the tile itself and the instantiations are what they were.
 //
 // CONSTA: the drainage read is the constant `rain` everywhere (the start state without rain map and drainageIn) and no
 // drainage plane is read or staged.  MAPS: the three read-only maps travel as a trailing argument, each read at the cell
@@ -36,6 +40,15 @@ constexpr int NRING = 2 * (FX + 2) + 2 * FZ;  // cells at radius 1 around the ti
 constexpr int NHALO2 = 4 * (FX + 4) + 4 * FZ;  // cells at radius 1 and 2 around the tile
 constexpr unsigned NONE = 8;     // receiver code of a cell without one
 constexpr float DIAG = 0x1.6a09e6p-1f;  // 0.70710678f, bits 0x3F3504F3
+
+// the plane a launch works on: tiles of res^2 cells back to back (pitch = res, everything else derived), or -- WIN -- a
+// window of one stripe-shaped buffer, rows in buffer coordinates
+struct fluvial_win {
+    int pitch;     // floats between rows; without WIN the tile's resolution
+    int xhi;       // last column of the grid
+    int zlo, zhi;  // first and last row of the global grid
+    int r0, r1;    // rows produced [r0, r1)
+};
 
 struct fluvial_maps {
     const float *rain_map, *hardness, *uplift_map;
@@ -76,10 +89,10 @@ __device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {
     }
 }
 
-template <bool CONSTA, bool MAPS, bool VEC, class... M>
+template <bool CONSTA, bool MAPS, bool VEC, bool WIN, class... M>
 __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h_in, float *__restrict__ h_out,
                                                      const float *__restrict__ a_in, float *__restrict__ a_out,
-                                                     nz_fluvial_params k, int res, M... ms) {
+                                                     nz_fluvial_params k, fluvial_win win, M... ms) {
     static_assert(sizeof...(M) == (MAPS ? 1 : 0), "the maps travel with MAPS only");
     const fluvial_maps m = maps_of(ms...);
     __shared__ __attribute__((aligned(16))) float H[(FZ + 4) * LP];            // radius 2: LDS row = plane row - z0 + 2
@@ -88,19 +101,25 @@ __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h
     unsigned char *RC = reinterpret_cast<unsigned char *>(RW);
 
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * FX, z0 = blockIdx.y * FZ;
-    const size_t base = (size_t)blockIdx.z * res * res;
-    const int pitch = res;
-    const int xhi = res - 1, zlo = 0, zhi = res - 1;  // the grid's bounds
-    auto inside = [&](int px, int pz) { return px >= 0 && px <= xhi && pz >= zlo && pz <= zhi; };
+    const int pitch = win.pitch;
+    const int x0 = blockIdx.x * FX, z0 = (WIN ? win.r0 : 0) + blockIdx.y * FZ;
+    const size_t base = WIN ? 0 : (size_t)blockIdx.z * pitch * pitch;
+    const int xhi = WIN ? win.xhi : pitch - 1, zlo = WIN ? win.zlo : 0, zhi = WIN ? win.zhi : pitch - 1;  // the grid's bounds
+    // the rows that are read: the grid's, WIN: no further than 2 rows from the rows produced
+    const int rlo = WIN ? (zlo > win.r0 - 2 ? zlo : win.r0 - 2) : zlo, rhi = WIN ? (zhi < win.r1 + 1 ? zhi : win.r1 + 1) : zhi;
+    auto inside = [&](int px, int pz) { return px >= 0 && px <= xhi && pz >= rlo && pz <= rhi; };
     auto on_border = [&](int px, int pz) { return px == 0 || px == xhi || pz == zlo || pz == zhi; };
+    // WIN without a drainage plane, with a rain map: the start state rain * rainMap[c], formed where it is read
+    const bool a_start = WIN && MAPS && !CONSTA && a_in == nullptr;
+    auto drain = [&](size_t q) { return a_start ? k.rain * m.rain_map[q] : a_in[q]; };
 
     // this thread's four cells
     const int tz = tid >> 4, tx = (tid & 15) * 4;
     const int px = x0 + tx, pz = z0 + tz;
     const size_t c0 = base + (size_t)pz * pitch + px;
-    const bool row_in = pz <= zhi;
-    const bool quad = VEC && row_in && px + 3 <= xhi;  // VEC: res % 4 == 0, so a quad lies inside or outside as a whole
+    const bool row_in = pz <= rhi;                    // read
+    const bool row_out = WIN ? pz < win.r1 : row_in;  // and produced
+    const bool quad = VEC && row_in && px + 3 <= xhi;  // VEC: cols % 4 == 0, so a quad lies inside or outside as a whole
 
     // ---- fill ----
     float hc[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ac[4] = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -108,15 +127,20 @@ __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h
         const float4 v = *reinterpret_cast<const float4 *>(h_in + c0);
         hc[0] = v.x, hc[1] = v.y, hc[2] = v.z, hc[3] = v.w;
         if constexpr (!CONSTA) {
-            const float4 a = *reinterpret_cast<const float4 *>(a_in + c0);
-            ac[0] = a.x, ac[1] = a.y, ac[2] = a.z, ac[3] = a.w;
+            if (a_start) {
+                const float4 a = *reinterpret_cast<const float4 *>(m.rain_map + c0);
+                ac[0] = k.rain * a.x, ac[1] = k.rain * a.y, ac[2] = k.rain * a.z, ac[3] = k.rain * a.w;
+            } else {
+                const float4 a = *reinterpret_cast<const float4 *>(a_in + c0);
+                ac[0] = a.x, ac[1] = a.y, ac[2] = a.z, ac[3] = a.w;
+            }
         }
     } else if (!VEC && row_in) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             if (px + j > xhi) break;
             hc[j] = h_in[c0 + j];
-            if constexpr (!CONSTA) ac[j] = a_in[c0 + j];
+            if constexpr (!CONSTA) ac[j] = drain(c0 + j);
         }
     }
     *reinterpret_cast<float4 *>(&H[(tz + 2) * LP + LC + tx]) = make_float4(hc[0], hc[1], hc[2], hc[3]);
@@ -140,7 +164,7 @@ __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h
             int lz, lx;
             ring_cell(i, lz, lx);
             const int qx = x0 + lx - LC, qz = z0 + lz - 1;
-            A[lz * LP + lx] = inside(qx, qz) ? a_in[base + (size_t)qz * pitch + qx] : 0.0f;
+            A[lz * LP + lx] = inside(qx, qz) ? drain(base + (size_t)qz * pitch + qx) : 0.0f;
         }
     }
     __syncthreads();
@@ -188,7 +212,7 @@ __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h
     __syncthreads();
 
     // ---- steps 2 and 3 on the own cells ----
-    if (!row_in || px > xhi) return;
+    if (!row_out || px > xhi) return;
     unsigned cw[3][6];  // the receiver codes of the window
     float aw[3][6];     // its drainage
 #pragma unroll
@@ -268,15 +292,30 @@ __global__ __launch_bounds__(256) void fluvial_start_kernel(float *__restrict__ 
     if (i < n) a[i] = rain * rain_map[i];
 }
 
-template <bool CONSTA, bool MAPS>
+template <bool CONSTA, bool MAPS, bool WIN>
 void launch(bool vec, dim3 grid, hipStream_t s, const float *h_in, float *h_out, const float *a_in, float *a_out,
-            const nz_fluvial_params &k, int res, const fluvial_maps &m) {
+            const nz_fluvial_params &k, const fluvial_win &w, const fluvial_maps &m) {
     if constexpr (MAPS) {
-        if (vec) NZ_LAUNCH((fluvial_kernel<CONSTA, true, true, fluvial_maps>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, res, m);
-        else NZ_LAUNCH((fluvial_kernel<CONSTA, true, false, fluvial_maps>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, res, m);
+        if (vec) NZ_LAUNCH((fluvial_kernel<CONSTA, true, true, WIN, fluvial_maps>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, w, m);
+        else NZ_LAUNCH((fluvial_kernel<CONSTA, true, false, WIN, fluvial_maps>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, w, m);
     } else {
-        if (vec) NZ_LAUNCH((fluvial_kernel<CONSTA, false, true>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, res);
-        else NZ_LAUNCH((fluvial_kernel<CONSTA, false, false>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, res);
+        if (vec) NZ_LAUNCH((fluvial_kernel<CONSTA, false, true, WIN>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, w);
+        else NZ_LAUNCH((fluvial_kernel<CONSTA, false, false, WIN>), grid, dim3(FT), 0, s, h_in, h_out, a_in, a_out, k, w);
+    }
+}
+
+// the form by the planes given: no drainage plane and no rain map is CONSTA; no drainage plane with a rain map is, WIN, the
+// start state formed in the kernel (the tile entry writes it to a plane first, nz_stages.cpp)
+template <bool WIN>
+void dispatch(bool vec, dim3 grid, hipStream_t s, const float *h_in, float *h_out, const float *a_in, float *a_out,
+              const nz_fluvial_params &k, const fluvial_win &w, const fluvial_maps &m) {
+    const bool maps = m.rain_map || m.hardness || m.uplift_map;
+    if (!a_in && !(WIN && m.rain_map)) {
+        if (maps) launch<true, true, WIN>(vec, grid, s, h_in, h_out, a_in, a_out, k, w, m);
+        else launch<true, false, WIN>(vec, grid, s, h_in, h_out, a_in, a_out, k, w, m);
+    } else {
+        if (maps) launch<false, true, WIN>(vec, grid, s, h_in, h_out, a_in, a_out, k, w, m);
+        else launch<false, false, WIN>(vec, grid, s, h_in, h_out, a_in, a_out, k, w, m);
     }
 }
 
@@ -295,19 +334,28 @@ int32_t nz_launch_fluvial(hipStream_t s, const float *h_in, float *h_out, const 
     if (res <= 0 || count <= 0) return NZ_OK;
     const dim3 grid((res + FX - 1) / FX, (res + FZ - 1) / FZ, count);
     const fluvial_maps m{rain_map, hardness, uplift_map};
-    const bool maps = rain_map || hardness || uplift_map;
     uintptr_t bits = reinterpret_cast<uintptr_t>(h_in) | reinterpret_cast<uintptr_t>(h_out) |
                      reinterpret_cast<uintptr_t>(a_in) | reinterpret_cast<uintptr_t>(a_out) |
                      reinterpret_cast<uintptr_t>(rain_map) | reinterpret_cast<uintptr_t>(hardness) |
                      reinterpret_cast<uintptr_t>(uplift_map);
     const bool vec = (bits & 15) == 0 && res % 4 == 0;  // a row, and with it a tile of the batch, starts 16-byte aligned
-    if (!a_in) {
-        if (maps) launch<true, true>(vec, grid, s, h_in, h_out, a_in, a_out, k, res, m);
-        else launch<true, false>(vec, grid, s, h_in, h_out, a_in, a_out, k, res, m);
-    } else {
-        if (maps) launch<false, true>(vec, grid, s, h_in, h_out, a_in, a_out, k, res, m);
-        else launch<false, false>(vec, grid, s, h_in, h_out, a_in, a_out, k, res, m);
-    }
+    dispatch<false>(vec, grid, s, h_in, h_out, a_in, a_out, k, fluvial_win{res, res - 1, 0, res - 1, 0, res}, m);
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_fluvial_stripe(hipStream_t s, const float *h_in, float *h_out, const float *a_in, float *a_out,
+                                 const nz_fluvial_params &k, const nz_geom &g, int zlo, int zhi, const float *rain_map,
+                                 const float *hardness, const float *uplift_map) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    const dim3 grid((g.cols + FX - 1) / FX, (g.or1 - g.or0 + FZ - 1) / FZ, 1);
+    const fluvial_maps m{rain_map, hardness, uplift_map};
+    uintptr_t bits = reinterpret_cast<uintptr_t>(h_in) | reinterpret_cast<uintptr_t>(h_out) |
+                     reinterpret_cast<uintptr_t>(a_in) | reinterpret_cast<uintptr_t>(a_out) |
+                     reinterpret_cast<uintptr_t>(rain_map) | reinterpret_cast<uintptr_t>(hardness) |
+                     reinterpret_cast<uintptr_t>(uplift_map);
+    const bool vec = (bits & 15) == 0 && g.cols % 4 == 0 && g.pitch % 4 == 0;  // every row starts 16-byte aligned
+    dispatch<true>(vec, grid, s, h_in, h_out, a_in, a_out, k, fluvial_win{g.pitch, g.cols - 1, zlo, zhi, g.or0, g.or1}, m);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

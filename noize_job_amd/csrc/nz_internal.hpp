@@ -346,6 +346,13 @@ struct nz_fluvial_params {
 int32_t nz_launch_fluvial(hipStream_t s, const float *h_in, float *h_out, const float *a_in, float *a_out,
                           const nz_fluvial_params &k, int res, int count, const float *rain_map, const float *hardness,
                           const float *uplift_map);
+// the stripe form: one iteration on rows [g.or0, g.or1) of one stripe-shaped plane set (g: nz_geom_from_stripe with the
+// launch's window as its produced rows); [zlo, zhi] are the first and last row of the global grid in buffer rows, which may
+// lie outside the buffer.  Reads reach 2 rows beyond the window, never beyond the grid.  a_in NULL with a rain map: the
+// start state rain * rain_map is formed in the kernel
+int32_t nz_launch_fluvial_stripe(hipStream_t s, const float *h_in, float *h_out, const float *a_in, float *a_out,
+                                 const nz_fluvial_params &k, const nz_geom &g, int zlo, int zhi, const float *rain_map,
+                                 const float *hardness, const float *uplift_map);
 // the start state with a rain map: a[i] = rain * rain_map[i]
 int32_t nz_launch_fluvial_start(hipStream_t s, float *a, const float *rain_map, float rain, size_t n);
 
@@ -357,6 +364,17 @@ int32_t nz_launch_fill_pass(hipStream_t s, const float *h, const float *w_in, fl
                             int pass, int sweeps);
 // converged: h = w and (depth given) depth = w - h; otherwise h stays and depth = 0.  Sets status[1]
 int32_t nz_launch_fill_finalise(hipStream_t s, float *h, const float *w, float *depth, int *status, size_t n);
+// the stripe form, one round (nz_fill_stripe): begin sets the status words from the caller's proceed word and the caller's
+// `changed` word; a pass works on the owned rows [g.or0, g.or1) of stripe-shaped planes against the frozen rows or0 - 1 and
+// or1 of w_ghost (first: derived from h), [zlo, zhi] the global grid in buffer rows; end brings the owned rows of the work
+// plane to w when all `passes` passes ran; finalise is all or nothing on the owned rows by the caller's verdict
+int32_t nz_launch_fill_round_begin(hipStream_t s, int *status, const int *proceed, int *changed, int first);
+int32_t nz_launch_fill_stripe_pass(hipStream_t s, const float *h, const float *w_in, float *w_out, const float *w_ghost,
+                                   int *status, const unsigned char *flags_in, unsigned char *flags_out, int *changed,
+                                   float eps, float sea, const nz_geom &g, int zlo, int zhi, int first, int pass, int sweeps);
+int32_t nz_launch_fill_round_end(hipStream_t s, float *w, const float *w_work, const int *status, int passes, const nz_geom &g);
+int32_t nz_launch_fill_stripe_finalise(hipStream_t s, float *h, const float *w, float *depth, const int *converged,
+                                       const nz_geom &g);
 
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid

@@ -1362,6 +1362,64 @@ extern "C" int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *w
     return nz_ctx_finish(ctx, out);
 }
 
+// ---- the stripe form (include/noize_hip.h): n iterations of one call on a row stripe, one launch each ----
+constexpr int FLU_STRIPE_RADIUS = 2;  // rows one iteration reads beyond the rows it produces: receivers at 1, their heights at 2
+
+extern "C" int32_t nz_fluvial_stripe_halo_rows(int32_t iterations) {
+    return iterations > 0 ? FLU_STRIPE_RADIUS * iterations : 0;
+}
+
+extern "C" size_t nz_fluvial_stripe_work_floats(const nz_stripe *st, int32_t iterations) {
+    if (!st || st->rows <= 0 || st->cols <= 0 || st->pitch < 0 || iterations <= 1) return 0;
+    return 2 * stripe_plane_floats(*st);
+}
+
+extern "C" int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float *height_out, float *drainage_out, float *work,
+                                     const nz_stripe *st, const nz_fluvial_desc *desc, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(desc, "desc is NULL");
+    const int n = desc->iterations;
+    NZ_REQUIRE(n >= 1, "iterations %d < 1", n);
+    NZ_REQUIRE(n <= INT32_MAX / FLU_STRIPE_RADIUS, "iterations %d out of range", n);
+    nz_fluvial_params k;
+    NZ_TRY(check_fluvial(desc, nullptr, nullptr, nullptr, 0, &k));  // the scalars; the planes below
+    NZ_TRY(nz_check_stripe(st, FLU_STRIPE_RADIUS * n));
+    NZ_REQUIRE(height_in && height_out && drainage_out, "height_in/height_out/drainage_out is NULL");
+    NZ_REQUIRE(n == 1 || work, "work is NULL");
+    // every plane the call writes lies apart from every other plane of the call; planes that are only read may alias
+    const nz_geom g0 = nz_geom_from_stripe(*st);
+    const size_t span = (size_t)(st->rows - 1) * g0.pitch + st->cols, plane = stripe_plane_floats(*st);
+    struct named { const char *name; const float *p; size_t n; };
+    const named reads[] = {{"height_in", height_in, span},     {"drainageIn", desc->drainageIn, span},
+                           {"rainMap", desc->rainMap, span},   {"hardness", desc->hardness, span},
+                           {"upliftMap", desc->upliftMap, span}};
+    const named writes[] = {{"height_out", height_out, span}, {"drainage_out", drainage_out, span},
+                            {"work", n > 1 ? work : nullptr, 2 * plane}};
+    auto overlap = [](const named &a, const named &b) {
+        return a.p && b.p && (uintptr_t)a.p < (uintptr_t)(b.p + b.n) && (uintptr_t)b.p < (uintptr_t)(a.p + a.n);
+    };
+    for (size_t i = 0; i < 3; i++) {
+        for (const auto &r : reads) NZ_REQUIRE(!overlap(writes[i], r), "%s overlaps %s", writes[i].name, r.name);
+        for (size_t j = i + 1; j < 3; j++)
+            NZ_REQUIRE(!overlap(writes[i], writes[j]), "%s overlaps %s", writes[i].name, writes[j].name);
+    }
+    // launch j writes set (n-1-j) & 1: 0 = the caller's output planes, where the last launch lands; 1 = `work`
+    float *hs[2] = {height_out, work}, *as[2] = {drainage_out, n > 1 ? work + plane : nullptr};
+    const int zlo = -st->grow0, zhi = st->grows - 1 - st->grow0;  // the global grid in buffer rows
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int j = 0; j < n; j++) {
+        const int to = (n - 1 - j) & 1, widen = FLU_STRIPE_RADIUS * (n - 1 - j);
+        nz_geom g = g0;
+        g.or0 = st->own0 - widen > zlo ? st->own0 - widen : zlo;
+        g.or1 = st->own1 + widen < zhi + 1 ? st->own1 + widen : zhi + 1;
+        if (j == n - 1) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fluvial_stripe(ctx->stream, j == 0 ? height_in : hs[to ^ 1], hs[to],
+                                        j == 0 ? desc->drainageIn : as[to ^ 1], as[to], k, g, zlo, zhi, desc->rainMap,
+                                        desc->hardness, desc->upliftMap));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
 // ---------------------------------------------------------------------------------------------
 // depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
 // ---------------------------------------------------------------------------------------------
@@ -1441,6 +1499,87 @@ extern "C" int32_t nz_fill_depressions_rw(nz_ctx *ctx, nz_rw_tile *tile, float *
     NZ_BEGIN(ctx, dep);
     NZ_TRY(check_rw(tile));
     return fill_impl(ctx, tile->read, tile->write, work, desc, tile->resolution, tile->count, out);
+}
+
+// ---- the stripe form (include/noize_hip.h): one round of passes on the owned rows against one frozen row on each side ----
+static fill_layout fill_stripe_layout(const nz_stripe &st) {
+    const size_t tiles = (size_t)((st.cols + 63) / 64) * ((st.own1 - st.own0 + 15) / 16);
+    return fill_layout{(tiles + 15) / 16 * 4, stripe_plane_floats(st)};
+}
+
+extern "C" int32_t nz_fill_stripe_halo_rows(void) { return 1; }
+
+// 16 status words, two generations of tile bytes, the second W plane
+extern "C" size_t nz_fill_stripe_work_floats(const nz_stripe *st) {
+    if (!st || st->rows <= 0 || st->cols <= 0 || st->pitch < 0 || st->own0 < 0 || st->own1 < st->own0) return 0;
+    const fill_layout L = fill_stripe_layout(*st);
+    return FILL_STATUS + 2 * L.gen_floats + L.n;
+}
+
+extern "C" int32_t nz_fill_stripe(nz_ctx *ctx, const float *height, float *w, float *work, const nz_stripe *st,
+                                  const nz_fill_desc *desc, int32_t first, const int32_t *proceed, int32_t *changed,
+                                  nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(desc, "desc is NULL");
+    NZ_REQUIRE(std::isfinite(desc->epsilon), "epsilon is not finite");
+    NZ_REQUIRE(std::isfinite(desc->seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(desc->epsilon >= 0.0f, "epsilon %g < 0", (double)desc->epsilon);
+    NZ_REQUIRE(desc->maxPasses >= 1, "maxPasses %d < 1", desc->maxPasses);
+    NZ_TRY(nz_check_stripe(st, 1));
+    NZ_REQUIRE(height && w && work, "height/w/work is NULL");
+    NZ_REQUIRE(changed, "changed is NULL");
+    const nz_geom g = nz_geom_from_stripe(*st);
+    const fill_layout L = fill_stripe_layout(*st);
+    const size_t span = (size_t)(st->rows - 1) * g.pitch + st->cols, total = FILL_STATUS + 2 * L.gen_floats + L.n;
+    auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
+        return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    };
+    NZ_REQUIRE(!overlap(w, span * 4, height, span * 4), "w overlaps height");
+    NZ_REQUIRE(!overlap(work, total * 4, height, span * 4), "work overlaps height");
+    NZ_REQUIRE(!overlap(work, total * 4, w, span * 4), "work overlaps w");
+    for (const void *p : {(const void *)height, (const void *)w, (const void *)work}) {
+        NZ_REQUIRE(!overlap(changed, 4, p, p == work ? total * 4 : span * 4), "changed overlaps a plane");
+        NZ_REQUIRE(!proceed || !overlap(proceed, 4, p, p == work ? total * 4 : span * 4), "proceed overlaps a plane");
+    }
+    int *status = reinterpret_cast<int *>(work);
+    unsigned char *flags[2] = {reinterpret_cast<unsigned char *>(work + FILL_STATUS),
+                               reinterpret_cast<unsigned char *>(work + FILL_STATUS + L.gen_floats)};
+    float *planes[2] = {w, work + FILL_STATUS + 2 * L.gen_floats};  // pass p reads plane p & 1 and writes the other
+    const float eps = desc->epsilon + 0.0f;  // -0 -> +0
+    const int sweeps = fill_sweeps.load(), passes = desc->maxPasses;
+    const int zlo = -st->grow0, zhi = st->grows - 1 - st->grow0;  // the global grid in buffer rows
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_fill_round_begin(ctx->stream, status, proceed, changed, first != 0));
+    for (int p = 0; p < passes; p++) {
+        if (p == passes - 1 && !(passes & 1)) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fill_stripe_pass(ctx->stream, height, planes[p & 1], planes[(p + 1) & 1], w, status, flags[(p + 1) & 1],
+                                          flags[p & 1], changed, eps, desc->seaLevel, g, zlo, zhi, first != 0, p, sweeps));
+    }
+    if (passes & 1) {  // the last pass wrote the work plane
+        nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fill_round_end(ctx->stream, w, planes[1], status, passes, g));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const float *w, float *depth, const nz_stripe *st,
+                                           const int32_t *converged, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(height && w, "height/w is NULL");
+    NZ_REQUIRE(converged, "converged is NULL");
+    const nz_geom g = nz_geom_from_stripe(*st);
+    const size_t span = ((size_t)(st->rows - 1) * g.pitch + st->cols) * 4;
+    auto overlap = [](const void *a, size_t na, const void *b, size_t nb) {
+        return a && b && (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+    };
+    NZ_REQUIRE(!overlap(height, span, w, span), "height overlaps w");
+    NZ_REQUIRE(!overlap(depth, span, height, span), "depth overlaps height");
+    NZ_REQUIRE(!overlap(depth, span, w, span), "depth overlaps w");
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_fill_stripe_finalise(ctx->stream, height, w, depth, converged, g));
+    return nz_ctx_finish(ctx, out);
 }
 
 // ---------------------------------------------------------------------------------------------

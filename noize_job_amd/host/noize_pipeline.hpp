@@ -779,6 +779,20 @@ class FluvialErosionStage : public PipelineStage {
         }
         jobHandle = done(h);
     }
+    // The stage on one row stripe of a larger grid (nz_fluvial_stripe): `n` iterations with this stage's scalars in one call.
+    // The planes -- all of the stripe's shape -- are the caller's, and so is the exchange of 2 * n ghost rows before the call
+    // (nz_halo_exchange on heightIn and, when given, drainageInRows; the maps once, before the first call); a NULL map is
+    // an option left off, a NULL drainageInRows the start state.
+    JobHandle ScheduleStripe(const float *heightIn, float *heightOut, float *drainageOut, float *stripeWork,
+                             const nz_stripe &st, int n, const float *drainageInRows, const float *rainMapRows,
+                             const float *hardnessRows, const float *upliftMapRows, JobHandle dependency) {
+        const nz_fluvial_desc desc{n, erodibility, uplift, dt, rain, seaLevel, rainMapRows, hardnessRows, upliftMapRows,
+                                   drainageInRows};
+        nz_handle h = 0;
+        check(nz_fluvial_stripe(ctx, heightIn, heightOut, drainageOut, stripeWork, &st, &desc, dependency.id, &h),
+              "nz_fluvial_stripe");
+        return done(h);
+    }
     const float *drainage() const { return work ? work->ptr : nullptr; }
     size_t drainageLength() const { return (size_t)count * resolution * resolution; }
     void OnDestroy() override { work.reset(); }
@@ -828,6 +842,28 @@ class DepressionFillStage : public PipelineStage {
                   "nz_fill_depressions");
         }
         jobHandle = done(h);
+    }
+    // The stage on one row stripe of a larger grid, one round (nz_fill_stripe): at most `passes` passes with this stage's
+    // epsilon and sea level over the owned rows, against one frozen ghost row of W on each side.  The planes and words are the
+    // caller's (stripeWork: nz_fill_stripe_work_floats), and so are the exchange of one row before the call -- of heightRows
+    // before the round with `first`, of wRows before every later one -- and the vote after it (nz_comm_allreduce_max_i32 on
+    // `changed`, which the next round takes as its `proceed`; NULL in the first).
+    JobHandle ScheduleStripe(const float *heightRows, float *wRows, float *stripeWork, const nz_stripe &st, int passes,
+                             bool first, const int32_t *proceed, int32_t *changed, JobHandle dependency) {
+        const nz_fill_desc desc{epsilon, seaLevel, passes, nullptr};
+        nz_handle h = 0;
+        check(nz_fill_stripe(ctx, heightRows, wRows, stripeWork, &st, &desc, first, proceed, changed, dependency.id, &h),
+              "nz_fill_stripe");
+        return done(h);
+    }
+    // ... and the end of the rounds (nz_fill_stripe_finalise): all or nothing on the owned rows by the device word
+    // `converged`, the verdict "the last vote was 0"; depthRows may be NULL.
+    JobHandle FinaliseStripe(float *heightRows, const float *wRows, float *depthRows, const nz_stripe &st,
+                             const int32_t *converged, JobHandle dependency) {
+        nz_handle h = 0;
+        check(nz_fill_stripe_finalise(ctx, heightRows, wRows, depthRows, &st, converged, dependency.id, &h),
+              "nz_fill_stripe_finalise");
+        return done(h);
     }
     const float *depth() const { return lakes ? lakes->ptr : nullptr; }
     size_t depthLength() const { return (size_t)count * resolution * resolution; }

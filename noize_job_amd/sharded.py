@@ -354,6 +354,167 @@ def run_hydraulic_lockstep(ops_list, plans, params, bufs_list, copy_rows, exchan
         _copy_ghost_rows(reqs, plans, copy_rows)
 
 
+# ---- stream-power fluvial erosion on row stripes (nz_fluvial_stripe) ------------------------------------------------------
+FLUVIAL_SCALARS = ("erodibility", "uplift", "dt", "rain", "seaLevel")
+FLUVIAL_DEFAULTS = dict(iterations=100, erodibility=0.05, uplift=0.002, dt=1.0, rain=1.0, seaLevel=-3.4028234663852886e38)
+FLUVIAL_MAPS = ("rainMap", "hardness", "upliftMap")
+
+
+def fluvial_halo_rows(k):
+    """Ghost rows on each side that k iterations without an exchange read beyond the owned rows: an iteration gathers
+    along the receivers of the cells 1 row away, which look at the heights 2 rows away."""
+    return 2 * k
+
+
+def fluvial_params(params=None, **kw):
+    """The scalar fields of nz_fluvial_desc from a dict and / or keyword arguments, the hosts' stage defaults for the
+    rest.  The maps of the desc are per-rank buffers and travel in `bufs`."""
+    prm = dict(FLUVIAL_DEFAULTS)
+    for src in (params or {}, kw):
+        for name, v in src.items():
+            assert name in prm, "%s is not a scalar field of nz_fluvial_desc" % name
+            prm[name] = v
+    return prm
+
+
+def fluvial_steps(ops, plan, params, bufs, exchange_every=1):
+    """Fluvial erosion on one rank's stripe as a generator in the style of hydraulic_steps: the iterations run in blocks
+    of at most `exchange_every` (split_iterations), every block one ops.fluvial call that recomputes the ghost rows its
+    later iterations need, and before every block it yields (planes, up_rows, down_rows) for the exchange:
+      before the first block   the height plane and, once, the maps that are given, 2 * n rows of block n
+      before each later block  the height plane and the drainage plane, 2 * n rows
+    The maps are read by every block; split_iterations puts the longest block first, so their one exchange covers the
+    later blocks.  bufs: dict with the height planes "A" (holds the input on its owned rows) and
+    "B", the drainage planes "D0" and "D1", "work" ([2, rows, cols]; needed when exchange_every > 1) and, optionally,
+    "rainMap", "hardness", "upliftMap" (owned rows filled) and "drainageIn" (the drainage to start from, owned rows
+    filled; it is exchanged with the heights).  Returns (height plane, drainage plane) whose owned rows hold the result."""
+    prm = fluvial_params(params)
+    blocks = split_iterations(prm["iterations"], exchange_every) if prm["iterations"] > 0 else []
+    maps = {k: bufs.get(k) for k in FLUVIAL_MAPS}
+    cur, nxt = bufs["A"], bufs["B"]
+    d_cur, d_nxt = bufs.get("drainageIn"), bufs["D0"]
+    for i, n in enumerate(blocks):
+        rows = fluvial_halo_rows(n)
+        if i == 0:
+            given = [maps[k] for k in FLUVIAL_MAPS if maps[k] is not None]
+            yield [cur] + ([d_cur] if d_cur is not None else []) + given, rows, rows
+        else:
+            yield [cur, d_cur], rows, rows
+        ops.fluvial(cur, nxt, d_cur, d_nxt, bufs.get("work"), plan, prm, n, **maps)
+        cur, nxt = nxt, cur
+        d_cur, d_nxt = d_nxt, (bufs["D1"] if d_nxt is bufs["D0"] else bufs["D0"])
+    return cur, d_cur
+
+
+def run_fluvial(ops, comm, plan, params, bufs, exchange_every=1):
+    """fluvial_steps on this rank, every exchange completed before the block that reads it (TorchComm, NativeComm, NoComm);
+    returns (height plane, drainage plane)."""
+    gen = fluvial_steps(ops, plan, params, bufs, exchange_every)
+    try:
+        while True:
+            planes, up_rows, down_rows = next(gen)
+            comm.exchange(planes, plan, up_rows, down_rows)
+    except StopIteration as done:
+        return done.value
+
+
+def run_fluvial_lockstep(ops_list, plans, params, bufs_list, copy_rows, exchange_every=1):
+    """All ranks inside one process, as run_hydraulic_lockstep; returns every rank's (height plane, drainage plane)."""
+    gens = [fluvial_steps(o, pl, params, b, exchange_every) for o, pl, b in zip(ops_list, plans, bufs_list)]
+    results = [None] * len(gens)
+    while True:
+        reqs = []
+        for r, g in enumerate(gens):
+            try:
+                reqs.append(next(g))
+            except StopIteration as done:
+                results[r] = done.value
+                reqs.append(None)
+        if all(r is None for r in reqs):
+            return results
+        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
+        _copy_ghost_rows(reqs, plans, copy_rows)
+
+
+# ---- depression filling on row stripes (nz_fill_stripe) -----------------------------------------------------------------
+FILL_DEFAULTS = dict(epsilon=1e-4, seaLevel=-3.4028234663852886e38, maxPasses=64, maxRounds=64)
+VOTE = "vote"  # a generator's request (VOTE, word): the maximum of every rank's word, in place, and its value sent back
+
+
+def fill_steps(ops, plan, params, bufs):
+    """Depression filling on one rank's stripe as a generator: rounds of ops.fill (at most maxPasses passes over the owned
+    rows against one frozen ghost row of W on each side), and between them
+      an exchange request (planes, 1, 1)   the height plane before round 0, the W plane before every later round
+      a vote request (VOTE, word)          after every round: the driver reduces the int32 word "did my stripe change" to
+                                           the maximum over all ranks, in place, and sends its value back
+    An exchange request is a 3-tuple of (list, int, int), a vote request a 2-tuple whose first item is VOTE.  The rounds
+    stop when the vote is 0 or after maxRounds; round r > 0 is handed the vote of round r - 1 as its `proceed` word, which
+    is the form a compiled host enqueues without reading back.  Then ops.fill_finalise with the verdict vote == 0 on every
+    rank: all or nothing.  bufs: "H" (the heights on the owned rows; receives the result), "W", "work"
+    (nz_fill_stripe_work_floats), "words" (int32[3]) and optionally "depth"; plan.halo >= 1.
+    Returns (height plane, depth plane or None, rounds, converged)."""
+    prm = dict(FILL_DEFAULTS)
+    for name, v in (params or {}).items():
+        assert name in prm, "%s is not a parameter of the sharded fill" % name
+        prm[name] = v
+    words = bufs["words"]
+    vote, rounds = 1, 0
+    while vote != 0 and rounds < prm["maxRounds"]:
+        yield [bufs["H"] if rounds == 0 else bufs["W"]], 1, 1
+        word = words[rounds & 1:(rounds & 1) + 1]
+        ops.fill(bufs["H"], bufs["W"], bufs["work"], plan, prm, rounds == 0,
+                 None if rounds == 0 else words[(rounds - 1) & 1:((rounds - 1) & 1) + 1], word)
+        vote = yield VOTE, word
+        rounds += 1
+    words[2:3].fill_(1 if vote == 0 else 0)
+    ops.fill_finalise(bufs["H"], bufs["W"], bufs.get("depth"), plan, words[2:3])
+    return bufs["H"], bufs.get("depth"), rounds, vote == 0
+
+
+def run_fill(ops, comm, plan, params, bufs):
+    """fill_steps on this rank: exchanges through comm.exchange, votes through comm.allreduce_max (TorchComm, NativeComm,
+    NoComm); returns (height plane, depth plane or None, rounds, converged)."""
+    gen = fill_steps(ops, plan, params, bufs)
+    answer = None
+    try:
+        while True:
+            req = gen.send(answer)
+            if req[0] == VOTE:
+                answer = comm.allreduce_max(req[1])
+            else:
+                comm.exchange(req[0], plan, req[1], req[2])
+                answer = None
+    except StopIteration as done:
+        return done.value
+
+
+def run_fill_lockstep(ops_list, plans, params, bufs_list, copy_rows):
+    """All ranks inside one process, as run_fluvial_lockstep; a vote is the maximum taken in process and written back to
+    every rank's word."""
+    gens = [fill_steps(o, pl, params, b) for o, pl, b in zip(ops_list, plans, bufs_list)]
+    results = [None] * len(gens)
+    answer = None
+    while True:
+        reqs = []
+        for r, g in enumerate(gens):
+            try:
+                reqs.append(g.send(answer))
+            except StopIteration as done:
+                results[r] = done.value
+                reqs.append(None)
+        if all(r is None for r in reqs):
+            return results
+        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
+        if reqs[0][0] == VOTE:
+            assert all(r[0] == VOTE for r in reqs), "ranks left the schedule at different points"
+            answer = max(int(r[1][0]) for r in reqs)
+            for r in reqs:
+                r[1].fill_(answer)
+        else:
+            _copy_ghost_rows(reqs, plans, copy_rows)
+            answer = None
+
+
 class HipStripeOps:
     """Stripe operations on device memory through the C ABI.  Buffers are objects with `.data_ptr()`
     (torch CUDA tensors used as plain HBM allocations); state buffers are indexable by plane."""
@@ -411,6 +572,27 @@ class HipStripeOps:
                                ptr(wear), ptr(deposits))
         self._call("nz_hydraulic_stripe", h_in.data_ptr(), h_out.data_ptr(), pin, pout, ptr(work), C.byref(st),
                    C.byref(desc), int(first), int(last))
+
+    def fluvial(self, h_in, h_out, d_in, d_out, work, plan, prm, n, rainMap=None, hardness=None, upliftMap=None, pitch=0):
+        """nz_fluvial_stripe: n iterations of `prm` (fluvial_params) in one call.  d_in None: the drainage starts at rain_c."""
+        st = plan.stripe(pitch)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        desc = N.FluvialDesc(n, *[prm[k] for k in FLUVIAL_SCALARS], ptr(rainMap), ptr(hardness), ptr(upliftMap), ptr(d_in))
+        self._call("nz_fluvial_stripe", h_in.data_ptr(), h_out.data_ptr(), d_out.data_ptr(), ptr(work), C.byref(st),
+                   C.byref(desc))
+
+    def fill(self, h, w, work, plan, prm, first, proceed, changed, pitch=0):
+        """nz_fill_stripe: one round, at most prm["maxPasses"] passes.  proceed: an int32 device word or None; changed: one."""
+        st = plan.stripe(pitch)
+        desc = N.FillDesc(prm["epsilon"], prm["seaLevel"], prm["maxPasses"], None)
+        self._call("nz_fill_stripe", h.data_ptr(), w.data_ptr(), work.data_ptr(), C.byref(st), C.byref(desc), int(first),
+                   proceed.data_ptr() if proceed is not None else None, changed.data_ptr())
+
+    def fill_finalise(self, h, w, depth, plan, converged, pitch=0):
+        """nz_fill_stripe_finalise on the owned rows, by the int32 device word `converged`."""
+        st = plan.stripe(pitch)
+        self._call("nz_fill_stripe_finalise", h.data_ptr(), w.data_ptr(), depth.data_ptr() if depth is not None else None,
+                   C.byref(st), converged.data_ptr())
 
     def upsample_halo_rows(self, filter):
         return self.lib.nz_upsample_stripe_halo_rows(int(filter))
@@ -497,12 +679,20 @@ class TorchComm:
         for req in reqs:
             req.wait()
 
+    def allreduce_max(self, words):
+        """The maximum of the int32 tensor `words` over the ranks, in place; returns words[0] on the host."""
+        self.dist.all_reduce(words, op=self.dist.ReduceOp.MAX)
+        return int(words[0])
+
 
 class NoComm:
     """world == 1: nothing to exchange (clamp-to-edge at both borders)."""
 
     def exchange(self, planes, plan, up_rows, down_rows):
         pass
+
+    def allreduce_max(self, words):
+        return int(words[0])
 
 
 # ---- the same schedule behind the C ABI (nz_comm.cpp): what a C# / C++ host calls ----------------------------------------
@@ -559,6 +749,12 @@ class NativeComm:
 
     def exchange(self, planes, plan, up_rows, down_rows):
         self.finish(self.begin(planes, plan, up_rows, down_rows))
+
+    def allreduce_max(self, words):
+        """nz_comm_allreduce_max_i32 on the int32 device tensor `words`, in place; returns words[0] on the host."""
+        N.check(N.lib.nz_comm_allreduce_max_i32(self.ctx._h, self._h, words.data_ptr(), words.numel(), 0, None),
+                "nz_comm_allreduce_max_i32")
+        return int(words[0])
 
     def allgather_range(self, map_ptr, n_floats, res_ptr, lim_min=float("inf"), lim_max=float("-inf")):
         N.check(N.lib.nz_comm_allgather_range(self.ctx._h, self._h, map_ptr, n_floats, res_ptr, lim_min, lim_max, 0, None),
