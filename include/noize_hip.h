@@ -332,6 +332,15 @@ int32_t nz_flow_fused_max_iterations(void);
 int32_t nz_flow_fused_stripe(nz_ctx *ctx, const float *height, const float *const *state_in, float *const *state_out,
                              float *dst, const nz_stripe *st, int32_t iterations, int32_t first, int32_t last,
                              float normMin, float normMax, nz_handle dep, nz_handle *out);
+/* The launch forms of a fused flow launch: tiles of 48 rows (512 threads), 32 or 64 rows (1024 threads) held on chip, or
+ * the row-streaming kernel (whole stages only: first and last).  Within one float mode every form computes the same bits. */
+enum nz_flow_form { NZ_FLOW_FORM_TILE48 = 0, NZ_FLOW_FORM_TILE32 = 1, NZ_FLOW_FORM_TILE64 = 2, NZ_FLOW_FORM_STREAM = 3 };
+/* the form nz_flow_fused_stripe / one launch of the stage entries takes for `rows` produced rows of `cols` cells,
+ * `count` grids, `iterations` (1..nz_flow_fused_max_iterations()) fused iterations; NZ_ERR_INVALID otherwise, NZ_ERR_HIP
+ * if the context's device cannot be made current.  The rule counts the CUs of the device that was current when the process
+ * first launched or queried; launcher and query share that count. */
+int32_t nz_flow_launch_form(nz_ctx *ctx, int32_t cols, int32_t rows, int32_t count, int32_t iterations,
+                            int32_t first, int32_t last);
 
 /* ---- grid hydraulic erosion with sediment transport (new-framework feature) ---------------------------
  * Takes material from where water runs fast and steep and lays it down where the water slows (the subtractive flow

@@ -104,6 +104,7 @@ NZ_OK, NZ_ERR_INVALID, NZ_ERR_UNSUPPORTED, NZ_ERR_HIP, NZ_ERR_NOMEM, NZ_ERR_NO_D
 NZ_COMM_ID_BYTES = 128
 NZ_HALO_RECOMPUTE, NZ_HALO_EXCHANGE, NZ_HALO_EXCHANGE_ONCE = 0, 1, 2
 NZ_FLOAT_STRICT, NZ_FLOAT_FAST, NZ_FLOAT_RELAXED = 0, 1, 2
+NZ_FLOW_FORM_TILE48, NZ_FLOW_FORM_TILE32, NZ_FLOW_FORM_TILE64, NZ_FLOW_FORM_STREAM = 0, 1, 2, 3
 NZ_HYDRAULIC_BORDER_CLOSED, NZ_HYDRAULIC_BORDER_OPEN = 0, 1
 NZ_RESAMPLE_NEAREST, NZ_RESAMPLE_BILINEAR, NZ_RESAMPLE_CATMULL_ROM = 0, 1, 2
 
@@ -176,6 +177,7 @@ SIGNATURES = {
     "nz_flow_fused_max_iterations": (_i, []),
     "nz_flow_fused_stripe": (_i, [ctx_p, dev_ptr, C.POINTER(dev_ptr), C.POINTER(dev_ptr), dev_ptr, stripe_p, _i, _i, _i,
                                   _f, _f] + _tail),
+    "nz_flow_launch_form": (_i, [ctx_p, _i, _i, _i, _i, _i, _i]),
     "nz_hydraulic_erosion_work_floats": (_sz, [_i, _i]),
     "nz_hydraulic_erosion_stage": (_i, [ctx_p, dev_ptr, dev_ptr, _i] + [_f] * 7 + [_i] + _tail),
     "nz_hydraulic_erosion_stage_rw": (_i, [ctx_p, rw_tile_p, dev_ptr, _i] + [_f] * 7 + _tail),

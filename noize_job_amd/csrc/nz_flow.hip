@@ -397,6 +397,32 @@ int nz_flow_fused_max() {
     return cap < 1 ? 1 : (cap > FT_MAX_N ? FT_MAX_N : cap);
 }
 
+// The form one fused launch takes (enum nz_flow_form): the launcher below and the ABI's query, nz_flow_launch_form, both ask
+// here.  `n` in 1..FT_MAX_N.
+int nz_flow_form(const nz_geom &g, int n, int first, int last) {
+    if (first && last && nz_flow_stream_wanted(g, n)) return NZ_FLOW_FORM_STREAM;
+    const int H = 2 * n, HX = (H + 3) & ~3;
+    const int OW = FT_TW - 2 * HX, OH = FT_TH - 2 * H;
+    const long long tiles_x = (g.cols + OW - 1) / OW, rows = g.or1 - g.or0;
+    const long long blocks = tiles_x * ((rows + OH - 1) / OH);
+    // A TINY grid (a tile of the reference's own sizes, 256^2 ... 512^2): at most a workgroup per CU whatever the tile, and what
+    // the launch waits for is the latency of one workgroup's dependent iterations.  32-row tiles of 1024 threads -- four cells
+    // per thread, four waves per SIMD -- run an iteration in ~0.6 of the time of the 48-row tile's twelve cells per thread (more
+    // workgroups, each with a third less work per SIMD): while they still fit one round of the CUs, they are used.
+    static const int tiny = getenv("NZ_FLOW_TINY") ? atoi(getenv("NZ_FLOW_TINY")) : 1;  // 0: never; 2 / 3: the 32- / 64-row tile at every size (test matrix)
+    const int OH_t = FT_TH_TINY - 2 * H;
+    const long long blocks_t = OH_t > 0 ? tiles_x * ((rows + OH_t - 1) / OH_t) : 0;
+    if (OH_t >= 4 && (tiny == 2 || (tiny == 1 && blocks_t * g.count <= nz_cu_count()))) return NZ_FLOW_FORM_TILE32;
+    // ... and the next size up (768^2 ... 1024^2): 64-row tiles of 1024 threads -- eight cells per thread, four waves per SIMD,
+    // 0.69 of the tile is interior at n = 5 instead of 0.58 -- while THEY fit one round (the 48-row tile's 370 workgroups at
+    // 1024^2 are one and a half per CU: the launch lasts as long as the CUs that hold two).  Flow x5: 512^2 20.3 -> 15.3 us
+    // (32-row tiles), 1024^2 30.6 -> 26.1 us (64-row tiles); 768^2 keeps the 48-row tile (224 workgroups: 21.4 against 24.5 us)
+    const int OH_m = FT_TH_MID - 2 * H;
+    const long long blocks_m = tiles_x * ((rows + OH_m - 1) / OH_m);
+    if (tiny == 3 || (tiny == 1 && blocks * g.count > nz_cu_count() && blocks_m * g.count <= nz_cu_count())) return NZ_FLOW_FORM_TILE64;
+    return NZ_FLOW_FORM_TILE48;
+}
+
 // n iterations; `first`: implied initial state, inputs unread; `last`: velocity+normalise into dst
 int32_t nz_launch_flow_fused(hipStream_t s, const float *h, const float *const in[5], float *const out[5], float *dst,
                              float *h_out, const nz_geom &g, int n, int first, int last, float nmin, float nrange) {
@@ -405,27 +431,12 @@ int32_t nz_launch_flow_fused(hipStream_t s, const float *h, const float *const i
         return NZ_ERR_INVALID;
     }
     if (g.or1 <= g.or0) return NZ_OK;
-    if (first && last && nz_flow_stream_wanted(g, n)) return nz_launch_flow_stream(s, h, dst, g, n, nmin, nrange);
-    int H = 2 * n, HX = (H + 3) & ~3;
-    int OW = FT_TW - 2 * HX, OH = FT_TH - 2 * H;
-    long long blocks = (long long)((g.cols + OW - 1) / OW) * ((g.or1 - g.or0 + OH - 1) / OH);
-    // A TINY grid (a tile of the reference's own sizes, 256^2 ... 512^2): at most a workgroup per CU whatever the tile, and what
-    // the launch waits for is the latency of one workgroup's dependent iterations.  32-row tiles of 1024 threads -- four cells
-    // per thread, four waves per SIMD -- run an iteration in ~0.6 of the time of the 48-row tile's twelve cells per thread (more
-    // workgroups, each with a third less work per SIMD): while they still fit one round of the CUs, they are used.
-    static const int tiny = getenv("NZ_FLOW_TINY") ? atoi(getenv("NZ_FLOW_TINY")) : 1;  // 0: never; 2 / 3: the 32- / 64-row tile at every size (test matrix)
-    const int OH_t = FT_TH_TINY - 2 * H;
-    const long long blocks_t = OH_t > 0 ? (long long)((g.cols + OW - 1) / OW) * ((g.or1 - g.or0 + OH_t - 1) / OH_t) : 0;
-    const bool use_tiny = OH_t >= 4 && (tiny == 2 || (tiny == 1 && blocks_t * g.count <= nz_cu_count()));
-    // ... and the next size up (768^2 ... 1024^2): 64-row tiles of 1024 threads -- eight cells per thread, four waves per SIMD,
-    // 0.69 of the tile is interior at n = 5 instead of 0.58 -- while THEY fit one round (the 48-row tile's 370 workgroups at
-    // 1024^2 are one and a half per CU: the launch lasts as long as the CUs that hold two).  Flow x5: 512^2 20.3 -> 15.3 us
-    // (32-row tiles), 1024^2 30.6 -> 26.1 us (64-row tiles); 768^2 keeps the 48-row tile (224 workgroups: 21.4 against 24.5 us)
-    const int OH_m = FT_TH_MID - 2 * H;
-    const long long blocks_m = (long long)((g.cols + OW - 1) / OW) * ((g.or1 - g.or0 + OH_m - 1) / OH_m);
-    const bool use_mid = !use_tiny && (tiny == 3 || (tiny == 1 && blocks * g.count > nz_cu_count() && blocks_m * g.count <= nz_cu_count()));
-    if (use_tiny) blocks = blocks_t;
-    if (use_mid) blocks = blocks_m;
+    const int form = nz_flow_form(g, n, first, last);
+    if (form == NZ_FLOW_FORM_STREAM) return nz_launch_flow_stream(s, h, dst, g, n, nmin, nrange);
+    const bool use_tiny = form == NZ_FLOW_FORM_TILE32, use_mid = form == NZ_FLOW_FORM_TILE64;
+    const int H = 2 * n, HX = (H + 3) & ~3;
+    const int OW = FT_TW - 2 * HX, OH = (use_tiny ? FT_TH_TINY : use_mid ? FT_TH_MID : FT_TH) - 2 * H;
+    const long long blocks = (long long)((g.cols + OW - 1) / OW) * ((g.or1 - g.or0 + OH - 1) / OH);
     uintptr_t bits = reinterpret_cast<uintptr_t>(h) | (uintptr_t)(g.pitch * 4);
     if (!first)
         for (int i = 0; i < 5; i++) bits |= reinterpret_cast<uintptr_t>(in[i]);

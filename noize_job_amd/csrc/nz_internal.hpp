@@ -305,6 +305,7 @@ int32_t nz_launch_flow_fused(hipStream_t s, const float *h, const float *const i
 
 // the whole stage (first && last) as one row-streaming launch (nz_flow_stream.hip)
 bool nz_flow_stream_wanted(const nz_geom &g, int n);
+int nz_flow_form(const nz_geom &g, int n, int first, int last);  // enum nz_flow_form: the form one fused launch takes
 int32_t nz_launch_flow_stream(hipStream_t s, const float *h, float *dst, const nz_geom &g, int n, float nmin, float nrange);
 
 // grid hydraulic erosion (nz_hydraulic.hip): one iteration per launch on `count` tiles of res^2 cells stored back to back.

@@ -977,7 +977,8 @@ extern "C" int32_t nz_flow_fused_stripe(nz_ctx *ctx, const float *height, const 
     NZ_TRY(nz_check_stripe(st, 2 * iterations));
     NZ_REQUIRE(height, "height is NULL");
     NZ_REQUIRE(first || state_in, "state_in is NULL");
-    NZ_REQUIRE(last ? dst != nullptr : state_out != nullptr, "output plane is NULL");
+    NZ_REQUIRE(!last || dst, "dst is NULL");
+    NZ_REQUIRE(last || state_out, "state_out is NULL");
     for (int i = 0; i < 5; i++) {
         NZ_REQUIRE(first || state_in[i], "state_in[%d] is NULL", i);
         NZ_REQUIRE(last || state_out[i], "state_out[%d] is NULL", i);
@@ -987,6 +988,20 @@ extern "C" int32_t nz_flow_fused_stripe(nz_ctx *ctx, const float *height, const 
                                 last ? dst : nullptr, nullptr, nz_geom_from_stripe(*st), iterations, first, last, normMin,
                                 normMax - normMin));
     return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_flow_launch_form(nz_ctx *ctx, int32_t cols, int32_t rows, int32_t count, int32_t iterations,
+                                       int32_t first, int32_t last) {
+    NZ_REQUIRE(ctx, "ctx is NULL");
+    // (the rule's CU count, nz_cu_count, is taken once per process from the device current at its first use: the launcher
+    // and this query share it)
+    NZ_HIP(hipSetDevice(ctx->device));
+    NZ_REQUIRE(cols >= 1 && rows >= 1 && count >= 1, "flow_launch_form: cols %d, rows %d, count %d", cols, rows, count);
+    NZ_REQUIRE(iterations >= 1 && iterations <= nz_flow_fused_max(), "iterations %d cannot be fused", iterations);
+    nz_geom g{cols, cols, rows, 0, rows - 1, 0, rows};
+    g.count = count;
+    g.bstride = (size_t)cols * rows;
+    return nz_flow_form(g, iterations, first, last);
 }
 
 // ---------------------------------------------------------------------------------------------

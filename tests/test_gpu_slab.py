@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import conv_ref as R
+import flow_ref as F
 from slab import Slab, is_canary
 
 pytestmark = pytest.mark.gpu
@@ -429,6 +430,36 @@ def test_flow_delegates(nj, ctx, oracle, res):
             same(t.h.ToArray((res, res)), normed, what + ("normalise",))
             for name in ("bN", "bS", "bE", "bW", "bw"):   # the __buff planes: the updates are done in place
                 assert is_canary(getattr(t, name).ToArray()).all(), what + (name,)
+            s.check()
+
+
+def test_flow_fused_stripe(nj, ctx, oracle):
+    """A first-only launch, then a last-only one that reads what it wrote: a 130 x 97 stripe (an odd row length: every row
+    starts at another phase), the height, the five state planes and the result each at a phase of their own."""
+    rows, cols, n1, n2 = 130, 97, 3, 2
+    h = F.terrain(np.random.default_rng(97), rows, cols)
+    state = memo(("flow stripe state",), lambda: np.stack(F.launch(h, n1, True, False)))
+    want = memo(("flow stripe",), lambda: F.launch(h, n2, False, True, list(state)))
+    assert oracle.flowmap(h, n1 + n2, *F.NORM).tobytes() == want.tobytes()
+    n = rows * cols
+    st = nj.Stripe(cols, rows, 0, rows, 0, rows, 0)
+    for p, q in PAIRS:
+        planes = dict(h=(n, p, h), dst=(n, q, None))
+        for k in range(5):
+            planes["s%d" % k] = (n, third(p, q, k), None)
+        with carved(ctx, cols, **planes) as (s, t):
+            what = ("flow stripe", p, q)
+            ptrs = (nj._native.dev_ptr * 5)(*[getattr(t, "s%d" % k).ptr for k in range(5)])
+            ctx.call("nz_flow_fused_stripe", t.h.ptr, None, ptrs, None, C.byref(st), n1, 1, 0, *F.NORM).Complete()
+            for k in range(5):
+                bits(getattr(t, "s%d" % k).ToArray((rows, cols)), state[k], what + ("state plane", k))
+            assert is_canary(t.dst.ToArray()).all(), what
+            s.check()
+            ctx.call("nz_flow_fused_stripe", t.h.ptr, ptrs, None, t.dst.ptr, C.byref(st), n2, 0, 1, *F.NORM).Complete()
+            bits(t.dst.ToArray((rows, cols)), want, what + ("result",))
+            for k in range(5):
+                bits(getattr(t, "s%d" % k).ToArray((rows, cols)), state[k], what + ("state plane is read only", k))
+            bits(t.h.ToArray((rows, cols)), h, "the heights are read only")
             s.check()
 
 
