@@ -92,12 +92,6 @@ int32_t rccl_load(const rccl_api **out) {
         }                                                                                                    \
     } while (0)
 
-#define NZ_TRY(expr)          \
-    do {                      \
-        int32_t rc_ = (expr); \
-        if (rc_) return rc_;  \
-    } while (0)
-
 // `floats` contiguous floats from `send` on rank `src` to `recv` on rank `dst`; a rank fills in the end(s) it holds.
 // Both ends of every pair of ranks walk their lists in the same order (RCCL matches the k-th send to a peer with that
 // peer's k-th receive from us), and a transfer between two stripes of ONE rank posts its send and its receive back to back.

@@ -12,10 +12,9 @@
 #include <vector>
 
 #include "../../include/noize_hip.h"
+#include "nz_planes.hpp"  // nz_set_error, NZ_REQUIRE, nz_check_stripe: the host-only geometry and aliasing helpers
 
 // ---- error plumbing -------------------------------------------------------------------------
-void nz_set_error(const char *fmt, ...);
-
 #define NZ_HIP(expr)                                                                      \
     do {                                                                                  \
         hipError_t e_ = (expr);                                                           \
@@ -26,12 +25,10 @@ void nz_set_error(const char *fmt, ...);
         }                                                                                 \
     } while (0)
 
-#define NZ_REQUIRE(cond, ...)        \
-    do {                             \
-        if (!(cond)) {               \
-            nz_set_error(__VA_ARGS__); \
-            return NZ_ERR_INVALID;   \
-        }                            \
+#define NZ_TRY(expr)              \
+    do {                          \
+        int32_t rc_ = (expr);     \
+        if (rc_) return rc_;      \
     } while (0)
 
 // ---- context --------------------------------------------------------------------------------
@@ -99,6 +96,13 @@ constexpr uint64_t NZ_HANDLE_SEQ_MASK = (1ull << NZ_HANDLE_SEQ_BITS) - 1;
 int32_t nz_ctx_begin(nz_ctx *ctx, nz_handle dep);           // set device, order the stream after `dep`
 int32_t nz_ctx_finish(nz_ctx *ctx, nz_handle *out);         // record the JobHandle marker
 int32_t nz_ctx_scratch(nz_ctx *ctx, size_t floats, float **out);
+
+// how every stage entry point opens
+#define NZ_BEGIN(ctx, dep)                   \
+    do {                                     \
+        int32_t rc_ = nz_ctx_begin(ctx, dep); \
+        if (rc_) return rc_;                 \
+    } while (0)
 
 // ---- kernel parameter blocks ----------------------------------------------------------------
 constexpr int NZ_MAX_KSIZE = 25;
@@ -234,7 +238,34 @@ inline std::vector<int> nz_split_iterations(int n, int cap, bool even = false) {
     return d;
 }
 
-int32_t nz_check_stripe(const nz_stripe *st, int halo, int halo_below = -1);  // rows needed above / below the owned ones
+// ---- argument checks shared by the stage entry points (nz_stages.cpp, nz_terrain_stages.cpp) ----------------------------
+static inline int32_t check_res(int32_t resolution) {
+    NZ_REQUIRE(resolution >= 1 && resolution <= 46340, "resolution %d out of range", resolution);
+    return NZ_OK;
+}
+static inline int32_t check_batch(int32_t resolution, int32_t count) {
+    NZ_TRY(check_res(resolution));
+    NZ_REQUIRE(count >= 1 && count <= 65535, "count %d out of range [1,65535]", count);
+    return NZ_OK;
+}
+// READ / WRITE pair forms (nz_rw_tile): TileHelpers.SWAP_RWTILE (Pipeline/Tiles/TileData.cs:42-45) as a swap of the two
+// pointers instead of a copy job
+static inline int32_t check_rw(const nz_rw_tile *t) {
+    NZ_REQUIRE(t, "tile is NULL");
+    NZ_TRY(check_batch(t->resolution, t->count));
+    NZ_REQUIRE(t->read && t->write && t->read != t->write, "read/write must be two distinct planes");
+    return NZ_OK;
+}
+static inline nz_geom rw_geom(const nz_rw_tile *t) {
+    return t->count > 1 ? nz_geom_batch(t->resolution, t->count) : nz_geom_tile(t->resolution);
+}
+static inline void rw_swap(nz_rw_tile *t, bool swapped) {
+    if (swapped) {
+        float *r = t->read;
+        t->read = t->write;
+        t->write = r;
+    }
+}
 
 // nz_stages.cpp, for the sharded plan (nz_comm.cpp)
 int32_t nz_filter_taps(int32_t filter, nz_kernel_taps *t);  // KernelFilterType -> taps

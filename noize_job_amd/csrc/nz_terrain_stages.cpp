@@ -1,0 +1,723 @@
+// nz_terrain_stages.cpp -- the extern "C" entry points of the terrain stages the reference does not have (grid hydraulic
+// erosion, fluvial erosion, depression filling, resampling; include/noize_hip.h): tile, batch, read/write-pair and row-stripe
+// forms.  The stripe geometry and the aliasing checks they share are in nz_planes.hpp.
+#include <atomic>
+#include <cmath>
+#include <iterator>
+#include <utility>
+
+#include "nz_internal.hpp"
+
+// Launch j of a series of n that ping-pongs between two plane sets writes set (n-1-j) & 1, so that the last launch lands in
+// set 0.  The stripe entries: 0 = the caller's output planes, 1 = `work`.
+static int pingpong_set(int n, int j) { return (n - 1 - j) & 1; }
+
+// The height ping-pong of the in-place series: `iterations` >= 1 launches, each reading *cur and writing *nxt before the
+// caller swaps the two.  *cur starts at h0, which holds the input, so the result lands in h0 when `iterations` is even and
+// in h1 when it is odd (*in_h1).  keep_h0: the caller wants it in h0 whatever the count, and an odd count copies h0 to h1
+// (n floats) first and starts there.
+static int32_t height_pingpong(nz_ctx *ctx, float *h0, float *h1, size_t n, int iterations, bool keep_h0, float **cur,
+                               float **nxt, bool *in_h1) {
+    *cur = h0, *nxt = h1;
+    *in_h1 = !keep_h0 && (iterations & 1);
+    if (keep_h0 && (iterations & 1)) {
+        NZ_TRY(nz_launch_copy(ctx->stream, h1, h0, n));
+        std::swap(*cur, *nxt);
+    }
+    return NZ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// grid hydraulic erosion with sediment transport (new-framework feature, include/noize_hip.h, nz_hydraulic.hip)
+// ---------------------------------------------------------------------------------------------
+// work planes of count * res^2 floats each: 0 the final water, 1-6 and 7-12 the state sets {d, s, fN, fS, fE, fW} the
+// launches ping-pong between, 13 the in-place forms' second height plane
+constexpr int HYD_PLANES = 14;
+
+extern "C" size_t nz_hydraulic_erosion_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? (size_t)HYD_PLANES * resolution * resolution * count : 0;
+}
+
+// the scalars of a nz_hydraulic_desc as the launches take them
+static int32_t check_hydraulic(const nz_hydraulic_desc &d, nz_hydraulic_params *k) {
+    NZ_REQUIRE(d.iterations >= 0, "iterations %d < 0", d.iterations);
+    const struct { const char *name; float v; float lo, hi; } args[] = {
+        {"initialWater", d.initialWater, 0.0f, INFINITY}, {"rain", d.rain, 0.0f, INFINITY},
+        {"evaporation", d.evaporation, 0.0f, 1.0f},       {"capacity", d.capacity, 0.0f, INFINITY},
+        {"dissolve", d.dissolve, 0.0f, 1.0f},             {"deposit", d.deposit, 0.0f, 1.0f},
+        {"minTilt", d.minTilt, 0.0f, INFINITY}};
+    for (const auto &a : args) {
+        NZ_REQUIRE(std::isfinite(a.v), "%s is not finite", a.name);
+        if (a.hi == INFINITY) NZ_REQUIRE(a.v >= a.lo, "%s %g < 0", a.name, (double)a.v);
+        else NZ_REQUIRE(a.v >= a.lo && a.v <= a.hi, "%s %g outside [0, 1]", a.name, (double)a.v);
+    }
+    *k = nz_hydraulic_params{d.initialWater, d.rain, 1.0f - d.evaporation, d.capacity, d.dissolve, d.deposit, d.minTilt};
+    return NZ_OK;
+}
+
+// ... and its options (border, maps, masks)
+static int32_t hydraulic_ex_of(const nz_hydraulic_desc &d, nz_hydraulic_ex *ex) {
+    NZ_REQUIRE(d.border == NZ_HYDRAULIC_BORDER_CLOSED || d.border == NZ_HYDRAULIC_BORDER_OPEN, "border %d is not a mode",
+               d.border);
+    *ex = nz_hydraulic_ex{d.border == NZ_HYDRAULIC_BORDER_OPEN, d.rainMap, d.hardness, d.wear, d.deposits};
+    return NZ_OK;
+}
+
+// The masks of a tile-shaped call.  h0 / h1: the height plane(s) the call reads or writes (h1 may be NULL), n floats each
+// like every plane of the desc; the masks may overlap none of them, nor the maps, each other or `work`
+static int32_t check_hydraulic_masks(const nz_hydraulic_desc &d, const float *h0, const float *h1, const float *work,
+                                     size_t n) {
+    const nz_named_plane masks[] = {{"wear", d.wear, n}, {"deposits", d.deposits, n}};
+    const nz_named_plane others[] = {{"src", h0, n}, {"the write plane", h1, n}, {"work", work, (size_t)HYD_PLANES * n},
+                                     {"rainMap", d.rainMap, n}, {"hardness", d.hardness, n}};
+    for (const auto &m : masks)
+        for (const auto &o : others) NZ_REQUIRE(!nz_planes_overlap(m.p, n, o.p, o.floats), "%s overlaps %s", m.name, o.name);
+    NZ_REQUIRE(!nz_planes_overlap(d.wear, n, d.deposits, n), "wear overlaps deposits");
+    return NZ_OK;
+}
+
+// The body of every tile-shaped entry behind its NULL checks: the desc's checks, then desc.iterations launches on `count`
+// tiles.  The height ping-pongs between h0 and h1 (height_pingpong); h1 NULL: the in-place forms, which keep the result in
+// h0 and take work plane 13 as h1.  The state ping-pongs between the two sets of `work`.  Ends with the final water in work plane 0 (initialWater itself when there is
+// no iteration).  The masks are written by the first launch, or cleared here when there is none.
+static int32_t hydraulic_series(nz_ctx *ctx, float *h0, float *h1, float *work, int res, int count, const nz_hydraulic_desc &d,
+                                nz_handle *out, bool *in_h1) {
+    const size_t n = (size_t)res * res * count;
+    const int iterations = d.iterations;
+    nz_hydraulic_params k;
+    NZ_TRY(check_hydraulic(d, &k));
+    nz_hydraulic_ex ex;
+    NZ_TRY(hydraulic_ex_of(d, &ex));
+    NZ_TRY(check_hydraulic_masks(d, h0, h1, work, n));
+    const bool keep_h0 = !h1;
+    if (keep_h0) h1 = work + (size_t)(HYD_PLANES - 1) * n;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (the last launch below is armed)
+    if (iterations == 0) {
+        *in_h1 = false;
+        if (ex.wear) NZ_TRY(nz_launch_fill(ctx->stream, ex.wear, n, 0.0f));
+        if (ex.deposits) NZ_TRY(nz_launch_fill(ctx->stream, ex.deposits, n, 0.0f));
+        nz_ctx_arm_last_launch(ctx);
+        return nz_launch_fill(ctx->stream, work, n, k.initial_water);
+    }
+    float *cur, *nxt;
+    NZ_TRY(height_pingpong(ctx, h0, h1, n, iterations, keep_h0, &cur, &nxt, in_h1));
+    nz_hydraulic_planes sets[2];
+    for (int j = 0; j < 2; j++)
+        for (int i = 0; i < 6; i++) sets[j].in[i] = sets[j].out[i] = work + (size_t)(1 + 6 * j + i) * n;
+    for (int it = 0; it < iterations; it++) {
+        const int first = it == 0, last = it == iterations - 1;
+        nz_hydraulic_planes p;
+        for (int i = 0; i < 6; i++) {
+            p.in[i] = sets[it & 1].in[i];
+            p.out[i] = last ? (i == 0 ? work : nullptr) : sets[(it + 1) & 1].out[i];
+        }
+        if (last) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_hydraulic(ctx->stream, cur, nxt, p, k, res, count, first, last, &ex));
+        std::swap(cur, nxt);
+    }
+    return NZ_OK;
+}
+
+// every in-place entry: the old ones come with a desc of their scalars and every option off
+static int32_t hydraulic_stage_impl(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc, int32_t resolution,
+                                    int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    NZ_REQUIRE(src && work, "src/work is NULL");
+    NZ_REQUIRE(desc, "desc is NULL");
+    bool in_h1;
+    NZ_TRY(hydraulic_series(ctx, src, nullptr, work, resolution, count, *desc, out, &in_h1));
+    return nz_ctx_finish(ctx, out);
+}
+
+static int32_t hydraulic_rw_impl(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_hydraulic_desc *desc, nz_handle dep,
+                                 nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(desc, "desc is NULL");
+    bool in_h1;
+    NZ_TRY(hydraulic_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, *desc, out, &in_h1));
+    rw_swap(tile, in_h1);
+    return nz_ctx_finish(ctx, out);
+}
+
+static nz_hydraulic_desc hydraulic_plain_desc(int32_t iterations, float initialWater, float rain, float evaporation,
+                                              float capacity, float dissolve, float deposit, float minTilt) {
+    return nz_hydraulic_desc{iterations, initialWater, rain,    evaporation, capacity, dissolve, deposit,
+                             minTilt,    NZ_HYDRAULIC_BORDER_CLOSED, nullptr, nullptr, nullptr, nullptr};
+}
+
+extern "C" int32_t nz_hydraulic_erosion_stage(nz_ctx *ctx, float *src, float *work, int32_t iterations, float initialWater,
+                                              float rain, float evaporation, float capacity, float dissolve, float deposit,
+                                              float minTilt, int32_t resolution, nz_handle dep, nz_handle *out) {
+    const nz_hydraulic_desc d =
+        hydraulic_plain_desc(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt);
+    return hydraulic_stage_impl(ctx, src, work, &d, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_stage_batch(nz_ctx *ctx, float *src, float *work, int32_t iterations,
+                                                    float initialWater, float rain, float evaporation, float capacity,
+                                                    float dissolve, float deposit, float minTilt, int32_t resolution,
+                                                    int32_t count, nz_handle dep, nz_handle *out) {
+    const nz_hydraulic_desc d =
+        hydraulic_plain_desc(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt);
+    return hydraulic_stage_impl(ctx, src, work, &d, resolution, count, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, int32_t iterations,
+                                                 float initialWater, float rain, float evaporation, float capacity,
+                                                 float dissolve, float deposit, float minTilt, nz_handle dep,
+                                                 nz_handle *out) {
+    const nz_hydraulic_desc d =
+        hydraulic_plain_desc(iterations, initialWater, rain, evaporation, capacity, dissolve, deposit, minTilt);
+    return hydraulic_rw_impl(ctx, tile, work, &d, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_ex(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc,
+                                           int32_t resolution, nz_handle dep, nz_handle *out) {
+    return hydraulic_stage_impl(ctx, src, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_ex_batch(nz_ctx *ctx, float *src, float *work, const nz_hydraulic_desc *desc,
+                                                 int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    return hydraulic_stage_impl(ctx, src, work, desc, resolution, count, dep, out);
+}
+
+extern "C" int32_t nz_hydraulic_erosion_ex_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_hydraulic_desc *desc,
+                                              nz_handle dep, nz_handle *out) {
+    return hydraulic_rw_impl(ctx, tile, work, desc, dep, out);
+}
+
+// ---- the stripe form (include/noize_hip.h): n iterations of one call on a row stripe, one launch each ----
+constexpr int HYD_STRIPE_RADIUS = 3;  // ghost rows one iteration reads beyond the rows it produces (nz_hydraulic.hip's HR)
+constexpr int HYD_STRIPE_PLANES = 7;  // the height and the six state planes
+
+extern "C" int32_t nz_hydraulic_stripe_halo_rows(int32_t iterations) {
+    return iterations > 0 ? HYD_STRIPE_RADIUS * iterations : 0;
+}
+
+extern "C" size_t nz_hydraulic_stripe_work_floats(const nz_stripe *st, int32_t iterations) {
+    return iterations > 1 ? (size_t)HYD_STRIPE_PLANES * nz_stripe_plane_floats(st) : 0;
+}
+
+extern "C" int32_t nz_hydraulic_stripe(nz_ctx *ctx, const float *height_in, float *height_out, const float *const *state_in,
+                                       float *const *state_out, float *work, const nz_stripe *st,
+                                       const nz_hydraulic_desc *desc, int32_t first, int32_t last, nz_handle dep,
+                                       nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(desc, "desc is NULL");
+    const int n = desc->iterations;
+    NZ_REQUIRE(n >= 1, "iterations %d < 1", n);
+    nz_hydraulic_params k;
+    NZ_TRY(check_hydraulic(*desc, &k));
+    nz_hydraulic_ex ex;
+    NZ_TRY(hydraulic_ex_of(*desc, &ex));
+    NZ_REQUIRE(n <= INT32_MAX / HYD_STRIPE_RADIUS, "iterations %d out of range", n);
+    NZ_TRY(nz_check_stripe(st, HYD_STRIPE_RADIUS * n));
+    NZ_REQUIRE(height_in && height_out, "height_in/height_out is NULL");
+    NZ_REQUIRE(first || state_in, "state_in is NULL");
+    NZ_REQUIRE(state_out, "state_out is NULL");
+    NZ_REQUIRE(n == 1 || work, "work is NULL");
+    for (int i = 0; i < 6; i++) {
+        NZ_REQUIRE(first || state_in[i], "state_in[%d] is NULL", i);
+        // the last launch of a `last` call writes the water only; the launches before it ping-pong through all six
+        NZ_REQUIRE(state_out[i] || (last && n == 1 && i > 0), "state_out[%d] is NULL", i);
+    }
+    const size_t span = nz_stripe_span(*st), plane = nz_stripe_plane_floats(st);
+    nz_named_plane reads[3 + 6] = {{"height_in", height_in, span}, {"rainMap", desc->rainMap, span},
+                                   {"hardness", desc->hardness, span}};
+    nz_named_plane writes[4 + 6] = {{"height_out", height_out, span}, {"wear", desc->wear, span},
+                                    {"deposits", desc->deposits, span},
+                                    {"work", n > 1 ? work : nullptr, HYD_STRIPE_PLANES * plane}};
+    nz_hydraulic_planes sets[2];  // pingpong_set
+    float *hs[2] = {height_out, work};
+    for (int i = 0; i < 6; i++) {
+        reads[3 + i] = {"state_in", first ? nullptr : state_in[i], span};
+        writes[4 + i] = {"state_out", state_out[i], span};
+        sets[0].in[i] = sets[0].out[i] = state_out[i];
+        sets[1].in[i] = sets[1].out[i] = n > 1 ? work + (size_t)(1 + i) * plane : nullptr;
+    }
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    nz_geom g = nz_geom_from_stripe(*st);
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int j = 0; j < n; j++) {
+        const int to = pingpong_set(n, j);
+        nz_stripe_window(*st, HYD_STRIPE_RADIUS * (n - 1 - j), &g.or0, &g.or1);
+        nz_hydraulic_planes p;
+        for (int i = 0; i < 6; i++) {
+            p.in[i] = j == 0 ? (first ? nullptr : state_in[i]) : sets[to ^ 1].in[i];
+            p.out[i] = sets[to].out[i];
+        }
+        if (j == n - 1) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_hydraulic_stripe(ctx->stream, j == 0 ? height_in : hs[to ^ 1], hs[to], p, k, g, st->own0, st->own1,
+                                          first && j == 0, last && j == n - 1, ex));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// stream-power fluvial erosion with drainage area (new-framework feature, include/noize_hip.h, nz_fluvial.hip)
+// ---------------------------------------------------------------------------------------------
+// work planes of count * res^2 floats each: 0 and 1 the drainage planes the launches ping-pong between -- in such an order
+// that the last launch writes plane 0 -- and 2 the in-place forms' second height plane
+constexpr int FLU_PLANES = 3;
+
+extern "C" size_t nz_fluvial_erosion_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? (size_t)FLU_PLANES * resolution * resolution * count : 0;
+}
+
+// the scalars of a nz_fluvial_desc as the launches take them
+static int32_t check_fluvial(const nz_fluvial_desc *d, nz_fluvial_params *k) {
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(d->iterations >= 0, "iterations %d < 0", d->iterations);
+    const struct { const char *name; float v; bool signed_; } args[] = {
+        {"erodibility", d->erodibility, false}, {"uplift", d->uplift, false}, {"dt", d->dt, false},
+        {"rain", d->rain, false},               {"seaLevel", d->seaLevel, true}};
+    for (const auto &a : args) {
+        NZ_REQUIRE(std::isfinite(a.v), "%s is not finite", a.name);
+        NZ_REQUIRE(a.signed_ || a.v >= 0.0f, "%s %g < 0", a.name, (double)a.v);
+    }
+    *k = nz_fluvial_params{d->erodibility, d->uplift, d->dt, d->rain, d->seaLevel};
+    return NZ_OK;
+}
+
+// The read-only planes of the desc of a tile-shaped call against the planes the call writes: h0 / h1 the height plane(s)
+// (h1 may be NULL), n floats each like every plane of the desc, and `work`
+static int32_t check_fluvial_planes(const nz_fluvial_desc &d, const float *h0, const float *h1, const float *work, size_t n) {
+    const nz_named_plane reads[] = {
+        {"drainageIn", d.drainageIn, n}, {"rainMap", d.rainMap, n}, {"hardness", d.hardness, n}, {"upliftMap", d.upliftMap, n}};
+    const nz_named_plane writes[] = {{"src", h0, n}, {"the write plane", h1, n}, {"work", work, (size_t)FLU_PLANES * n}};
+    for (const auto &r : reads)
+        for (const auto &w : writes) NZ_REQUIRE(!nz_planes_overlap(r.p, n, w.p, w.floats), "%s overlaps %s", r.name, w.name);
+    return NZ_OK;
+}
+
+// The body of every tile-shaped entry behind its NULL checks: the desc's checks, then desc->iterations launches on `count`
+// tiles.  The height ping-pongs between h0 and h1 (height_pingpong); h1 NULL: the in-place forms, which keep the result in
+// h0 and take work plane 2 as h1.  The drainage ping-pongs between work planes 0 and 1 (pingpong_set).  The first launch reads
+// drainageIn, or the start state rain * rainMap written here into the plane it does not write, or -- without either -- no
+// drainage plane at all.  Without an iteration plane 0 receives the start state.
+static int32_t fluvial_series(nz_ctx *ctx, float *h0, float *h1, float *work, int res, int count, const nz_fluvial_desc *desc,
+                              nz_handle *out, bool *in_h1) {
+    const size_t n = (size_t)res * res * count;
+    nz_fluvial_params k;
+    NZ_TRY(check_fluvial(desc, &k));
+    const nz_fluvial_desc &d = *desc;
+    NZ_TRY(check_fluvial_planes(d, h0, h1, work, n));
+    const bool keep_h0 = !h1;
+    if (keep_h0) h1 = work + (size_t)(FLU_PLANES - 1) * n;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // (the last launch below is armed)
+    const int iterations = d.iterations;
+    float *planes[2] = {work, work + n};
+    if (iterations == 0) {
+        *in_h1 = false;
+        nz_ctx_arm_last_launch(ctx);
+        if (d.drainageIn) return nz_launch_copy(ctx->stream, work, d.drainageIn, n);
+        if (d.rainMap) return nz_launch_fluvial_start(ctx->stream, work, d.rainMap, k.rain, n);
+        return nz_launch_fill(ctx->stream, work, n, k.rain);
+    }
+    float *cur, *nxt;
+    NZ_TRY(height_pingpong(ctx, h0, h1, n, iterations, keep_h0, &cur, &nxt, in_h1));
+    const float *a_in = d.drainageIn;
+    if (!a_in && d.rainMap) {
+        NZ_TRY(nz_launch_fluvial_start(ctx->stream, planes[iterations & 1], d.rainMap, k.rain, n));
+        a_in = planes[iterations & 1];
+    }
+    for (int it = 0; it < iterations; it++) {
+        float *a_out = planes[pingpong_set(iterations, it)];
+        if (it == iterations - 1) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fluvial(ctx->stream, cur, nxt, a_in, a_out, k, res, count, d.rainMap, d.hardness, d.upliftMap));
+        a_in = a_out;
+        std::swap(cur, nxt);
+    }
+    return NZ_OK;
+}
+
+static int32_t fluvial_stage_impl(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
+                                  int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    NZ_REQUIRE(src && work, "src/work is NULL");
+    bool in_h1;
+    NZ_TRY(fluvial_series(ctx, src, nullptr, work, resolution, count, desc, out, &in_h1));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fluvial_erosion(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc, int32_t resolution,
+                                      nz_handle dep, nz_handle *out) {
+    return fluvial_stage_impl(ctx, src, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_fluvial_erosion_batch(nz_ctx *ctx, float *src, float *work, const nz_fluvial_desc *desc,
+                                            int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    return fluvial_stage_impl(ctx, src, work, desc, resolution, count, dep, out);
+}
+
+extern "C" int32_t nz_fluvial_erosion_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_fluvial_desc *desc,
+                                         nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    NZ_REQUIRE(work, "work is NULL");
+    bool in_h1;
+    NZ_TRY(fluvial_series(ctx, tile->read, tile->write, work, tile->resolution, tile->count, desc, out, &in_h1));
+    rw_swap(tile, in_h1);
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---- the stripe form (include/noize_hip.h): n iterations of one call on a row stripe, one launch each ----
+constexpr int FLU_STRIPE_RADIUS = 2;  // rows one iteration reads beyond the rows it produces: receivers at 1, their heights at 2
+
+extern "C" int32_t nz_fluvial_stripe_halo_rows(int32_t iterations) {
+    return iterations > 0 ? FLU_STRIPE_RADIUS * iterations : 0;
+}
+
+extern "C" size_t nz_fluvial_stripe_work_floats(const nz_stripe *st, int32_t iterations) {
+    return iterations > 1 ? 2 * nz_stripe_plane_floats(st) : 0;
+}
+
+extern "C" int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float *height_out, float *drainage_out, float *work,
+                                     const nz_stripe *st, const nz_fluvial_desc *desc, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(desc, "desc is NULL");
+    const int n = desc->iterations;
+    NZ_REQUIRE(n >= 1, "iterations %d < 1", n);
+    NZ_REQUIRE(n <= INT32_MAX / FLU_STRIPE_RADIUS, "iterations %d out of range", n);
+    nz_fluvial_params k;
+    NZ_TRY(check_fluvial(desc, &k));
+    NZ_TRY(nz_check_stripe(st, FLU_STRIPE_RADIUS * n));
+    NZ_REQUIRE(height_in && height_out && drainage_out, "height_in/height_out/drainage_out is NULL");
+    NZ_REQUIRE(n == 1 || work, "work is NULL");
+    const size_t span = nz_stripe_span(*st), plane = nz_stripe_plane_floats(st);
+    const nz_named_plane reads[] = {{"height_in", height_in, span},   {"drainageIn", desc->drainageIn, span},
+                                    {"rainMap", desc->rainMap, span}, {"hardness", desc->hardness, span},
+                                    {"upliftMap", desc->upliftMap, span}};
+    const nz_named_plane writes[] = {{"height_out", height_out, span}, {"drainage_out", drainage_out, span},
+                                     {"work", n > 1 ? work : nullptr, 2 * plane}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    float *hs[2] = {height_out, work}, *as[2] = {drainage_out, n > 1 ? work + plane : nullptr};  // pingpong_set
+    const int zlo = nz_stripe_grid_lo(*st), zhi = nz_stripe_grid_hi(*st) - 1;
+    nz_geom g = nz_geom_from_stripe(*st);
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int j = 0; j < n; j++) {
+        const int to = pingpong_set(n, j);
+        nz_stripe_window(*st, FLU_STRIPE_RADIUS * (n - 1 - j), &g.or0, &g.or1);
+        if (j == n - 1) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fluvial_stripe(ctx->stream, j == 0 ? height_in : hs[to ^ 1], hs[to],
+                                        j == 0 ? desc->drainageIn : as[to ^ 1], as[to], k, g, zlo, zhi, desc->rainMap,
+                                        desc->hardness, desc->upliftMap));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
+// ---------------------------------------------------------------------------------------------
+// `work` in floats: 16 status words ({passes, converged, changed[3]}, the rest spare), two generations of per-tile bytes,
+// each rounded up to 16 bytes, and the W planes the passes alternate between: both of them in the tile forms (count * res^2
+// floats each), one in the stripe form, whose other W plane is the caller's `w`.  One pass is one launch whatever its depth,
+// so the launch-series planner (nz_split_iterations) has nothing to split here.
+namespace {
+constexpr size_t FILL_STATUS = 16;
+constexpr int FILL_SWEEPS = 16;  // measured: DESIGN.md section 4
+std::atomic<int> fill_sweeps{FILL_SWEEPS};  // nz_debug_fill_sweeps may be called while another thread runs an entry
+struct fill_layout {
+    size_t gen_floats, n;  // one generation of tile bytes in floats, floats of one W plane
+    size_t total(int w_planes) const { return FILL_STATUS + 2 * gen_floats + w_planes * n; }
+};
+fill_layout fill_layout_of(int res, int count) {
+    const size_t tiles = (size_t)((res + 63) / 64) * ((res + 15) / 16) * count;
+    return fill_layout{(tiles + 15) / 16 * 4, (size_t)res * res * count};
+}
+fill_layout fill_stripe_layout(const nz_stripe &st) {
+    const size_t tiles = (size_t)((st.cols + 63) / 64) * ((st.own1 - st.own0 + 15) / 16);
+    return fill_layout{(tiles + 15) / 16 * 4, nz_stripe_plane_floats(&st)};
+}
+struct fill_work { int *status; unsigned char *flags[2]; float *planes; };  // planes: the first (or only) W plane of `work`
+fill_work fill_carve(float *work, const fill_layout &L) {
+    unsigned char *bytes = reinterpret_cast<unsigned char *>(work + FILL_STATUS);
+    return fill_work{reinterpret_cast<int *>(work), {bytes, bytes + 4 * L.gen_floats}, work + FILL_STATUS + 2 * L.gen_floats};
+}
+}  // namespace
+
+static int32_t check_fill_desc(const nz_fill_desc *d) {
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(std::isfinite(d->epsilon), "epsilon is not finite");
+    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(d->epsilon >= 0.0f, "epsilon %g < 0", (double)d->epsilon);
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    return NZ_OK;
+}
+
+extern "C" size_t nz_fill_depressions_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? fill_layout_of(resolution, count).total(2) : 0;
+}
+
+extern "C" int32_t nz_debug_fill_sweeps(int32_t sweeps) {
+    return fill_sweeps.exchange(sweeps > 0 ? sweeps : FILL_SWEEPS);
+}
+
+// h: the plane that holds the input and receives the result; other: the write plane of an _rw pair or NULL
+static int32_t fill_impl(nz_ctx *ctx, float *h, const float *other, float *work, const nz_fill_desc *d, int res, int count,
+                         nz_handle *out) {
+    NZ_REQUIRE(h && work, "src/work is NULL");
+    NZ_TRY(check_fill_desc(d));
+    const fill_layout L = fill_layout_of(res, count);
+    NZ_REQUIRE(!nz_planes_overlap(d->depth, L.n, h, L.n), "depth overlaps src");
+    NZ_REQUIRE(!nz_planes_overlap(d->depth, L.n, other, L.n), "depth overlaps the write plane");
+    NZ_REQUIRE(!nz_planes_overlap(d->depth, L.n, work, L.total(2)), "depth overlaps work");
+    const fill_work c = fill_carve(work, L);
+    float *planes[2] = {c.planes, c.planes + L.n};
+    const float eps = d->epsilon + 0.0f;  // -0 -> +0
+    const int sweeps = fill_sweeps.load();  // one cap for the whole series
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int p = 0; p < d->maxPasses; p++)  // pass p writes plane p & 1 and byte generation p & 1
+        NZ_TRY(nz_launch_fill_pass(ctx->stream, h, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1], c.status,
+                                   c.flags[(p - 1) & 1], c.flags[p & 1], eps, d->seaLevel, res, count, p, sweeps));
+    nz_ctx_arm_last_launch(ctx);
+    // a converged series holds the fixed point in both planes, so either serves
+    NZ_TRY(nz_launch_fill_finalise(ctx->stream, h, planes[0], d->depth, c.status, L.n));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fill_depressions(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc, int32_t resolution,
+                                       nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, 1));
+    return fill_impl(ctx, src, nullptr, work, desc, resolution, 1, out);
+}
+
+extern "C" int32_t nz_fill_depressions_batch(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc,
+                                             int32_t resolution, int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_batch(resolution, count));
+    return fill_impl(ctx, src, nullptr, work, desc, resolution, count, out);
+}
+
+extern "C" int32_t nz_fill_depressions_rw(nz_ctx *ctx, nz_rw_tile *tile, float *work, const nz_fill_desc *desc, nz_handle dep,
+                                          nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_rw(tile));
+    return fill_impl(ctx, tile->read, tile->write, work, desc, tile->resolution, tile->count, out);
+}
+
+// ---- the stripe form (include/noize_hip.h): one round of passes on the owned rows against one frozen row on each side ----
+extern "C" int32_t nz_fill_stripe_halo_rows(void) { return 1; }
+
+extern "C" size_t nz_fill_stripe_work_floats(const nz_stripe *st) {
+    if (!nz_stripe_plane_floats(st) || st->own0 < 0 || st->own1 < st->own0) return 0;
+    return fill_stripe_layout(*st).total(1);
+}
+
+extern "C" int32_t nz_fill_stripe(nz_ctx *ctx, const float *height, float *w, float *work, const nz_stripe *st,
+                                  const nz_fill_desc *desc, int32_t first, const int32_t *proceed, int32_t *changed,
+                                  nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_fill_desc(desc));
+    NZ_TRY(nz_check_stripe(st, 1));
+    NZ_REQUIRE(height && w && work, "height/w/work is NULL");
+    NZ_REQUIRE(changed, "changed is NULL");
+    const nz_geom g = nz_geom_from_stripe(*st);
+    const fill_layout L = fill_stripe_layout(*st);
+    const size_t span = nz_stripe_span(*st), total = L.total(1);
+    NZ_REQUIRE(!nz_planes_overlap(w, span, height, span), "w overlaps height");
+    NZ_REQUIRE(!nz_planes_overlap(work, total, height, span), "work overlaps height");
+    NZ_REQUIRE(!nz_planes_overlap(work, total, w, span), "work overlaps w");
+    const nz_named_plane planes_of_call[] = {{"height", height, span}, {"w", w, span}, {"work", work, total}};
+    for (const auto &p : planes_of_call) {  // the two words are ints, not planes of floats
+        NZ_REQUIRE(!nz_bytes_overlap(changed, 4, p.p, p.floats * 4), "changed overlaps a plane");
+        NZ_REQUIRE(!nz_bytes_overlap(proceed, 4, p.p, p.floats * 4), "proceed overlaps a plane");
+    }
+    const fill_work c = fill_carve(work, L);
+    float *planes[2] = {w, c.planes};  // pass p reads plane p & 1 and writes the other
+    const float eps = desc->epsilon + 0.0f;  // -0 -> +0
+    const int sweeps = fill_sweeps.load(), passes = desc->maxPasses;
+    const int zlo = nz_stripe_grid_lo(*st), zhi = nz_stripe_grid_hi(*st) - 1;
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_fill_round_begin(ctx->stream, c.status, proceed, changed, first != 0));
+    for (int p = 0; p < passes; p++) {
+        if (p == passes - 1 && !(passes & 1)) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fill_stripe_pass(ctx->stream, height, planes[p & 1], planes[(p + 1) & 1], w, c.status,
+                                          c.flags[(p + 1) & 1], c.flags[p & 1], changed, eps, desc->seaLevel, g, zlo, zhi,
+                                          first != 0, p, sweeps));
+    }
+    if (passes & 1) {  // the last pass wrote the work plane
+        nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fill_round_end(ctx->stream, w, planes[1], c.status, passes, g));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const float *w, float *depth, const nz_stripe *st,
+                                           const int32_t *converged, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(height && w, "height/w is NULL");
+    NZ_REQUIRE(converged, "converged is NULL");
+    const size_t span = nz_stripe_span(*st);
+    NZ_REQUIRE(!nz_planes_overlap(height, span, w, span), "height overlaps w");
+    NZ_REQUIRE(!nz_planes_overlap(depth, span, height, span), "depth overlaps height");
+    NZ_REQUIRE(!nz_planes_overlap(depth, span, w, span), "depth overlaps w");
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_fill_stripe_finalise(ctx->stream, height, w, depth, converged, nz_geom_from_stripe(*st)));
+    return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// upsample / downsample (new-framework feature, include/noize_hip.h, nz_resample.hip)
+// ---------------------------------------------------------------------------------------------
+static int32_t check_resample(int32_t factor, int32_t filter) {
+    NZ_REQUIRE(factor == 2 || factor == 4 || factor == 8, "factor %d is not 2, 4 or 8", factor);
+    NZ_REQUIRE(filter >= NZ_RESAMPLE_NEAREST && filter <= NZ_RESAMPLE_CATMULL_ROM, "filter %d is not a resample filter",
+               filter);
+    return NZ_OK;
+}
+
+// the planes of a call: src read, dst written (fine_n / coarse_n floats each way round), base NULL, dst or apart from dst
+static int32_t check_resample_planes(const float *src, size_t src_n, const float *dst, size_t dst_n, const float *base) {
+    NZ_REQUIRE(src, "src is NULL");
+    NZ_REQUIRE(dst, "dst is NULL");
+    NZ_REQUIRE(dst_n < ((size_t)1 << 31), "dst: an output of %zu cells (2^31 or more)", dst_n);
+    NZ_REQUIRE(!nz_planes_overlap(dst, dst_n, src, src_n), "dst overlaps src");
+    NZ_REQUIRE(!base || base == dst || !nz_planes_overlap(dst, dst_n, base, dst_n), "base partly overlaps dst");
+    return NZ_OK;
+}
+
+static int32_t upsample_impl(nz_ctx *ctx, const float *src, int32_t res, float *dst, int32_t factor, int32_t filter,
+                             const float *base, int32_t count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, filter));
+    NZ_REQUIRE(res >= 1, "srcResolution %d < 1", res);
+    NZ_REQUIRE(count >= 1 && count <= 65535, "count %d out of range [1,65535]", count);
+    // 46340^2 < 2^31 <= 46341^2: bounding the side first keeps every product below from wrapping
+    NZ_REQUIRE(res <= 46340 / factor, "dst: an output of 2^31 cells or more (srcResolution %d x factor %d)", res, factor);
+    const size_t fine = (size_t)res * factor;
+    NZ_TRY(check_resample_planes(src, (size_t)count * res * res, dst, (size_t)count * fine * fine, base));
+    nz_up_geom g{};
+    g.ccols = g.cpitch = g.crows = g.cgrows = res;
+    g.fcols = g.fpitch = g.w1 = (int)fine;
+    g.cstride = (size_t)res * res;
+    g.fstride = fine * fine;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_upsample(ctx->stream, src, dst, base, g, factor, filter, count));
+    return nz_ctx_finish(ctx, out);
+}
+
+static int32_t downsample_impl(nz_ctx *ctx, const float *src, int32_t res, float *dst, int32_t factor, int32_t count,
+                               nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, NZ_RESAMPLE_NEAREST));
+    NZ_REQUIRE(res >= 1, "srcResolution %d < 1", res);
+    NZ_REQUIRE(res % factor == 0, "srcResolution %d is not divisible by factor %d", res, factor);
+    NZ_REQUIRE(count >= 1 && count <= 65535, "count %d out of range [1,65535]", count);
+    const size_t coarse = (size_t)(res / factor);
+    NZ_REQUIRE(res <= 46340 && (size_t)count * res * res < ((size_t)1 << 31), "src: an input of 2^31 cells or more");
+    NZ_TRY(check_resample_planes(src, (size_t)count * res * res, dst, (size_t)count * coarse * coarse, nullptr));
+    nz_down_geom g{};
+    g.ccols = g.cpitch = g.w1 = (int)coarse;
+    g.fpitch = res;
+    g.cstride = coarse * coarse;
+    g.fstride = (size_t)res * res;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_downsample(ctx->stream, src, dst, g, factor, count));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_upsample(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                               int32_t filter, const float *base, nz_handle dep, nz_handle *out) {
+    return upsample_impl(ctx, src, srcResolution, dst, factor, filter, base, 1, dep, out);
+}
+
+extern "C" int32_t nz_upsample_batch(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                                     int32_t filter, const float *base, int32_t count, nz_handle dep, nz_handle *out) {
+    return upsample_impl(ctx, src, srcResolution, dst, factor, filter, base, count, dep, out);
+}
+
+extern "C" int32_t nz_downsample(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                                 nz_handle dep, nz_handle *out) {
+    return downsample_impl(ctx, src, srcResolution, dst, factor, 1, dep, out);
+}
+
+extern "C" int32_t nz_downsample_batch(nz_ctx *ctx, const float *src, int32_t srcResolution, float *dst, int32_t factor,
+                                       int32_t count, nz_handle dep, nz_handle *out) {
+    return downsample_impl(ctx, src, srcResolution, dst, factor, count, dep, out);
+}
+
+extern "C" int32_t nz_upsample_stripe_halo_rows(int32_t filter) {
+    return filter >= NZ_RESAMPLE_NEAREST && filter <= NZ_RESAMPLE_CATMULL_ROM ? nz_resample_halo(filter) : 0;
+}
+
+// the two stripes of a resampling call: each a valid stripe of its own grid (no ghost rows demanded of the output), the
+// fine grid f times the coarse one
+static int32_t check_resample_stripes(const nz_stripe *coarse, const char *cname, const nz_stripe *fine, const char *fname,
+                                      int factor) {
+    NZ_REQUIRE(coarse, "%s is NULL", cname);
+    NZ_REQUIRE(fine, "%s is NULL", fname);
+    NZ_TRY(nz_check_stripe(coarse, 0));
+    NZ_TRY(nz_check_stripe(fine, 0));
+    NZ_REQUIRE((int64_t)coarse->cols * factor == fine->cols && (int64_t)coarse->grows * factor == fine->grows,
+               "%s / %s: the fine grid %d x %d is not %d times the coarse grid %d x %d", cname, fname, fine->grows,
+               fine->cols, factor, coarse->grows, coarse->cols);
+    return NZ_OK;
+}
+
+extern "C" int32_t nz_upsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst,
+                                      const nz_stripe *dstSt, int32_t factor, int32_t filter, const float *base,
+                                      nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, filter));
+    NZ_TRY(check_resample_stripes(srcSt, "srcSt", dstSt, "dstSt", factor));
+    NZ_REQUIRE(src, "src is NULL");
+    NZ_REQUIRE(dst, "dst is NULL");
+    NZ_REQUIRE(nz_stripe_plane_floats(dstSt) < ((size_t)1 << 31), "dst: an output of 2^31 cells or more");
+    NZ_REQUIRE(!nz_planes_overlap(dst, nz_stripe_span(*dstSt), src, nz_stripe_span(*srcSt)), "dst overlaps src");
+    NZ_REQUIRE(!base || base == dst || !nz_planes_overlap(dst, nz_stripe_span(*dstSt), base, nz_stripe_span(*dstSt)),
+               "base partly overlaps dst");
+    nz_up_geom g{};
+    g.ccols = srcSt->cols;
+    g.cpitch = nz_stripe_pitch(*srcSt);
+    g.crows = srcSt->rows;
+    g.cgrow0 = srcSt->grow0;
+    g.cgrows = srcSt->grows;
+    g.fcols = dstSt->cols;
+    g.fpitch = nz_stripe_pitch(*dstSt);
+    g.fgrow0 = dstSt->grow0;
+    g.w0 = dstSt->own0;
+    g.w1 = dstSt->own1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_upsample(ctx->stream, src, dst, base, g, factor, filter, 1));  // refuses a missing ghost row
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_downsample_stripe(nz_ctx *ctx, const float *src, const nz_stripe *srcSt, float *dst,
+                                        const nz_stripe *dstSt, int32_t factor, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_resample(factor, NZ_RESAMPLE_NEAREST));
+    NZ_TRY(check_resample_stripes(dstSt, "dstSt", srcSt, "srcSt", factor));
+    NZ_REQUIRE(src, "src is NULL");
+    NZ_REQUIRE(dst, "dst is NULL");
+    NZ_REQUIRE(nz_stripe_plane_floats(srcSt) < ((size_t)1 << 31), "src: an input of 2^31 cells or more");
+    NZ_REQUIRE(!nz_planes_overlap(dst, nz_stripe_span(*dstSt), src, nz_stripe_span(*srcSt)), "dst overlaps src");
+    // output global rows [g0, g1) read fine global rows [f g0, f g1): all of them in the source buffer
+    const int64_t f0 = (int64_t)(dstSt->own0 + dstSt->grow0) * factor - srcSt->grow0;
+    const int64_t f1 = (int64_t)(dstSt->own1 + dstSt->grow0) * factor - srcSt->grow0;
+    NZ_REQUIRE(dstSt->own1 == dstSt->own0 || (f0 >= 0 && f1 <= srcSt->rows),
+               "srcSt: fine rows [%lld, %lld) of the buffer are required, it holds %d", (long long)f0, (long long)f1,
+               srcSt->rows);
+    nz_down_geom g{};
+    g.ccols = dstSt->cols;
+    g.cpitch = nz_stripe_pitch(*dstSt);
+    g.cgrow0 = dstSt->grow0;
+    g.fpitch = nz_stripe_pitch(*srcSt);
+    g.fgrow0 = srcSt->grow0;
+    g.w0 = dstSt->own0;
+    g.w1 = dstSt->own1;
+    nz_ctx_handle_rides(ctx, out != nullptr);  // one launch, nothing behind it
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_downsample(ctx->stream, src, dst, g, factor, 1));
+    return nz_ctx_finish(ctx, out);
+}

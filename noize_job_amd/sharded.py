@@ -252,22 +252,70 @@ def _copy_ghost_rows(reqs, plans, copy_rows):
                 copy_rows(t, pl.own1, reqs[pl.down][0][i], q.own0, down_rows)
 
 
+VOTE = "vote"  # a generator's request (VOTE, word): the maximum of every rank's word, in place, and its value sent back
+
+
+def _stage_params(defaults, what, params, kw=None):
+    """`defaults` overridden from a dict and / or keyword arguments; a name that is not among them is not `what`."""
+    prm = dict(defaults)
+    for src in (params or {}, kw or {}):
+        for name, v in src.items():
+            assert name in prm, "%s is not %s" % (name, what)
+            prm[name] = v
+    return prm
+
+
+def _run_steps(gen, comm, plan):
+    """Drives one rank's *_steps generator to its end and returns its value.  An exchange request (planes, up_rows,
+    down_rows) is completed through comm.exchange before the generator goes on, and answered with None; a vote request
+    (VOTE, word) goes through comm.allreduce_max, whose value is sent back (TorchComm, NativeComm, NoComm)."""
+    answer = None
+    try:
+        while True:
+            req = gen.send(answer)
+            if req[0] == VOTE:
+                answer = comm.allreduce_max(req[1])
+            else:
+                comm.exchange(req[0], plan, req[1], req[2])
+                answer = None
+    except StopIteration as done:
+        return done.value
+
+
+def _run_steps_lockstep(gens, plans, copy_rows):
+    """All ranks of a grid inside ONE process (tests, single-GPU rehearsal): the per-rank generators advance in lockstep
+    and every rank's value is returned.  Ghost rows are copied directly, copy_rows(dst_plane, d0, src_plane, s0, n); a
+    vote is the maximum taken in process and written back to every rank's word."""
+    results = [None] * len(gens)
+    answer = None
+    while True:
+        reqs = []
+        for r, g in enumerate(gens):
+            try:
+                reqs.append(g.send(answer))
+            except StopIteration as done:
+                results[r] = done.value
+                reqs.append(None)
+        if all(r is None for r in reqs):
+            return results
+        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
+        votes = [r[0] == VOTE for r in reqs]
+        assert all(votes) or not any(votes), "ranks left the schedule at different points"
+        if votes[0]:
+            answer = max(int(r[1][0]) for r in reqs)
+            for r in reqs:
+                r[1].fill_(answer)
+        else:
+            _copy_ghost_rows(reqs, plans, copy_rows)
+            answer = None
+
+
 def run_pipeline_lockstep(ops_list, plans, p, bufs_list, copy_rows):
     """All ranks of a grid inside ONE process (tests, single-GPU rehearsal): the per-rank generators
     advance in lockstep and ghost rows are copied directly, copy_rows(dst_plane, d0, src_plane, s0, n)."""
     results = [[] for _ in plans]
-    gens = [pipeline_steps(o, pl, p, b, r) for o, pl, b, r in zip(ops_list, plans, bufs_list, results)]
-    while True:
-        reqs = []
-        for g in gens:
-            try:
-                reqs.append(next(g))
-            except StopIteration:
-                reqs.append(None)
-        if all(r is None for r in reqs):
-            break
-        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
-        _copy_ghost_rows(reqs, plans, copy_rows)
+    _run_steps_lockstep([pipeline_steps(o, pl, p, b, r) for o, pl, b, r in zip(ops_list, plans, bufs_list, results)],
+                        plans, copy_rows)
     return [r[0] for r in results]
 
 
@@ -288,12 +336,7 @@ def hydraulic_halo_rows(k):
 def hydraulic_params(params=None, **kw):
     """The scalar fields of nz_hydraulic_desc (and `border`) from a dict and / or keyword arguments, the hosts' stage
     defaults for the rest.  The four planes of the desc are per-rank buffers and travel in `bufs`."""
-    prm = dict(HYDRAULIC_DEFAULTS)
-    for src in (params or {}, kw):
-        for name, v in src.items():
-            assert name in prm, "%s is not a scalar field of nz_hydraulic_desc" % name
-            prm[name] = v
-    return prm
+    return _stage_params(HYDRAULIC_DEFAULTS, "a scalar field of nz_hydraulic_desc", params, kw)
 
 
 def hydraulic_steps(ops, plan, params, bufs, exchange_every=1):
@@ -327,31 +370,13 @@ def hydraulic_steps(ops, plan, params, bufs, exchange_every=1):
 def run_hydraulic(ops, comm, plan, params, bufs, exchange_every=1):
     """hydraulic_steps on this rank, every exchange completed before the block that reads it (TorchComm, NativeComm,
     NoComm); returns (height plane, water plane)."""
-    gen = hydraulic_steps(ops, plan, params, bufs, exchange_every)
-    try:
-        while True:
-            planes, up_rows, down_rows = next(gen)
-            comm.exchange(planes, plan, up_rows, down_rows)
-    except StopIteration as done:
-        return done.value
+    return _run_steps(hydraulic_steps(ops, plan, params, bufs, exchange_every), comm, plan)
 
 
 def run_hydraulic_lockstep(ops_list, plans, params, bufs_list, copy_rows, exchange_every=1):
     """All ranks inside one process, as run_pipeline_lockstep; returns every rank's (height plane, water plane)."""
     gens = [hydraulic_steps(o, pl, params, b, exchange_every) for o, pl, b in zip(ops_list, plans, bufs_list)]
-    results = [None] * len(gens)
-    while True:
-        reqs = []
-        for r, g in enumerate(gens):
-            try:
-                reqs.append(next(g))
-            except StopIteration as done:
-                results[r] = done.value
-                reqs.append(None)
-        if all(r is None for r in reqs):
-            return results
-        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
-        _copy_ghost_rows(reqs, plans, copy_rows)
+    return _run_steps_lockstep(gens, plans, copy_rows)
 
 
 # ---- stream-power fluvial erosion on row stripes (nz_fluvial_stripe) ------------------------------------------------------
@@ -369,12 +394,7 @@ def fluvial_halo_rows(k):
 def fluvial_params(params=None, **kw):
     """The scalar fields of nz_fluvial_desc from a dict and / or keyword arguments, the hosts' stage defaults for the
     rest.  The maps of the desc are per-rank buffers and travel in `bufs`."""
-    prm = dict(FLUVIAL_DEFAULTS)
-    for src in (params or {}, kw):
-        for name, v in src.items():
-            assert name in prm, "%s is not a scalar field of nz_fluvial_desc" % name
-            prm[name] = v
-    return prm
+    return _stage_params(FLUVIAL_DEFAULTS, "a scalar field of nz_fluvial_desc", params, kw)
 
 
 def fluvial_steps(ops, plan, params, bufs, exchange_every=1):
@@ -409,36 +429,17 @@ def fluvial_steps(ops, plan, params, bufs, exchange_every=1):
 def run_fluvial(ops, comm, plan, params, bufs, exchange_every=1):
     """fluvial_steps on this rank, every exchange completed before the block that reads it (TorchComm, NativeComm, NoComm);
     returns (height plane, drainage plane)."""
-    gen = fluvial_steps(ops, plan, params, bufs, exchange_every)
-    try:
-        while True:
-            planes, up_rows, down_rows = next(gen)
-            comm.exchange(planes, plan, up_rows, down_rows)
-    except StopIteration as done:
-        return done.value
+    return _run_steps(fluvial_steps(ops, plan, params, bufs, exchange_every), comm, plan)
 
 
 def run_fluvial_lockstep(ops_list, plans, params, bufs_list, copy_rows, exchange_every=1):
     """All ranks inside one process, as run_hydraulic_lockstep; returns every rank's (height plane, drainage plane)."""
     gens = [fluvial_steps(o, pl, params, b, exchange_every) for o, pl, b in zip(ops_list, plans, bufs_list)]
-    results = [None] * len(gens)
-    while True:
-        reqs = []
-        for r, g in enumerate(gens):
-            try:
-                reqs.append(next(g))
-            except StopIteration as done:
-                results[r] = done.value
-                reqs.append(None)
-        if all(r is None for r in reqs):
-            return results
-        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
-        _copy_ghost_rows(reqs, plans, copy_rows)
+    return _run_steps_lockstep(gens, plans, copy_rows)
 
 
 # ---- depression filling on row stripes (nz_fill_stripe) -----------------------------------------------------------------
 FILL_DEFAULTS = dict(epsilon=1e-4, seaLevel=-3.4028234663852886e38, maxPasses=64, maxRounds=64)
-VOTE = "vote"  # a generator's request (VOTE, word): the maximum of every rank's word, in place, and its value sent back
 
 
 def fill_steps(ops, plan, params, bufs):
@@ -453,10 +454,7 @@ def fill_steps(ops, plan, params, bufs):
     rank: all or nothing.  bufs: "H" (the heights on the owned rows; receives the result), "W", "work"
     (nz_fill_stripe_work_floats), "words" (int32[3]) and optionally "depth"; plan.halo >= 1.
     Returns (height plane, depth plane or None, rounds, converged)."""
-    prm = dict(FILL_DEFAULTS)
-    for name, v in (params or {}).items():
-        assert name in prm, "%s is not a parameter of the sharded fill" % name
-        prm[name] = v
+    prm = _stage_params(FILL_DEFAULTS, "a parameter of the sharded fill", params)
     words = bufs["words"]
     vote, rounds = 1, 0
     while vote != 0 and rounds < prm["maxRounds"]:
@@ -474,45 +472,14 @@ def fill_steps(ops, plan, params, bufs):
 def run_fill(ops, comm, plan, params, bufs):
     """fill_steps on this rank: exchanges through comm.exchange, votes through comm.allreduce_max (TorchComm, NativeComm,
     NoComm); returns (height plane, depth plane or None, rounds, converged)."""
-    gen = fill_steps(ops, plan, params, bufs)
-    answer = None
-    try:
-        while True:
-            req = gen.send(answer)
-            if req[0] == VOTE:
-                answer = comm.allreduce_max(req[1])
-            else:
-                comm.exchange(req[0], plan, req[1], req[2])
-                answer = None
-    except StopIteration as done:
-        return done.value
+    return _run_steps(fill_steps(ops, plan, params, bufs), comm, plan)
 
 
 def run_fill_lockstep(ops_list, plans, params, bufs_list, copy_rows):
     """All ranks inside one process, as run_fluvial_lockstep; a vote is the maximum taken in process and written back to
     every rank's word."""
-    gens = [fill_steps(o, pl, params, b) for o, pl, b in zip(ops_list, plans, bufs_list)]
-    results = [None] * len(gens)
-    answer = None
-    while True:
-        reqs = []
-        for r, g in enumerate(gens):
-            try:
-                reqs.append(g.send(answer))
-            except StopIteration as done:
-                results[r] = done.value
-                reqs.append(None)
-        if all(r is None for r in reqs):
-            return results
-        assert all(r is not None for r in reqs), "ranks left the schedule at different points"
-        if reqs[0][0] == VOTE:
-            assert all(r[0] == VOTE for r in reqs), "ranks left the schedule at different points"
-            answer = max(int(r[1][0]) for r in reqs)
-            for r in reqs:
-                r[1].fill_(answer)
-        else:
-            _copy_ghost_rows(reqs, plans, copy_rows)
-            answer = None
+    return _run_steps_lockstep([fill_steps(o, pl, params, b) for o, pl, b in zip(ops_list, plans, bufs_list)], plans,
+                               copy_rows)
 
 
 class HipStripeOps:
