@@ -65,6 +65,14 @@ namespace xshazwar.noize.hip {
         public IntPtr depth;
     }
 
+    // the drainage-area stage's scalars and the optional rain map (nz_drainage_area*); IntPtr.Zero = rain everywhere
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzDrainageDesc {                                                                   // nz_drainage_desc
+        public float rain, seaLevel;
+        public int maxPasses;
+        public IntPtr rainMap;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

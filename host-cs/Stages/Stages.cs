@@ -470,6 +470,61 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; lakes?.Dispose(); lakes = null; }
     }
 
+    // Drainage area (new-framework feature; the model: nz_drainage_area in include/noize_hip.h): the exact flow accumulation
+    // over the steepest-descent tree of the payload's heights -- the river map -- in one call.  The heights pass through
+    // untouched.  Once the handle completes, Drainage holds the plane of the last payload (count * resolution^2 floats);
+    // Passes and Converged wait for the handle and read the status words.  seaLevel: cells at or below it are outlets like
+    // the border (-float.MaxValue: off).  rainMap: a plane of the payload's size the caller supplies and keeps alive.
+    // maxPasses null means the default, 64 + resolution / 4; a budget that runs out is no error: Converged is false and the
+    // drainage is the start state.  @out: a caller-supplied plane of the payload's size that receives the drainage -- the plane
+    // FluvialErosionStage.drainageIn takes; without it the stage owns the plane.
+    public class DrainageAreaStage : PipelineStage {
+        public float rain = 1f, seaLevel = -float.MaxValue;
+        public int? maxPasses = null;
+        public DeviceTile rainMap = null;
+        public DeviceTile @out = null;
+        DeviceTile work;                         // nz_drainage_area_work_floats floats; its first two int32: {passes, converged}
+        DeviceTile plane;
+        int resolution, count = 1;
+        public DrainageAreaStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Drainage => work == null ? null : @out ?? plane;
+        public int? Passes => Status(0);
+        public bool? Converged => Status(1) is int c ? c == 1 : (bool?) null;
+        int? Status(int k) {
+            if (work == null) return null;
+            jobHandle.Complete();
+            return BitConverter.SingleToInt32Bits(work.Offset(0, 2).ToArray()[k]);
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            foreach (DeviceTile m in new[] { rainMap, @out })   // before any launch
+                if (m != null && m.Length != Cells) throw new Exception($"DrainageAreaStage: a plane of {m.Length} floats does not fit the payload's {Cells}");
+            // sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+            int need = (int) (ulong) Native.nz_drainage_area_work_floats(resolution, count);
+            if (work == null || work.Length != need) { work?.Dispose(); work = ctx.Alloc(need); }
+            if (@out != null || (plane != null && plane.Length != Cells)) { plane?.Dispose(); plane = null; }
+            if (@out == null && plane == null) plane = ctx.Alloc(Cells);
+            NzDrainageDesc desc = new NzDrainageDesc {
+                rain = rain, seaLevel = seaLevel, maxPasses = maxPasses ?? 64 + resolution / 4,
+                rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero };
+            IntPtr dst = (@out ?? plane).Ptr;
+            ulong h;
+            if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_drainage_area_batch(ctx.Handle, b.data.Ptr, dst, work.Ptr, ref desc, b.resolution, b.count, dependency.id, out h), "nz_drainage_area_batch");
+            } else {
+                Native.Check(Native.nz_drainage_area(ctx.Handle, d.data.Ptr, dst, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_drainage_area");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() { work?.Dispose(); work = null; plane?.Dispose(); plane = null; }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

@@ -921,6 +921,65 @@ int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const float *w, floa
  * while entries run on other threads; a call that has begun keeps the cap it read. */
 int32_t nz_debug_fill_sweeps(int32_t sweeps);
 
+/* ---- drainage area: the exact river map of a heightmap in one call (new-framework feature) ------------------------------
+ * The flow accumulation over the steepest-descent tree: what nz_fluvial_erosion's drainage plane turns into when the bed
+ * stands still, computed directly.  Feed it a filled tile (nz_fill_depressions) and every river reaches the border.
+ *
+ * THE MODEL (tests/drainage_ref.py restates it as a topological walk; the kernels are nz_drainage.hip):
+ *   Square tile res x res, row-major z * res + x, float32 throughout, no contraction, the same in every float mode
+ *   (nz_ctx_set_float_mode does not apply).  Outlets, the neighbour order W E S N SW SE NW NE, "a neighbour outside the
+ *   tile does not exist" and the receiver r(c) with its strict comparison and tie rule are exactly step 1 of the fluvial
+ *   model above.
+ *   rain_c = rain * rainMap[c] (one multiply), or rain without a map.
+ *   The result is the plane A with, for every cell: A[c] = rain_c; then, for k ascending over the existing neighbours whose
+ *   receiver is c, A[c] = A[c] + A[k].
+ * That is step 2 of the fluvial model at rest.  A receiver is strictly lower than its donor, so the receiver graph has no
+ * cycle, every cell's value is a fixed function of its donors' values, and the plane is unique whatever the order of updates
+ * (Jacobi, tile-local sweeps and a topological walk give the same floats).  What follows:
+ *   - the result equals what nz_fluvial_erosion with erodibility = uplift = 0 reaches after enough iterations, bit for bit;
+ *   - it is a valid nz_fluvial_desc.drainageIn: the fluvial stage then erodes with the formed river network from its first
+ *     iteration instead of starting at A = rain_c;
+ *   - outlets and pits accumulate and pass nothing on;
+ *   - with rain == 1 and no map every value is an integer, and the sum over the receiver-less cells is res^2.
+ * `height` is read only.
+ *
+ * The entry enqueues one mask launch (heights -> one donor byte per cell: bit k set when neighbour k drains into the cell),
+ * maxPasses pass launches and one finalise launch, stream-ordered; nothing is read back.  A pass is nz_fill_depressions'
+ * scheme applied to A: every 64 x 16 tile is swept on chip against its frozen ring, tiles whose neighbourhood was at rest in
+ * the pass before are skipped, and a launch returns at once when the pass before changed nothing.  After completion the
+ * first two int32 of `work` hold {passes that did work, converged 0/1}.  The result is ALL OR NOTHING: when the last pass
+ * that ran changed nothing, `drainage` holds the fixed point; otherwise -- the budget was too small -- `drainage` holds the
+ * start state rain_c in every cell and converged == 0, which is not an error.  A partial state would depend on the schedule
+ * and never reaches the caller.  A pass is at least one Jacobi step, so a budget of "cells of the longest flow path" + 1
+ * always suffices; the hosts' default is far below that and measured ("drainage area").
+ * Defaults of the hosts' DrainageAreaStage: rain 1, seaLevel -FLT_MAX (off), maxPasses 64 + resolution / 4.
+ * The evidence (tools/bench_drainage.py): the 13-octave simplex fBm tile behind nz_fill_depressions
+ * comes to rest in 82 passes at 1024^2 and 192 at 4096^2; the defaults allow 320 and 1088.  Not a bound: a path that winds
+ * through many tiles needs more, and a budget that runs out shows as converged == 0.
+ *
+ * `work` = nz_drainage_area_work_floats(resolution, count) floats, stage-owned: status words, tile bytes, the donor bytes
+ * and one A plane (the other is `drainage`).  The _batch form runs `count` tiles stored back to back, each with its own
+ * border; every batch position equals the single-tile call bit for bit, and the status words cover the whole batch.
+ * resolution == 0 or count == 0 does nothing and returns NZ_OK.  The 16-byte path runs when every plane is 16-byte aligned
+ * and resolution % 4 == 0, the 4-byte path otherwise; both give the same bits.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: rain or seaLevel not finite (-FLT_MAX
+ * switches the sea off); rain < 0; maxPasses < 1; a NULL desc, height, drainage or work; drainage overlapping height, work
+ * or rainMap; work overlapping height or rainMap.
+ * There is no _rw form (the heights do not change), no receiver-code output and no stripe form. */
+typedef struct nz_drainage_desc {
+    float rain, seaLevel;
+    int32_t maxPasses;
+    const float *rainMap;   /* NULL: rain everywhere */
+} nz_drainage_desc;
+size_t nz_drainage_area_work_floats(int32_t resolution, int32_t count);
+int32_t nz_drainage_area(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_desc *desc,
+                         int32_t resolution, nz_handle dep, nz_handle *out);
+int32_t nz_drainage_area_batch(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_desc *desc,
+                               int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
+/* Test hook, the twin of nz_debug_fill_sweeps: the cap on a drainage pass's on-chip sweeps per tile (process-wide; <= 0
+ * restores the default).  Results must not change.  Returns the cap that was in force. */
+int32_t nz_debug_drainage_sweeps(int32_t sweeps);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

@@ -7,7 +7,7 @@ it is missing: there is no CPU or PyTorch fallback in the product path.
 from . import _native
 from ._native import NoizeError, Stripe
 from .runtime import Context, DeviceTile, JobHandle
-from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DepressionFillStage, DownsampleData, DownsampleStage, ErosionStage, FlowMapStage, FluvialErosionStage, FractalNoise, FractalShape, GaussSigma,
+from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DepressionFillStage, DownsampleData, DrainageAreaStage, DownsampleStage, ErosionStage, FlowMapStage, FluvialErosionStage, FractalNoise, FractalShape, GaussSigma,
                        GeneratorData, GeneratorDataBatch, HydraulicBorder, HydraulicErosionStage, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
                        ReducePipeline, ReduceStage, ShapedNoiseStage, UpsampleStage, Upstream, WarpedNoiseStage,

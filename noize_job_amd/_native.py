@@ -94,9 +94,16 @@ class FillDesc(C.Structure):
     _fields_ = [("epsilon", C.c_float), ("seaLevel", C.c_float), ("maxPasses", C.c_int32), ("depth", C.c_void_p)]
 
 
+class DrainageDesc(C.Structure):
+    """nz_drainage_desc (include/noize_hip.h): the scalars of the drainage-area stage and the optional rain map (a device
+    address; None = rain everywhere)."""
+    _fields_ = [("rain", C.c_float), ("seaLevel", C.c_float), ("maxPasses", C.c_int32), ("rainMap", C.c_void_p)]
+
+
 hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
 fill_p = C.POINTER(FillDesc)
+drain_p = C.POINTER(DrainageDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -205,6 +212,10 @@ SIGNATURES = {
     "nz_fill_stripe": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, fill_p, _i, dev_ptr, dev_ptr] + _tail),
     "nz_fill_stripe_finalise": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, dev_ptr] + _tail),
     "nz_debug_fill_sweeps": (_i, [_i]),
+    "nz_drainage_area_work_floats": (_sz, [_i, _i]),
+    "nz_drainage_area": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, drain_p, _i] + _tail),
+    "nz_drainage_area_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, drain_p, _i, _i] + _tail),
+    "nz_debug_drainage_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

@@ -29,6 +29,7 @@
 // planes alternate so that the last launch writes the plane the caller reads (nz_stages.cpp), so the last launch is no
 // form of its own.
 #include "nz_internal.hpp"
+#include "nz_receiver.hpp"
 
 namespace {
 
@@ -38,8 +39,8 @@ constexpr int LP = 72;           // LDS row pitch in cells; plane column x0 + i 
 constexpr int LC = 4;            // keeps a thread's four cells 16-byte aligned in LDS
 constexpr int NRING = 2 * (FX + 2) + 2 * FZ;  // cells at radius 1 around the tile
 constexpr int NHALO2 = 4 * (FX + 4) + 4 * FZ;  // cells at radius 1 and 2 around the tile
-constexpr unsigned NONE = 8;     // receiver code of a cell without one
-constexpr float DIAG = 0x1.6a09e6p-1f;  // 0.70710678f, bits 0x3F3504F3
+using nz_recv::NONE;      // receiver code of a cell without one
+using nz_recv::receiver;  // step 1 at one cell (nz_receiver.hpp, shared with nz_drainage.hip)
 
 // the plane a launch works on: tiles of res^2 cells back to back (pitch = res, everything else derived), or -- WIN -- a
 // window of one stripe-shaped buffer, rows in buffer coordinates
@@ -55,26 +56,6 @@ struct fluvial_maps {
 };
 __device__ __forceinline__ fluvial_maps maps_of() { return fluvial_maps{}; }
 __device__ __forceinline__ fluvial_maps maps_of(const fluvial_maps &m) { return m; }
-
-// step 1 at one cell: c and its neighbours in the order W E S N SW SE NW NE; a tie keeps the earlier neighbour
-__device__ __forceinline__ unsigned receiver(float c, float w, float e, float s, float n, float sw, float se, float nw,
-                                             float ne, float &best, float &drop) {
-    const float hk[8] = {w, e, s, n, sw, se, nw, ne};
-    unsigned r = NONE;
-    best = 0.0f;
-    drop = 0.0f;
-#pragma unroll
-    for (unsigned k = 0; k < 8; k++) {
-        const float d = c - hk[k];
-        const float sl = k < 4 ? d : d * DIAG;
-        if (sl > best) {
-            best = sl;
-            r = k;
-            drop = d;
-        }
-    }
-    return r;
-}
 
 // the ring at radius 1 of the tile, cell i of NRING: its LDS row and column in the radius-1 planes
 __device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {

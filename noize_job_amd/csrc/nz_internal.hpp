@@ -408,6 +408,17 @@ int32_t nz_launch_fill_round_end(hipStream_t s, float *w, const float *w_work, c
 int32_t nz_launch_fill_stripe_finalise(hipStream_t s, float *h, const float *w, float *depth, const int *converged,
                                        const nz_geom &g);
 
+// drainage area (nz_drainage.hip) on `count` tiles of res^2 cells stored back to back.  mask: one donor byte per cell from
+// the heights (bit k: neighbour k drains into the cell).  pass `pass` of the series: A planes a_in -> a_out (pass 0 reads
+// none: it derives the start state rain * rain_map, rain_map NULL: rain), tile bytes flags_in -> flags_out, at most `sweeps`
+// in-LDS sweeps per tile; status: {passes, converged, changed[3]}, maintained by the launches themselves.  finalise sets
+// status[1] and, when the series did not come to rest, writes the start state to `drainage`
+int32_t nz_launch_drainage_mask(hipStream_t s, const float *h, unsigned char *donors, float sea, int res, int count);
+int32_t nz_launch_drainage_pass(hipStream_t s, const unsigned char *donors, const float *rain_map, const float *a_in,
+                                float *a_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain,
+                                int res, int count, int pass, int sweeps);
+int32_t nz_launch_drainage_finalise(hipStream_t s, float *drainage, const float *rain_map, int *status, float rain, size_t n);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {

@@ -1,0 +1,31 @@
+// nz_receiver.hpp -- the receiver rule of the drainage network, stated once: step 1 of the fluvial model
+// (include/noize_hip.h).  nz_fluvial.hip erodes along it, nz_drainage.hip accumulates down it; both include this file, so
+// the two cannot drift apart.
+#pragma once
+
+namespace nz_recv {
+
+constexpr unsigned NONE = 8;            // receiver code of a cell without one
+constexpr float DIAG = 0x1.6a09e6p-1f;  // 0.70710678f, bits 0x3F3504F3
+
+// step 1 at one cell: c and its neighbours in the order W E S N SW SE NW NE; a tie keeps the earlier neighbour
+__device__ __forceinline__ unsigned receiver(float c, float w, float e, float s, float n, float sw, float se, float nw,
+                                             float ne, float &best, float &drop) {
+    const float hk[8] = {w, e, s, n, sw, se, nw, ne};
+    unsigned r = NONE;
+    best = 0.0f;
+    drop = 0.0f;
+#pragma unroll
+    for (unsigned k = 0; k < 8; k++) {
+        const float d = c - hk[k];
+        const float sl = k < 4 ? d : d * DIAG;
+        if (sl > best) {
+            best = sl;
+            r = k;
+            drop = d;
+        }
+    }
+    return r;
+}
+
+}  // namespace nz_recv

@@ -1,6 +1,6 @@
 // nz_terrain_stages.cpp -- the extern "C" entry points of the terrain stages the reference does not have (grid hydraulic
-// erosion, fluvial erosion, depression filling, resampling; include/noize_hip.h): tile, batch, read/write-pair and row-stripe
-// forms.  The stripe geometry and the aliasing checks they share are in nz_planes.hpp.
+// erosion, fluvial erosion, depression filling, drainage area, resampling; include/noize_hip.h): tile, batch,
+// read/write-pair and row-stripe forms.  The stripe geometry and the aliasing checks they share are in nz_planes.hpp.
 #include <atomic>
 #include <cmath>
 #include <iterator>
@@ -562,6 +562,77 @@ extern "C" int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const flo
     nz_ctx_arm_last_launch(ctx);
     NZ_TRY(nz_launch_fill_stripe_finalise(ctx->stream, height, w, depth, converged, nz_geom_from_stripe(*st)));
     return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// drainage area (new-framework feature, include/noize_hip.h, nz_drainage.hip)
+// ---------------------------------------------------------------------------------------------
+// `work` in floats: the fill stage's 16 status words and two generations of per-tile bytes, then one donor byte per cell
+// (rounded up to 16 bytes) and one A plane of count * res^2 floats; the other A plane is the caller's `drainage`.
+namespace {
+constexpr int DRAINAGE_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "drainage area"
+std::atomic<int> drainage_sweeps{DRAINAGE_SWEEPS};  // nz_debug_drainage_sweeps may be called while a thread runs an entry
+struct drainage_layout {
+    fill_layout f;
+    size_t donor_floats;
+    size_t total() const { return FILL_STATUS + 2 * f.gen_floats + donor_floats + f.n; }
+};
+drainage_layout drainage_layout_of(int res, int count) {
+    const fill_layout f = fill_layout_of(res, count);
+    return drainage_layout{f, (f.n + 15) / 16 * 4};
+}
+}  // namespace
+
+extern "C" size_t nz_drainage_area_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? drainage_layout_of(resolution, count).total() : 0;
+}
+
+extern "C" int32_t nz_debug_drainage_sweeps(int32_t sweeps) {
+    return drainage_sweeps.exchange(sweeps > 0 ? sweeps : DRAINAGE_SWEEPS);
+}
+
+static int32_t drainage_impl(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_desc *d, int res,
+                             int count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(drainage, "drainage is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(std::isfinite(d->rain), "rain is not finite");
+    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(d->rain >= 0.0f, "rain %g < 0", (double)d->rain);
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    const drainage_layout L = drainage_layout_of(res, count);
+    const size_t n = L.f.n;
+    const nz_named_plane writes[] = {{"drainage", drainage, n}, {"work", work, L.total()}};
+    const nz_named_plane reads[] = {{"height", height, n}, {"rainMap", d->rainMap, n}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
+    unsigned char *donors = reinterpret_cast<unsigned char *>(c.planes);
+    float *planes[2] = {drainage, c.planes + L.donor_floats};  // pass p writes plane p & 1 and byte generation p & 1
+    const int sweeps = drainage_sweeps.load();  // one cap for the whole series
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_drainage_mask(ctx->stream, height, donors, d->seaLevel, res, count));
+    for (int p = 0; p < d->maxPasses; p++)
+        NZ_TRY(nz_launch_drainage_pass(ctx->stream, donors, d->rainMap, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1],
+                                       c.status, c.flags[(p - 1) & 1], c.flags[p & 1], d->rain, res, count, p, sweeps));
+    nz_ctx_arm_last_launch(ctx);
+    // a series at rest holds the fixed point in both planes, so `drainage` has it whichever plane was written last
+    NZ_TRY(nz_launch_drainage_finalise(ctx->stream, drainage, d->rainMap, c.status, d->rain, n));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_drainage_area(nz_ctx *ctx, const float *height, float *drainage, float *work,
+                                    const nz_drainage_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out) {
+    return drainage_impl(ctx, height, drainage, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_drainage_area_batch(nz_ctx *ctx, const float *height, float *drainage, float *work,
+                                          const nz_drainage_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                                          nz_handle *out) {
+    return drainage_impl(ctx, height, drainage, work, desc, resolution, count, dep, out);
 }
 
 // ---------------------------------------------------------------------------------------------

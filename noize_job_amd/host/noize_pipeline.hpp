@@ -884,6 +884,66 @@ class DepressionFillStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, lakes;
 };
 
+// Drainage area (new-framework feature; the model: nz_drainage_area in include/noize_hip.h): the exact flow accumulation
+// over the steepest-descent tree of the payload's heights -- the river map -- in one call.  The heights pass through
+// untouched.  Once the handle completes, drainage() holds the plane of the last payload (drainageLength() floats); passes()
+// and converged() wait for the handle and read the status words.  seaLevel: cells at or below it are outlets like the
+// border (-FLT_MAX: off).  rainMap: a plane of the payload's size the caller supplies and keeps alive (rain * rainMap).
+// maxPasses < 1 means the default, 64 + resolution / 4; a budget that runs out is no error: converged() is false and the
+// drainage is the start state.  out: a caller-supplied plane of the payload's size that receives the drainage -- the plane
+// FluvialErosionStage::drainageIn takes; without it the stage owns the plane.
+class DrainageAreaStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    float rain = 1.f, seaLevel = -3.402823466e+38f;
+    int maxPasses = 0;  // < 1: 64 + resolution / 4
+    const DeviceTile *rainMap = nullptr;
+    DeviceTile *out = nullptr;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        for (const DeviceTile *m : {rainMap, static_cast<const DeviceTile *>(out)})  // before any launch
+            if (m && m->Length != drainageLength()) throw std::runtime_error("DrainageAreaStage: a plane does not fit the payload");
+        // sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        const size_t need = nz_drainage_area_work_floats(resolution, count);
+        if (!work || work->Length != need) work.reset(new DeviceTile(ctx, need));
+        if (out) plane.reset();
+        else if (!plane || plane->Length != drainageLength()) plane.reset(new DeviceTile(ctx, drainageLength()));
+        const nz_drainage_desc desc{rain, seaLevel, maxPasses >= 1 ? maxPasses : 64 + resolution / 4,
+                                    rainMap ? rainMap->ptr : nullptr};
+        float *dst = out ? out->ptr : plane->ptr;
+        nz_handle h = 0;
+        if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_drainage_area_batch(ctx, b->data->ptr, dst, work->ptr, &desc, b->resolution, b->count, dependency.id, &h),
+                  "nz_drainage_area_batch");
+        } else {
+            check(nz_drainage_area(ctx, d->data->ptr, dst, work->ptr, &desc, d->resolution, dependency.id, &h),
+                  "nz_drainage_area");
+        }
+        jobHandle = done(h);
+    }
+    const float *drainage() const { return !work ? nullptr : out ? out->ptr : plane->ptr; }  // nullptr before a payload
+    size_t drainageLength() const { return (size_t)count * resolution * resolution; }
+    int passes() const { return status(0); }                // -1 before the first run
+    bool converged() const { return status(1) == 1; }
+    void OnDestroy() override { work.reset(); plane.reset(); }
+
+  private:
+    int status(int k) const {
+        if (!work) return -1;
+        jobHandle.Complete();
+        int32_t words[2];
+        check(nz_tile_download(ctx, work->ptr, reinterpret_cast<float *>(words), 2, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[k];
+    }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, plane;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

@@ -1041,6 +1041,101 @@ class DepressionFillStage(PipelineStage):
         self.DisposeArrays()
 
 
+class DrainageAreaStage(PipelineStage):
+    """Drainage area (new-framework feature; the model is the comment block of nz_drainage_area in include/noize_hip.h): the
+    exact flow accumulation over the steepest-descent tree of the payload's heights -- the river map -- in one call.  The
+    heights pass through untouched.  Once the stage's handle completes, `drainage` holds the plane of the last payload
+    (count * resolution^2 floats); `passes` and `converged` are the status words of that run.  Behind DepressionFillStage
+    every river reaches the border, and the plane is what FluvialErosionStage(drainageIn=...) takes as a warm start.
+
+    seaLevel: cells at or below it are outlets like the border cells (the default, -FLT_MAX, switches it off).  rainMap: a
+    device plane of the payload's size the caller supplies and keeps alive; rain is multiplied by it.  maxPasses: the number
+    of pass launches; None means 64 + resolution // 4.  A budget that runs out is no error: converged is False and the
+    drainage is the start state, rain (times rainMap) in every cell.  out: a caller-supplied plane of the payload's size
+    that receives the drainage; without it the stage owns the plane."""
+
+    SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+
+    def __init__(self, ctx, rain=1.0, seaLevel=SEA_OFF, maxPasses=None, rainMap=None, out=None):
+        super().__init__(ctx)
+        self.rain = rain
+        self.seaLevel = seaLevel
+        self.maxPasses = maxPasses
+        self.rainMap = rainMap
+        self.out = out
+        self.resolution = 0
+        self.count = 0
+        self.work = None    # nz_drainage_area_work_floats floats; its first two int32: {passes, converged}
+        self._plane = None  # the stage's own drainage plane (no `out`)
+
+    def DisposeArrays(self):
+        for t in (self.work, self._plane):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.work = self._plane = None
+
+    @property
+    def drainage(self):
+        """The drainage plane(s) of the last run -- `out` when the caller gave one -- or None before the first payload and
+        after OnDestroy."""
+        if self.work is None:
+            return None
+        return self.out if self.out is not None else self._plane
+
+    def _status(self):
+        if self.work is None:
+            return None
+        self.jobHandle.Complete()
+        return self.ctx.wrap(self.work.ptr, 2, dtype=np.int32).ToArray()
+
+    @property
+    def passes(self):
+        """Passes of the last run that did work (the launches after them returned at once); None before the first run."""
+        s = self._status()
+        return None if s is None else int(s[0])
+
+    @property
+    def converged(self):
+        """Whether the last run reached the fixed point within maxPasses; None before the first run."""
+        s = self._status()
+        return None if s is None else bool(s[1])
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        n = self.count * self.resolution * self.resolution
+        for name, m in (("rainMap", self.rainMap), ("out", self.out)):  # before any launch
+            if m is not None and m.Length != n:
+                raise ValueError("DrainageAreaStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
+        # sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        need = N.lib.nz_drainage_area_work_floats(self.resolution, self.count)
+        if self.work is None or self.work.Length != need:
+            if self.work is not None and self.work.IsCreated:
+                self.work.Dispose()
+            self.work = self.ctx.alloc(need)
+        if self.out is not None and self._plane is not None:
+            self._plane.Dispose()
+            self._plane = None
+        if self.out is None and (self._plane is None or self._plane.Length != n):
+            if self._plane is not None:
+                self._plane.Dispose()
+            self._plane = self.ctx.alloc(n)
+        budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
+        desc = N.DrainageDesc(self.rain, self.seaLevel, budget, self.rainMap.ptr if self.rainMap is not None else None)
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_drainage_area_batch", d.data.ptr, self.drainage.ptr, self.work.ptr,
+                                           C.byref(desc), d.resolution, d.count, dep=dependency)
+        else:
+            self.jobHandle = self.ctx.call("nz_drainage_area", d.data.ptr, self.drainage.ptr, self.work.ptr, C.byref(desc),
+                                           d.resolution, dep=dependency)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
     def __init__(self, ctx, meshType=MeshType.SquareGridHeightMap):
         super().__init__(ctx)
