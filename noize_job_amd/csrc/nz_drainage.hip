@@ -11,56 +11,30 @@
 // topological walk -- ends in the same floats.  No monotonicity is needed (a rain map may be negative), only that a test
 // "nothing changed" looks at every single update: see `relax` below.
 //
-// The mask launch, once per call, on the fluvial stage's geometry (a workgroup of 256 threads owns an FX x FZ = 64 x 16
-// tile, a thread four consecutive cells of a row, 16-byte accesses where planes and pitch allow, batch tiles on
-// blockIdx.z): heights at radius 2 into LDS, receiver codes at radius 1, and per own cell one DONOR BYTE -- bit k set when
-// neighbour k exists and its receiver is the direction opposite to k.  After it no launch looks at a height.
+// The mask launch, once per call, on the geometry of nz_tile64.hpp (16-byte accesses where planes and pitch allow):
+// heights at radius 2 into LDS, receiver codes at radius 1, and per own cell one DONOR BYTE -- bit k set when neighbour k
+// exists and its receiver is the direction opposite to k.  After it no launch looks at a height.
 //
-// One launch per PASS, nz_fill.hip's scheme applied to A.  A pass reads A_in and writes A_out, two planes that alternate
-// (the caller's `drainage` is plane 0), so no workgroup waits for another and no launch has a race:
-//   skip     (pass > 0) when neither this tile nor one of its eight neighbours changed in the pass before -- one byte per
-//            tile, two generations -- the tile is at rest against an unchanged ring: a zero byte, and return.  A tile
-//            that did not change has equal cells in both planes, so nothing has to be copied.
+// One launch per PASS of A, by the pass protocol of nz_relax_pass.hpp -- gate, tile skip, sweeps against a frozen ring,
+// the closing byte and word, and the argument for them; the caller's `drainage` is plane 0.  What is this stage's own:
 //   fill     the four donor bytes and rain_c of the thread's cells into registers, A at radius 1 into LDS (18 x 72
 //            floats); a ring cell outside the grid holds +0 and is never gathered (its donor bit is clear).  The first
 //            pass reads no A plane: it derives the start state rain_c.
-//   sweeps   with the ring frozen: every thread reads its 3 x 6 window, updates its four cells left to right and back
-//            (Gauss-Seidel inside the thread, Jacobi between threads), a workgroup-wide OR of "changed" doubles as the
-//            barrier behind the read phase, then the write phase and a second barrier.  The loop ends when a sweep
-//            changes nothing, or after `sweeps` of them.
-//   store    the own cells to A_out, the tile's byte, one ordinary global atomic on changed[pass % 3] when they changed.
-// Convergence without the host is nz_fill.hip's: pass p reads changed[(p - 1) % 3] and returns at once on zero, bumps
-// word p and zeroes word p + 1; the first pass changes every tile by decree, so pass 1 writes all of the second plane and
-// a series that came to rest holds the fixed point in BOTH planes -- the finalise launch has nothing to copy.  It sets
-// the verdict and, when the last pass that ran did change something, puts rain_c back into every cell: all or nothing.
+//   sweeps   every thread updates its four cells left to right and back (Gauss-Seidel inside the thread, Jacobi between
+//            threads); "changed" looks at every single update (`relax`).
+// A series at rest holds the fixed point in BOTH planes, so the finalise launch has nothing to copy: it sets the protocol's
+// verdict and, when the last pass that ran did change something, puts rain_c back into every cell: all or nothing.
 #include "nz_internal.hpp"
 #include "nz_receiver.hpp"
+#include "nz_relax_pass.hpp"
+#include "nz_tile64.hpp"
 
 namespace {
 
 using nz_recv::NONE;
 using nz_recv::receiver;
-
-constexpr int FX = 64, FZ = 16;  // tile of one workgroup
-constexpr int FT = 256;          // threads: one per four cells of a row
-constexpr int LP = 72;           // LDS row pitch in cells; plane column x0 + i is LDS column LC + i
-constexpr int LC = 4;            // keeps a thread's four cells 16-byte aligned in LDS
-constexpr int NRING = 2 * (FX + 2) + 2 * FZ;   // cells at radius 1 around the tile
-constexpr int NHALO2 = 4 * (FX + 4) + 4 * FZ;  // cells at radius 1 and 2 around the tile
-constexpr int ST_PASSES = 0, ST_CONVERGED = 1, ST_CHANGED = 2;  // the status words: changed[3] from ST_CHANGED on
-
-// the ring at radius 1 of the tile, cell i of NRING: its LDS row and column in the radius-1 planes
-__device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {
-    if (i < 2 * (FX + 2)) {
-        const int rr = i / (FX + 2);
-        lz = rr ? FZ + 1 : 0;
-        lx = LC - 1 + (i - rr * (FX + 2));
-    } else {
-        const int j = i - 2 * (FX + 2);
-        lz = 1 + (j >> 1);
-        lx = (j & 1) ? LC + FX : LC - 1;
-    }
-}
+using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, halo2_cell
+using namespace nz_relax;   // the status words and the pass protocol
 
 // ---- the mask launch: heights -> donor bytes ----
 // VEC: 16-byte height reads; WORD: the four donor bytes of a thread as one 32-bit store (res % 4 == 0)
@@ -99,15 +73,7 @@ __global__ __launch_bounds__(FT) void drainage_mask_kernel(const float *__restri
     *reinterpret_cast<float4 *>(&H[(tz + 2) * LP + LC + tx]) = make_float4(hc[0], hc[1], hc[2], hc[3]);
     for (int i = tid; i < NHALO2; i += FT) {  // the heights at radius 1 and 2
         int lz, lx;
-        if (i < 4 * (FX + 4)) {
-            const int rr = i / (FX + 4);
-            lz = rr < 2 ? rr : FZ + rr;
-            lx = LC - 2 + (i - rr * (FX + 4));
-        } else {
-            const int j = i - 4 * (FX + 4), cc = j & 3;
-            lz = 2 + (j >> 2);
-            lx = cc < 2 ? LC - 2 + cc : LC + FX - 2 + cc;
-        }
+        halo2_cell(i, lz, lx);
         const int qx = x0 + lx - LC, qz = z0 + lz - 2;
         H[lz * LP + lx] = inside(qx, qz) ? h[base + (size_t)qz * res + qx] : 0.0f;
     }
@@ -152,28 +118,10 @@ __global__ __launch_bounds__(FT) void drainage_mask_kernel(const float *__restri
     // ---- the donor bytes of the own cells ----
     if (!row_in || px > hi) return;
     unsigned cw[3][6];  // the receiver codes of the window
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const int l = (tz + r) * LP + LC + tx;
-        const unsigned q = RW[l >> 2];
-        cw[r][0] = RC[l - 1], cw[r][1] = q & 255u, cw[r][2] = (q >> 8) & 255u, cw[r][3] = (q >> 16) & 255u, cw[r][4] = q >> 24;
-        cw[r][5] = RC[l + 4];
-    }
+    window_bytes(RW, tz, tx, cw);
     unsigned word = 0;
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        // neighbour k drains here when its receiver is the direction opposite to k: E W N S NE NW SE SW
-        unsigned m = 0;
-        m |= (cw[1][j] == 1u) << 0;
-        m |= (cw[1][j + 2] == 0u) << 1;
-        m |= (cw[0][j + 1] == 3u) << 2;
-        m |= (cw[2][j + 1] == 2u) << 3;
-        m |= (cw[0][j] == 7u) << 4;
-        m |= (cw[0][j + 2] == 6u) << 5;
-        m |= (cw[2][j] == 5u) << 6;
-        m |= (cw[2][j + 2] == 4u) << 7;
-        word |= m << (8 * j);
-    }
+    for (int j = 0; j < 4; j++) word |= nz_recv::donor_mask(cw, j) << (8 * j);
     if (WORD && quad) {
         *reinterpret_cast<unsigned *>(donors + c0) = word;
     } else {
@@ -197,29 +145,16 @@ __global__ __launch_bounds__(FT) void drainage_pass_kernel(const unsigned char *
                                                            int pass, int sweeps) {
     __shared__ __attribute__((aligned(16))) float A[(FZ + 2) * LP];  // radius 1: LDS row = plane row - z0 + 1
     const int tid = threadIdx.x;
-    int *changed = status + ST_CHANGED;
 
-    // ---- did the pass before change anything at all? ----
-    const int prev = FIRST ? 1 : changed[(pass + 2) % 3];
-    if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-        changed[(pass + 1) % 3] = 0;
-        if (FIRST) changed[0] = 1;  // by decree; no workgroup bumps it
-        if (prev) status[ST_PASSES] = pass + 1;
-    }
+    const bool t0 = tid == 0;
+    const int prev = series_gate<FIRST>(status, t0, pass, false);
     if (!prev) return;
-
-    // ---- did this tile's neighbourhood? ----
     const int tnx = gridDim.x, tnz = gridDim.y;
     const size_t tile0 = (size_t)blockIdx.z * tnx * tnz;
-    const size_t me = tile0 + (size_t)blockIdx.y * tnx + blockIdx.x;
+    const size_t me = tile0 + (size_t)blockIdx.y * tnx + blockIdx.x;  // this tile's byte
     if (!FIRST) {
-        int live = 0;
-        if (tid < 9) {
-            const int bx = (int)blockIdx.x + tid % 3 - 1, bz = (int)blockIdx.y + tid / 3 - 1;
-            if (bx >= 0 && bx < tnx && bz >= 0 && bz < tnz) live = flags_in[tile0 + (size_t)bz * tnx + bx];
-        }
-        if (!__syncthreads_or(live)) {
-            if (tid == 0) flags_out[me] = 0;
+        if (!__syncthreads_or(tile_live(flags_in, tile0, tnx, tnz, tid))) {
+            if (t0) flags_out[me] = 0;
             return;
         }
     }
@@ -332,10 +267,7 @@ __global__ __launch_bounds__(FT) void drainage_pass_kernel(const unsigned char *
             a_out[c0 + j] = ac[j];
         }
     }
-    if (tid == 0) {
-        flags_out[me] = moved ? 1 : 0;
-        if (!FIRST && moved) atomicAdd(&changed[pass % 3], 1);
-    }
+    if (t0) close_tile<FIRST>(status, flags_out, me, pass, moved);
 }
 
 // all or nothing: the fixed point stands in `drainage` when the last pass that ran changed nothing (nz_drainage_area keeps
@@ -344,8 +276,7 @@ template <bool MAP>
 __global__ __launch_bounds__(256) void drainage_finalise_kernel(float *__restrict__ drainage,
                                                                 const float *__restrict__ rain_map, int *status, float rain,
                                                                 size_t n) {
-    const int passes = status[ST_PASSES];
-    const bool converged = status[ST_CHANGED + (passes + 2) % 3] == 0;
+    const bool converged = series_at_rest(status);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) status[ST_CONVERGED] = converged ? 1 : 0;
     if (i >= n || converged) return;
@@ -356,7 +287,7 @@ __global__ __launch_bounds__(256) void drainage_finalise_kernel(float *__restric
 
 int32_t nz_launch_drainage_mask(hipStream_t s, const float *h, unsigned char *donors, float sea, int res, int count) {
     if (res <= 0 || count <= 0) return NZ_OK;
-    const dim3 grid((res + FX - 1) / FX, (res + FZ - 1) / FZ, count);
+    const dim3 grid(tiles_x(res), tiles_z(res), count);
     const bool word = res % 4 == 0 && (reinterpret_cast<uintptr_t>(donors) & 3) == 0;
     const bool vec = res % 4 == 0 && (reinterpret_cast<uintptr_t>(h) & 15) == 0;
     if (vec && word) NZ_LAUNCH((drainage_mask_kernel<true, true>), grid, dim3(FT), 0, s, h, donors, sea, res);
@@ -380,7 +311,7 @@ int32_t nz_launch_drainage_pass(hipStream_t s, const unsigned char *donors, cons
                                 float *a_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain,
                                 int res, int count, int pass, int sweeps) {
     if (res <= 0 || count <= 0) return NZ_OK;
-    const dim3 grid((res + FX - 1) / FX, (res + FZ - 1) / FZ, count);
+    const dim3 grid(tiles_x(res), tiles_z(res), count);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(rain_map) | reinterpret_cast<uintptr_t>(a_in) |
                            reinterpret_cast<uintptr_t>(a_out) | reinterpret_cast<uintptr_t>(donors);
     const bool vec = (bits & 15) == 0 && res % 4 == 0;  // a row, and with it a tile of the batch, starts 16-byte aligned

@@ -14,25 +14,14 @@
 // value is a NaN (heights are finite, +inf + epsilon = +inf), and t is never -0 (x + +0 and x + epsilon round to +0, not
 // -0), so min_k (W[k] + epsilon) == (min_k W[k]) + epsilon bit for bit whatever the order of the minimum.
 //
-// One launch per PASS on the fluvial stage's geometry: a workgroup of 256 threads owns an FX x FZ = 64 x 16 tile, a thread
-// four consecutive cells of a row (16-byte accesses where planes and pitch allow, VEC), batch tiles on blockIdx.z.  A pass
-// reads W_in and writes W_out, two planes that alternate, so no workgroup waits for another and no launch has a race:
-//   skip     (pass > 0) when neither this tile nor one of its eight neighbours changed in the pass before -- one byte per
-//            tile, two generations alternating with the planes -- the tile is at rest against an unchanged ring: it writes
-//            a zero byte and returns.  No copy is needed: a tile that did not change has equal cells in both planes.
+// One launch per PASS of W, on the geometry of nz_tile64.hpp (VEC: 16-byte accesses where planes and pitch allow), by the
+// pass protocol of nz_relax_pass.hpp: gate, tile skip, sweeps, closing byte and word, and why.  What is the fill's own:
 //   fill     the tile's own h into registers, its W at radius 1 into LDS (18 x 72 floats); ring cells outside the grid hold
 //            +inf.  The first pass reads no W plane: it derives the start state from h.
-//   sweeps   with the ring frozen: every thread reads its 3 x 6 window, updates its four cells left to right and back right
-//            to left in registers (Gauss-Seidel inside the thread, Jacobi between threads), a workgroup-wide OR of "changed"
-//            doubles as the barrier behind the read phase, then the write phase and a second barrier.  The loop ends when a
-//            sweep changes nothing, or after `sweeps` of them.
-//   store    the own cells to W_out, the tile's byte, and one ordinary global atomic on changed[pass % 3] when they changed.
-// Convergence without the host: pass p first reads changed[(p - 1) % 3]; zero means the pass before changed nothing, both
-// planes hold the fixed point, and the whole launch returns at once -- as does every later one.  Three words in turn are
-// enough: pass p reads word p - 1, bumps word p and (one thread of the grid) zeroes word p + 1.  The first pass changes every
-// tile by decree (its predecessor is the +inf start, which exists in no plane), so pass 1 writes all of the second plane.
-// The finalise launch looks at the word of the last pass that ran: zero -> W to the heights and W - h to the depth plane;
-// otherwise the heights stay and the depth is zero: all or nothing, a caller never sees +inf.
+//   sweeps   every thread updates its four cells left to right and back right to left in registers (Gauss-Seidel inside
+//            the thread, Jacobi between threads).  W only ever falls, so "changed" is the net effect of a sweep.
+// The finalise launch takes the protocol's verdict: at rest -> W to the heights and W - h to the depth plane; otherwise
+// the heights stay and the depth is zero: all or nothing, a caller never sees +inf.
 //
 // WIN, the stripe form (nz_fill_stripe): one ROUND on the owned rows [r0, r1) of a stripe-shaped buffer with a pitch; the
 // workgroups tile the owned rows, the grid's bounds are the global grid's seen from the buffer.  The one row of W on each
@@ -46,16 +35,13 @@
 // The cap, `sweeps`, is 16 (nz_stages.cpp): enough to carry a value across the tile's 16 rows and 64 columns.  4 to 64 were
 // measured: DESIGN.md section 4, "depression filling".
 #include "nz_internal.hpp"
+#include "nz_relax_pass.hpp"
+#include "nz_tile64.hpp"
 
 namespace {
 
-constexpr int FX = 64, FZ = 16;  // tile of one workgroup
-constexpr int FT = 256;          // threads: one per four cells of a row
-constexpr int LP = 72;           // LDS row pitch in cells; plane column x0 + i is LDS column LC + i
-constexpr int LC = 4;            // keeps a thread's four cells 16-byte aligned in LDS
-constexpr int NRING = 2 * (FX + 2) + 2 * FZ;  // cells at radius 1 around the tile
-constexpr int ST_PASSES = 0, ST_CONVERGED = 1, ST_CHANGED = 2;  // the status words: changed[3] from ST_CHANGED on
-constexpr int ST_GO = 5;                                          // stripe rounds: 0 = every launch returns at once
+using namespace nz_tile64;  // the tile, its LDS layout, ring_cell
+using namespace nz_relax;   // the status words and the pass protocol
 
 // the plane a pass works on: tiles of res^2 cells back to back (pitch = res, the rest derived), or -- WIN -- the owned rows
 // of one stripe-shaped buffer, rows in buffer coordinates
@@ -69,19 +55,6 @@ struct fill_win {
     int *changed_out;    // the caller's word
 };
 
-// the ring at radius 1 of the tile, cell i of NRING: its LDS row and column
-__device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {
-    if (i < 2 * (FX + 2)) {
-        const int rr = i / (FX + 2);
-        lz = rr ? FZ + 1 : 0;
-        lx = LC - 1 + (i - rr * (FX + 2));
-    } else {
-        const int j = i - 2 * (FX + 2);
-        lz = 1 + (j >> 1);
-        lx = (j & 1) ? LC + FX : LC - 1;
-    }
-}
-
 template <bool FIRST, bool VEC, bool WIN>
 __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__ h, const float *__restrict__ w_in,
                                                        float *__restrict__ w_out, int *status,
@@ -90,33 +63,26 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
                                                        fill_win win, int pass, int sweeps) {
     __shared__ __attribute__((aligned(16))) float W[(FZ + 2) * LP];  // radius 1: LDS row = plane row - z0 + 1
     const int tid = threadIdx.x;
-    int *changed = status + ST_CHANGED;
 
     if constexpr (WIN) {
         if (!status[ST_GO]) return;
     }
     const bool all_live = WIN && pass == 0;  // a round's first pass: nothing is known about the pass before
-    // ---- did the pass before change anything at all? ----
-    const int prev = FIRST || all_live ? 1 : changed[(pass + 2) % 3];
-    if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-        changed[(pass + 1) % 3] = 0;
-        if (FIRST) changed[0] = 1;  // by decree; no workgroup bumps it
-        if (prev) status[ST_PASSES] = pass + 1;
-    }
+    const bool t0 = tid == 0;
+    const int prev = series_gate<FIRST>(status, t0, pass, all_live);
     if (!prev) return;
-
-    // ---- did this tile's neighbourhood? ----
     const int tnx = gridDim.x, tnz = gridDim.y;
     const size_t tile0 = (size_t)blockIdx.z * tnx * tnz;
-    const size_t me = tile0 + (size_t)blockIdx.y * tnx + blockIdx.x;
+    const size_t me = tile0 + (size_t)blockIdx.y * tnx + blockIdx.x;  // this tile's byte
     if (!FIRST && !all_live) {
+        // nz_relax::tile_live, written out: through the helper this kernel measures 0.5 % slower
         int live = 0;
         if (tid < 9) {
             const int bx = (int)blockIdx.x + tid % 3 - 1, bz = (int)blockIdx.y + tid / 3 - 1;
             if (bx >= 0 && bx < tnx && bz >= 0 && bz < tnz) live = flags_in[tile0 + (size_t)bz * tnx + bx];
         }
         if (!__syncthreads_or(live)) {
-            if (tid == 0) flags_out[me] = 0;
+            if (t0) flags_out[me] = 0;
             return;
         }
     }
@@ -242,9 +208,8 @@ __global__ __launch_bounds__(FT) void fill_pass_kernel(const float *__restrict__
             w_out[c0 + j] = wc[j];
         }
     }
-    if (tid == 0) {
-        flags_out[me] = moved ? 1 : 0;
-        if (!FIRST && moved) atomicAdd(&changed[pass % 3], 1);
+    if (t0) {
+        close_tile<FIRST>(status, flags_out, me, pass, moved);
         if (WIN && !FIRST && pass == 0 && moved) *win.changed_out = 1;
     }
 }
@@ -288,8 +253,7 @@ __global__ __launch_bounds__(256) void fill_stripe_finalise_kernel(float *__rest
 // all or nothing: the fixed point when the last pass that ran changed nothing, otherwise the heights as they were
 __global__ __launch_bounds__(256) void fill_finalise_kernel(float *__restrict__ h, const float *__restrict__ w,
                                                             float *__restrict__ depth, int *status, size_t n) {
-    const int passes = status[ST_PASSES];
-    const bool converged = status[ST_CHANGED + (passes + 2) % 3] == 0;
+    const bool converged = series_at_rest(status);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0) status[ST_CONVERGED] = converged ? 1 : 0;
     if (i >= n) return;
@@ -302,23 +266,27 @@ __global__ __launch_bounds__(256) void fill_finalise_kernel(float *__restrict__ 
     }
 }
 
+// the form of a pass by <FIRST, VEC, WIN>
+template <bool FIRST, bool WIN>
+void launch_pass(bool vec, dim3 grid, hipStream_t s, const float *h, const float *w_in, float *w_out, int *status,
+                 const unsigned char *flags_in, unsigned char *flags_out, float eps, float sea, const fill_win &win, int pass,
+                 int sweeps) {
+    if (vec) NZ_LAUNCH((fill_pass_kernel<FIRST, true, WIN>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+    else NZ_LAUNCH((fill_pass_kernel<FIRST, false, WIN>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+}
+
 }  // namespace
 
 int32_t nz_launch_fill_pass(hipStream_t s, const float *h, const float *w_in, float *w_out, int *status,
                             const unsigned char *flags_in, unsigned char *flags_out, float eps, float sea, int res, int count,
                             int pass, int sweeps) {
     if (res <= 0 || count <= 0) return NZ_OK;
-    const dim3 grid((res + FX - 1) / FX, (res + FZ - 1) / FZ, count);
+    const dim3 grid(tiles_x(res), tiles_z(res), count);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w_in) | reinterpret_cast<uintptr_t>(w_out);
     const bool vec = (bits & 15) == 0 && res % 4 == 0;  // a row, and with it a tile of the batch, starts 16-byte aligned
     const fill_win win{res, res - 1, 0, res - 1, 0, res, 0, nullptr, nullptr};
-    if (pass == 0) {
-        if (vec) NZ_LAUNCH((fill_pass_kernel<true, true, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-        else NZ_LAUNCH((fill_pass_kernel<true, false, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-    } else {
-        if (vec) NZ_LAUNCH((fill_pass_kernel<false, true, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-        else NZ_LAUNCH((fill_pass_kernel<false, false, false>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-    }
+    if (pass == 0) launch_pass<true, false>(vec, grid, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+    else launch_pass<false, false>(vec, grid, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
@@ -333,17 +301,12 @@ int32_t nz_launch_fill_stripe_pass(hipStream_t s, const float *h, const float *w
                                    int *status, const unsigned char *flags_in, unsigned char *flags_out, int *changed,
                                    float eps, float sea, const nz_geom &g, int zlo, int zhi, int first, int pass, int sweeps) {
     if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
-    const dim3 grid((g.cols + FX - 1) / FX, (g.or1 - g.or0 + FZ - 1) / FZ, 1);
+    const dim3 grid(tiles_x(g.cols), tiles_z(g.or1 - g.or0), 1);
     const uintptr_t bits = reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w_in) | reinterpret_cast<uintptr_t>(w_out);
     const bool vec = (bits & 15) == 0 && g.cols % 4 == 0 && g.pitch % 4 == 0;  // every row starts 16-byte aligned
     const fill_win win{g.pitch, g.cols - 1, zlo, zhi, g.or0, g.or1, first, w_ghost, changed};
-    if (first && pass == 0) {
-        if (vec) NZ_LAUNCH((fill_pass_kernel<true, true, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-        else NZ_LAUNCH((fill_pass_kernel<true, false, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-    } else {
-        if (vec) NZ_LAUNCH((fill_pass_kernel<false, true, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-        else NZ_LAUNCH((fill_pass_kernel<false, false, true>), grid, dim3(FT), 0, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
-    }
+    if (first && pass == 0) launch_pass<true, true>(vec, grid, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
+    else launch_pass<false, true>(vec, grid, s, h, w_in, w_out, status, flags_in, flags_out, eps, sea, win, pass, sweeps);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

@@ -4,8 +4,8 @@
 // k sqrt(A) slope against an uplift.  Strict IEEE binary32 in every float mode, no contraction (-ffp-contract=off, Makefile),
 // no atomics and a fixed summation order, so the result is independent of the launch shape.
 //
-// One launch per iteration, batch tiles on blockIdx.z.  A workgroup of 256 threads produces an FX x FZ = 64 x 16 tile of one
-// plane; a thread owns four consecutive cells of a row (one 16-byte access per plane where plane and pitch allow, VEC):
+// One launch per iteration on the geometry of nz_tile64.hpp: a workgroup produces a 64 x 16 tile of one plane, a thread
+// four consecutive cells of a row (one 16-byte access per plane where plane and pitch allow, VEC), batch tiles on blockIdx.z:
 //   fill     heights at radius 2 (5.6 KB) and drainage at radius 1 (5.1 KB) into LDS; a cell outside the grid reads as +0 and
 //            is never looked at (below)
 //   barrier
@@ -30,15 +30,11 @@
 // form of its own.
 #include "nz_internal.hpp"
 #include "nz_receiver.hpp"
+#include "nz_tile64.hpp"
 
 namespace {
 
-constexpr int FX = 64, FZ = 16;  // tile produced by one workgroup
-constexpr int FT = 256;          // threads: one per four cells of a row
-constexpr int LP = 72;           // LDS row pitch in cells; plane column x0 + i is LDS column LC + i
-constexpr int LC = 4;            // keeps a thread's four cells 16-byte aligned in LDS
-constexpr int NRING = 2 * (FX + 2) + 2 * FZ;  // cells at radius 1 around the tile
-constexpr int NHALO2 = 4 * (FX + 4) + 4 * FZ;  // cells at radius 1 and 2 around the tile
+using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, halo2_cell
 using nz_recv::NONE;      // receiver code of a cell without one
 using nz_recv::receiver;  // step 1 at one cell (nz_receiver.hpp, shared with nz_drainage.hip)
 
@@ -56,19 +52,6 @@ struct fluvial_maps {
 };
 __device__ __forceinline__ fluvial_maps maps_of() { return fluvial_maps{}; }
 __device__ __forceinline__ fluvial_maps maps_of(const fluvial_maps &m) { return m; }
-
-// the ring at radius 1 of the tile, cell i of NRING: its LDS row and column in the radius-1 planes
-__device__ __forceinline__ void ring_cell(int i, int &lz, int &lx) {
-    if (i < 2 * (FX + 2)) {
-        const int rr = i / (FX + 2);
-        lz = rr ? FZ + 1 : 0;
-        lx = LC - 1 + (i - rr * (FX + 2));
-    } else {
-        const int j = i - 2 * (FX + 2);
-        lz = 1 + (j >> 1);
-        lx = (j & 1) ? LC + FX : LC - 1;
-    }
-}
 
 template <bool CONSTA, bool MAPS, bool VEC, bool WIN, class... M>
 __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h_in, float *__restrict__ h_out,
@@ -128,15 +111,7 @@ __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h
     if constexpr (!CONSTA) *reinterpret_cast<float4 *>(&A[(tz + 1) * LP + LC + tx]) = make_float4(ac[0], ac[1], ac[2], ac[3]);
     for (int i = tid; i < NHALO2; i += FT) {  // the heights at radius 1 and 2
         int lz, lx;
-        if (i < 4 * (FX + 4)) {
-            const int rr = i / (FX + 4);
-            lz = rr < 2 ? rr : FZ + rr;
-            lx = LC - 2 + (i - rr * (FX + 4));
-        } else {
-            const int j = i - 4 * (FX + 4), cc = j & 3;
-            lz = 2 + (j >> 2);
-            lx = cc < 2 ? LC - 2 + cc : LC + FX - 2 + cc;
-        }
+        halo2_cell(i, lz, lx);
         const int qx = x0 + lx - LC, qz = z0 + lz - 2;
         H[lz * LP + lx] = inside(qx, qz) ? h_in[base + (size_t)qz * pitch + qx] : 0.0f;
     }
@@ -231,7 +206,7 @@ __global__ __launch_bounds__(FT) void fluvial_kernel(const float *__restrict__ h
     float hn[4], an[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        // the neighbour k drains here when its receiver is the direction opposite to k: E W N S NE NW SE SW
+        // neighbour k drains here: nz_recv::donor_mask's comparisons, written out (the mask changes this code object)
         float a = MAPS ? k.rain * rm[j] : k.rain;
         if (cw[1][j] == 1u) a = a + aw[1][j];
         if (cw[1][j + 2] == 0u) a = a + aw[1][j + 2];
@@ -313,7 +288,7 @@ int32_t nz_launch_fluvial(hipStream_t s, const float *h_in, float *h_out, const 
                           const nz_fluvial_params &k, int res, int count, const float *rain_map, const float *hardness,
                           const float *uplift_map) {
     if (res <= 0 || count <= 0) return NZ_OK;
-    const dim3 grid((res + FX - 1) / FX, (res + FZ - 1) / FZ, count);
+    const dim3 grid(tiles_x(res), tiles_z(res), count);
     const fluvial_maps m{rain_map, hardness, uplift_map};
     uintptr_t bits = reinterpret_cast<uintptr_t>(h_in) | reinterpret_cast<uintptr_t>(h_out) |
                      reinterpret_cast<uintptr_t>(a_in) | reinterpret_cast<uintptr_t>(a_out) |
@@ -329,7 +304,7 @@ int32_t nz_launch_fluvial_stripe(hipStream_t s, const float *h_in, float *h_out,
                                  const nz_fluvial_params &k, const nz_geom &g, int zlo, int zhi, const float *rain_map,
                                  const float *hardness, const float *uplift_map) {
     if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
-    const dim3 grid((g.cols + FX - 1) / FX, (g.or1 - g.or0 + FZ - 1) / FZ, 1);
+    const dim3 grid(tiles_x(g.cols), tiles_z(g.or1 - g.or0), 1);
     const fluvial_maps m{rain_map, hardness, uplift_map};
     uintptr_t bits = reinterpret_cast<uintptr_t>(h_in) | reinterpret_cast<uintptr_t>(h_out) |
                      reinterpret_cast<uintptr_t>(a_in) | reinterpret_cast<uintptr_t>(a_out) |

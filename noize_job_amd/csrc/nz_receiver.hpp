@@ -28,4 +28,20 @@ __device__ __forceinline__ unsigned receiver(float c, float w, float e, float s,
     return r;
 }
 
+// The donors of own cell j against the receiver codes cw of the thread's 3 x 6 window: bit k set when neighbour k drains
+// here, that is when its receiver is the direction opposite to k -- E W N S NE NW SE SW.  nz_drainage.hip stores the mask;
+// nz_fluvial.hip's gather keeps the same eight comparisons written out, which leaves its code object as it was.
+__device__ __forceinline__ unsigned donor_mask(const unsigned (&cw)[3][6], int j) {
+    unsigned m = 0;
+    m |= (cw[1][j] == 1u) << 0;
+    m |= (cw[1][j + 2] == 0u) << 1;
+    m |= (cw[0][j + 1] == 3u) << 2;
+    m |= (cw[2][j + 1] == 2u) << 3;
+    m |= (cw[0][j] == 7u) << 4;
+    m |= (cw[0][j + 2] == 6u) << 5;
+    m |= (cw[2][j] == 5u) << 6;
+    m |= (cw[2][j + 2] == 4u) << 7;
+    return m;
+}
+
 }  // namespace nz_recv

@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "nz_internal.hpp"
+#include "nz_tile64.hpp"  // the tile counts of the fill and drainage launches
 
 // Launch j of a series of n that ping-pongs between two plane sets writes set (n-1-j) & 1, so that the last launch lands in
 // set 0.  The stripe entries: 0 = the caller's output planes, 1 = `work`.
@@ -413,7 +414,7 @@ extern "C" int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float 
 // ---------------------------------------------------------------------------------------------
 // depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
 // ---------------------------------------------------------------------------------------------
-// `work` in floats: 16 status words ({passes, converged, changed[3]}, the rest spare), two generations of per-tile bytes,
+// `work` in floats: 16 status words (nz_relax_pass.hpp; the rest spare), two generations of per-tile bytes (nz_tile64.hpp),
 // each rounded up to 16 bytes, and the W planes the passes alternate between: both of them in the tile forms (count * res^2
 // floats each), one in the stripe form, whose other W plane is the caller's `w`.  One pass is one launch whatever its depth,
 // so the launch-series planner (nz_split_iterations) has nothing to split here.
@@ -426,11 +427,11 @@ struct fill_layout {
     size_t total(int w_planes) const { return FILL_STATUS + 2 * gen_floats + w_planes * n; }
 };
 fill_layout fill_layout_of(int res, int count) {
-    const size_t tiles = (size_t)((res + 63) / 64) * ((res + 15) / 16) * count;
+    const size_t tiles = (size_t)nz_tile64::tiles_x(res) * nz_tile64::tiles_z(res) * count;
     return fill_layout{(tiles + 15) / 16 * 4, (size_t)res * res * count};
 }
 fill_layout fill_stripe_layout(const nz_stripe &st) {
-    const size_t tiles = (size_t)((st.cols + 63) / 64) * ((st.own1 - st.own0 + 15) / 16);
+    const size_t tiles = (size_t)nz_tile64::tiles_x(st.cols) * nz_tile64::tiles_z(st.own1 - st.own0);
     return fill_layout{(tiles + 15) / 16 * 4, nz_stripe_plane_floats(&st)};
 }
 struct fill_work { int *status; unsigned char *flags[2]; float *planes; };  // planes: the first (or only) W plane of `work`
@@ -567,8 +568,9 @@ extern "C" int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const flo
 // ---------------------------------------------------------------------------------------------
 // drainage area (new-framework feature, include/noize_hip.h, nz_drainage.hip)
 // ---------------------------------------------------------------------------------------------
-// `work` in floats: the fill stage's 16 status words and two generations of per-tile bytes, then one donor byte per cell
-// (rounded up to 16 bytes) and one A plane of count * res^2 floats; the other A plane is the caller's `drainage`.
+// The passes follow the fill stage's protocol (nz_relax_pass.hpp), so `work` begins as the fill's does -- 16 status words,
+// two generations of per-tile bytes -- and goes on with one donor byte per cell (rounded up to 16 bytes) and one A plane of
+// count * res^2 floats; the other A plane is the caller's `drainage`.
 namespace {
 constexpr int DRAINAGE_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "drainage area"
 std::atomic<int> drainage_sweeps{DRAINAGE_SWEEPS};  // nz_debug_drainage_sweeps may be called while a thread runs an entry

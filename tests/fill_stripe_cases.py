@@ -1,5 +1,7 @@
 """Grids, buffers and drivers shared by tests/test_fill_stripe_ref.py (CPU) and tests/test_gpu_fill_stripe.py: a fBm corner
 with pits, a bowl that spans three stripes, and a serpentine lake whose spill path crosses every cut many times."""
+import contextlib
+import ctypes as C
 import functools
 
 import numpy as np
@@ -80,6 +82,24 @@ def lockstep(sh, ops, world, h, params, work_floats=lambda plan: 0, device="cpu"
     assert len({(r[2], r[3]) for r in res}) == 1, "the ranks disagree about rounds / converged"
     return (np.concatenate([rows(r[0], pl) for r, pl in zip(res, plans)]),
             np.concatenate([rows(r[1], pl) for r, pl in zip(res, plans)]), res[0][2], res[0][3], plans, bufs)
+
+
+@contextlib.contextmanager
+def stripe_ops(nj):
+    """(sharded module, HipStripeOps) on a context that shares torch's stream: the buffers are torch CUDA tensors."""
+    from noize_job_amd import sharded as sh
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        tctx = nj.Context(0, stream=stream.cuda_stream)
+        try:
+            yield sh, sh.HipStripeOps(tctx)
+            stream.synchronize()
+        finally:
+            tctx.close()
+
+
+def work_floats(nj, pitch=0):
+    return lambda plan: nj._native.lib.nz_fill_stripe_work_floats(C.byref(plan.stripe(pitch)))
 
 
 def assert_bits(got, want, what):

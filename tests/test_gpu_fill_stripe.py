@@ -13,7 +13,7 @@ import torch
 
 import fill_ref as L
 from conftest import ROOT
-from fill_stripe_cases import EPS, WORLDS, assert_bits, bowl, flood, grid, lockstep, pitted, stripe_bufs
+from fill_stripe_cases import EPS, WORLDS, assert_bits, bowl, flood, grid, lockstep, pitted, stripe_bufs, stripe_ops, work_floats
 from test_gpu_fill import run_gpu
 
 pytestmark = pytest.mark.gpu
@@ -23,18 +23,9 @@ PARAMS = dict(epsilon=EPS, maxPasses=400, maxRounds=400)  # 400 passes: the gene
 
 @pytest.fixture(scope="module")
 def hip(nj):
-    """(sharded module, HipStripeOps) on a context that shares torch's stream: the buffers are torch CUDA tensors."""
-    from noize_job_amd import sharded as sh
-    stream = torch.cuda.Stream()
-    with torch.cuda.stream(stream):
-        tctx = nj.Context(0, stream=stream.cuda_stream)
-        yield sh, sh.HipStripeOps(tctx)
-        stream.synchronize()
-        tctx.close()
-
-
-def work_floats(nj, pitch=0):
-    return lambda plan: nj._native.lib.nz_fill_stripe_work_floats(C.byref(plan.stripe(pitch)))
+    """fill_stripe_cases.stripe_ops, once for the module."""
+    with stripe_ops(nj) as pair:
+        yield pair
 
 
 def one_stripe(hip, nj, h, params=PARAMS, pitch=None):
