@@ -522,6 +522,27 @@ namespace xshazwar.noize.hip {
             }
             jobHandle = Done(h);
         }
+        // The stage on one row stripe of a larger grid, one round (nz_drainage_stripe_round): at most `passes` passes with this stage's
+        // rain and sea level over the owned rows, against one frozen ghost row of A on each side.  The planes and words are the
+        // caller's (stripeWork: Native.nz_drainage_stripe_work_floats; rainMapRows may be IntPtr.Zero), and so are the exchange
+        // before the call -- 2 rows of heightRows and of rainMapRows before the round with `first`, 1 row of aRows before every
+        // later one -- and the vote after it (Native.nz_comm_allreduce_max_i32 on `changed`, which the next round takes as its
+        // `proceed`; IntPtr.Zero in the first).
+        public GpuJobHandle ScheduleStripe(IntPtr heightRows, IntPtr aRows, IntPtr stripeWork, IntPtr rainMapRows, ref NzStripe st, int passes,
+                                           bool first, IntPtr proceed, IntPtr changed, GpuJobHandle dependency) {
+            NzDrainageDesc desc = new NzDrainageDesc { rain = rain, seaLevel = seaLevel, maxPasses = passes, rainMap = rainMapRows };
+            ulong h;
+            Native.Check(Native.nz_drainage_stripe_round(ctx.Handle, heightRows, aRows, stripeWork, ref st, ref desc, first ? 1 : 0, proceed, changed, dependency.id, out h), "nz_drainage_stripe_round");
+            return Done(h);
+        }
+        // ... and the end of the rounds (nz_drainage_stripe_finalise): all or nothing on the owned rows by the device word
+        // `converged`, the verdict "the last vote was 0".  aRows then serves FluvialErosionStage's stripe form as its drainageIn.
+        public GpuJobHandle FinaliseStripe(IntPtr aRows, IntPtr rainMapRows, ref NzStripe st, IntPtr converged, GpuJobHandle dependency) {
+            NzDrainageDesc desc = new NzDrainageDesc { rain = rain, seaLevel = seaLevel, maxPasses = 1, rainMap = rainMapRows };
+            ulong h;
+            Native.Check(Native.nz_drainage_stripe_finalise(ctx.Handle, aRows, ref st, ref desc, converged, dependency.id, out h), "nz_drainage_stripe_finalise");
+            return Done(h);
+        }
         public override void OnDestroy() { work?.Dispose(); work = null; plane?.Dispose(); plane = null; }
     }
 

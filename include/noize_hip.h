@@ -965,7 +965,7 @@ int32_t nz_debug_fill_sweeps(int32_t sweeps);
  * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: rain or seaLevel not finite (-FLT_MAX
  * switches the sea off); rain < 0; maxPasses < 1; a NULL desc, height, drainage or work; drainage overlapping height, work
  * or rainMap; work overlapping height or rainMap.
- * There is no _rw form (the heights do not change), no receiver-code output and no stripe form. */
+ * There is no _rw form (the heights do not change) and no receiver-code output. */
 typedef struct nz_drainage_desc {
     float rain, seaLevel;
     int32_t maxPasses;
@@ -976,6 +976,46 @@ int32_t nz_drainage_area(nz_ctx *ctx, const float *height, float *drainage, floa
                          int32_t resolution, nz_handle dep, nz_handle *out);
 int32_t nz_drainage_area_batch(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_desc *desc,
                                int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
+/* The same model on a row stripe of a larger grid (nz_stripe), one ROUND per call, in the wording of nz_fill_stripe.  The
+ * receiver graph is a forest, so rounds of per-stripe relaxation against one frozen ghost row of A on each side, with one
+ * row of A exchanged between them, reach the monolithic plane bit for bit: a cell whose donors all hold their final values
+ * takes its final value in the next round at the latest, and by induction over the height of the forest the rounds end --
+ * with a signed rainMap too.  All planes have the stripe's shape and pitch, desc->rainMap included.
+ *   (The round entry carries _round in its name: one call is one round.)
+ *   nz_drainage_stripe_round runs at most desc->maxPasses passes of the pass kernel's scheme (64 x 16 tiles swept on chip against
+ *     their frozen ring, quiet tiles skipped, early return once a pass changed nothing) over the owned rows; the first pass
+ *     of a round starts a fresh series and visits every tile, because the ghost rows may have changed.  The one ghost row
+ *     of `a` on each side is FROZEN: read, never written.  Outlets, and neighbours that do not exist, follow the global grid
+ *     (global rows 0 and grows-1, columns 0 and cols-1; h <= seaLevel); a cut is no border.  Rows beyond what is needed are
+ *     neither read nor written, nor are the floats between cols and pitch.
+ *   first != 0: a mask launch turns `height` into donor bytes in `work`; a ghost-row cell's receiver looks one row further
+ *     out, so `height` needs TWO valid ghost rows towards every cut.  The start state is rain_c on the owned rows and the
+ *     ghost row: rainMap needs one valid ghost row, `a` is not read.
+ *   first == 0: `height` is not read; `work` must be the buffer of the round before, untouched in between (it carries the
+ *     donor bytes); the current A is read from `a`, whose ghost rows the caller has exchanged.
+ *   On return the owned rows of `a` hold the stripe's A, whatever the parity of the passes that ran.  `changed` (device)
+ *     receives 1 with `first`; otherwise 1 if any single update of any pass of the round changed a value (values may move
+ *     both ways, so this is not "differs from the entry state"), a budget that ran out before rest included; 0 only when
+ *     the round's first pass found every owned cell at rest against the ghost rows.
+ *   proceed (device, may be NULL): a word of zero makes every launch of the call return at once -- `a` untouched, `changed`
+ *     0 -- so that a host can enqueue a fixed budget of rounds without reading anything back.
+ *   `work` = nz_drainage_stripe_work_floats(st) floats: status words and tile bytes as nz_fill_stripe leaves them, the donor
+ *     bytes, a second A plane.
+ *   nz_drainage_stripe_finalise, on the owned rows: where *converged != 0, `a` stays; otherwise a = rain_c -- all or
+ *     nothing, as in the tile entry.  `converged` is the caller's verdict: the vote over all ranks after the last round was
+ *     0 (nz_comm_allreduce_max_i32).
+ *   One stripe over a square grid with `first`, followed by finalise with the verdict "`changed` of a second round == 0",
+ *     equals nz_drainage_area bit for bit, on the 16-byte path (all planes 16-byte aligned, pitch % 4 == 0) and the 4-byte one.
+ * NZ_ERR_INVALID, the message naming the argument, and nothing written: rain or seaLevel not finite; rain < 0;
+ * maxPasses < 1; a NULL desc, plane or word; a missing ghost row (2 with `first`, else 1); height, a, work, rainMap or the
+ * words overlapping where one of them is written. */
+int32_t nz_drainage_stripe_halo_rows(void); /* 2: the heights; A and rainMap need 1 */
+size_t nz_drainage_stripe_work_floats(const nz_stripe *st);
+int32_t nz_drainage_stripe_round(nz_ctx *ctx, const float *height, float *a, float *work, const nz_stripe *st,
+                           const nz_drainage_desc *desc, int32_t first, const int32_t *proceed, int32_t *changed,
+                           nz_handle dep, nz_handle *out);
+int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_stripe *st, const nz_drainage_desc *desc,
+                                    const int32_t *converged, nz_handle dep, nz_handle *out);
 /* Test hook, the twin of nz_debug_fill_sweeps: the cap on a drainage pass's on-chip sweeps per tile (process-wide; <= 0
  * restores the default).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_drainage_sweeps(int32_t sweeps);

@@ -215,6 +215,10 @@ SIGNATURES = {
     "nz_drainage_area_work_floats": (_sz, [_i, _i]),
     "nz_drainage_area": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, drain_p, _i] + _tail),
     "nz_drainage_area_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, drain_p, _i, _i] + _tail),
+    "nz_drainage_stripe_halo_rows": (_i, []),
+    "nz_drainage_stripe_work_floats": (_sz, [stripe_p]),
+    "nz_drainage_stripe_round": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, drain_p, _i, dev_ptr, dev_ptr] + _tail),
+    "nz_drainage_stripe_finalise": (_i, [ctx_p, dev_ptr, stripe_p, drain_p, dev_ptr] + _tail),
     "nz_debug_drainage_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),

@@ -24,12 +24,34 @@
 //            threads); "changed" looks at every single update (`relax`).
 // A series at rest holds the fixed point in BOTH planes, so the finalise launch has nothing to copy: it sets the protocol's
 // verdict and, when the last pass that ran did change something, puts rain_c back into every cell: all or nothing.
+//
+// WIN, the stripe form (nz_drainage_stripe_round), on the pattern of nz_fill.hip's: one ROUND on the owned rows [r0, r1) of a
+// stripe-shaped buffer with a pitch; the workgroups tile the owned rows, the grid's bounds are the global grid's seen from
+// the buffer.  The mask launch of a round with `first` reads heights two rows beyond the owned ones (the receiver of a cell
+// of a ghost row looks one row further out) and stores donor bytes for the owned rows only.  The one row of A on each side
+// of the owned rows is FROZEN: read from the caller's plane in every pass (in a round with `first`: rain_c), never written,
+// whichever of the two planes the pass alternates between.  When the owned rows end inside a tile, the frozen row lies in
+// a thread's own slot: it is loaded, has no donor byte and is not stored.  status[GO], pass 0 of a round that continues
+// from A (all tiles live) and the caller's `changed` word are the fill stripe's (nz_relax_pass.hpp), except that only the
+// mask launch and pass 0 read status[GO]: the later passes of a round that does not go return at their gate; `changed` follows
+// `relax`: a pass 0 in which any single update changed a value stores 1, and a pass 0 that stores nothing has found every
+// owned cell at rest against the frozen rows.
 #include "nz_internal.hpp"
 #include "nz_receiver.hpp"
 #include "nz_relax_pass.hpp"
 #include "nz_tile64.hpp"
 
 namespace {
+
+// WIN: the owned rows of one stripe-shaped buffer, rows in buffer coordinates; the pitch travels as the kernels' `res`
+struct drain_win {
+    int xhi;                // last column of the grid
+    int zlo, zhi;           // first and last row of the global grid
+    int r0, r1;             // owned rows [r0, r1)
+    int ghost_from_rain;    // the frozen rows are the start state rain_c (a round with `first`), else the caller's plane's
+    int *status;            // the round's status words (the mask launch reads status[GO])
+    int *changed_out;       // the caller's word
+};
 
 using nz_recv::NONE;
 using nz_recv::receiver;
@@ -38,24 +60,31 @@ using namespace nz_relax;   // the status words and the pass protocol
 
 // ---- the mask launch: heights -> donor bytes ----
 // VEC: 16-byte height reads; WORD: the four donor bytes of a thread as one 32-bit store (res % 4 == 0)
-template <bool VEC, bool WORD>
+// WIN: res is the pitch; heights are read on the rows within 2 of the owned ones, donor bytes stored for the owned rows,
+// at the cell's index in the plane
+template <bool VEC, bool WORD, bool WIN>
 __global__ __launch_bounds__(FT) void drainage_mask_kernel(const float *__restrict__ h, unsigned char *__restrict__ donors,
-                                                           float sea, int res) {
+                                                           float sea, int res, drain_win win) {
     __shared__ __attribute__((aligned(16))) float H[(FZ + 4) * LP];          // radius 2: LDS row = plane row - z0 + 2
     __shared__ __attribute__((aligned(16))) unsigned RW[(FZ + 2) * LP / 4];  // radius 1, one byte per cell
     unsigned char *RC = reinterpret_cast<unsigned char *>(RW);
 
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * FX, z0 = blockIdx.y * FZ;
-    const size_t base = (size_t)blockIdx.z * res * res;
-    const int hi = res - 1;
-    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= 0 && pz <= hi; };
-    auto on_border = [&](int px, int pz) { return px == 0 || px == hi || pz == 0 || pz == hi; };
+    if constexpr (WIN) {
+        if (!win.status[ST_GO]) return;
+    }
+    const int x0 = blockIdx.x * FX, z0 = (WIN ? win.r0 : 0) + blockIdx.y * FZ;
+    const size_t base = WIN ? 0 : (size_t)blockIdx.z * res * res;
+    const int hi = WIN ? win.xhi : res - 1;                            // last column
+    const int zlo = WIN ? win.zlo : 0, zhi = WIN ? win.zhi : res - 1;  // the grid's rows
+    const int rlo = WIN ? (zlo > win.r0 - 2 ? zlo : win.r0 - 2) : 0, rhi = WIN ? (zhi < win.r1 + 1 ? zhi : win.r1 + 1) : hi;  // rows read
+    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= rlo && pz <= rhi; };
+    auto on_border = [&](int px, int pz) { return px == 0 || px == hi || pz == zlo || pz == zhi; };
 
     const int tz = tid >> 4, tx = (tid & 15) * 4;
     const int px = x0 + tx, pz = z0 + tz;
     const size_t c0 = base + (size_t)pz * res + px;
-    const bool row_in = pz <= hi;
+    const bool row_in = pz <= rhi;  // WIN: the two rows below the owned ones lie in own slots when the tile reaches them
     const bool quad = row_in && px + 3 <= hi;
 
     // ---- fill: a cell outside the grid reads as +0 and is never looked at ----
@@ -116,7 +145,7 @@ __global__ __launch_bounds__(FT) void drainage_mask_kernel(const float *__restri
     __syncthreads();
 
     // ---- the donor bytes of the own cells ----
-    if (!row_in || px > hi) return;
+    if (!(WIN ? pz < win.r1 : row_in) || px > hi) return;
     unsigned cw[3][6];  // the receiver codes of the window
     window_bytes(RW, tz, tx, cw);
     unsigned word = 0;
@@ -135,41 +164,55 @@ __global__ __launch_bounds__(FT) void drainage_mask_kernel(const float *__restri
 
 // ---- a pass ----
 // FIRST: the start state rain_c, no A plane is read; VEC: 16-byte accesses to the float planes and a 32-bit one to the
-// donor bytes (all planes 16-byte aligned, res % 4 == 0); MAP: rain_c = rain * rain_map[c]
-template <bool FIRST, bool VEC, bool MAP>
-__global__ __launch_bounds__(FT) void drainage_pass_kernel(const unsigned char *__restrict__ donors,
-                                                           const float *__restrict__ rain_map,
-                                                           const float *__restrict__ a_in, float *__restrict__ a_out,
-                                                           int *status, const unsigned char *__restrict__ flags_in,
-                                                           unsigned char *__restrict__ flags_out, float rain, int res,
-                                                           int pass, int sweeps) {
+// donor bytes (all planes 16-byte aligned, res % 4 == 0); MAP: rain_c = rain * rain_map[c]; WIN: res is the pitch
+// The cap of 102 SGPRs is what eight waves per SIMD allow.  The tile forms take 96 to 99 and compile as without it; the
+// stripe forms that read A would take 103 to 106 and seven waves, and keep one value in a VGPR lane instead (measured:
+// DESIGN.md section 4, "drainage area on row stripes")
+template <bool FIRST, bool VEC, bool MAP, bool WIN>
+__global__ __launch_bounds__(FT) __attribute__((amdgpu_num_sgpr(102)))
+void drainage_pass_kernel(const unsigned char *__restrict__ donors, const float *__restrict__ rain_map,
+                          const float *__restrict__ a_in, float *__restrict__ a_out, int *status,
+                          const unsigned char *__restrict__ flags_in, unsigned char *__restrict__ flags_out, float rain, int res,
+                          int pass, int sweeps, drain_win win) {
     __shared__ __attribute__((aligned(16))) float A[(FZ + 2) * LP];  // radius 1: LDS row = plane row - z0 + 1
     const int tid = threadIdx.x;
 
+    if constexpr (WIN) {
+        // pass 0 alone asks: round_begin has zeroed the three words, so behind a pass 0 that returned here every later
+        // pass finds "the pass before changed nothing" at its gate, without a load of its own
+        if (pass == 0 && !status[ST_GO]) return;
+    }
+    const bool all_live = WIN && pass == 0;  // a round's first pass: nothing is known about the pass before
     const bool t0 = tid == 0;
-    const int prev = series_gate<FIRST>(status, t0, pass, false);
+    const int prev = series_gate<FIRST>(status, t0, pass, all_live);
     if (!prev) return;
     const int tnx = gridDim.x, tnz = gridDim.y;
     const size_t tile0 = (size_t)blockIdx.z * tnx * tnz;
     const size_t me = tile0 + (size_t)blockIdx.y * tnx + blockIdx.x;  // this tile's byte
-    if (!FIRST) {
+    if (!FIRST && !all_live) {
         if (!__syncthreads_or(tile_live(flags_in, tile0, tnx, tnz, tid))) {
             if (t0) flags_out[me] = 0;
             return;
         }
     }
 
-    const int x0 = blockIdx.x * FX, z0 = blockIdx.y * FZ;
-    const size_t base = (size_t)blockIdx.z * res * res;
-    const int hi = res - 1;
-    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= 0 && pz <= hi; };
+    const int x0 = blockIdx.x * FX, z0 = (WIN ? win.r0 : 0) + blockIdx.y * FZ;
+    const size_t base = WIN ? 0 : (size_t)blockIdx.z * res * res;
+    const int hi = WIN ? win.xhi : res - 1;                            // last column
+    const int zlo = WIN ? win.zlo : 0, zhi = WIN ? win.zhi : res - 1;  // the grid's rows
+    const int rlo = WIN ? (zlo > win.r0 - 1 ? zlo : win.r0 - 1) : 0, rhi = WIN ? (zhi < win.r1 ? zhi : win.r1) : hi;  // rows read
+    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= rlo && pz <= rhi; };
     auto rain_at = [&](size_t q) { return MAP ? rain * rain_map[q] : rain; };
+    // WIN: A of a cell of a frozen row.  The caller's plane is one of the two a round alternates between: pass p reads it
+    // when p is even and writes it (its owned rows) when p is odd
+    const float *a_ghost = pass & 1 ? a_out : a_in;
+    auto ghost = [&](size_t q) { return win.ghost_from_rain ? rain_at(q) : a_ghost[q]; };
 
     // this thread's four cells
     const int tz = tid >> 4, tx = (tid & 15) * 4;
     const int px = x0 + tx, pz = z0 + tz;
     const size_t c0 = base + (size_t)pz * res + px;
-    const bool row_in = pz <= hi;
+    const bool row_in = WIN ? pz < win.r1 : pz <= hi;
     const bool quad = VEC && row_in && px + 3 <= hi;  // VEC: res % 4 == 0, so a quad lies inside or outside as a whole
 
     // ---- fill ----
@@ -200,6 +243,13 @@ __global__ __launch_bounds__(FT) void drainage_pass_kernel(const unsigned char *
 #pragma unroll
         for (int j = 0; j < 4; j++) ac[j] = rc[j];
     }
+    if constexpr (WIN) {
+        if (pz == win.r1 && pz <= zhi) {  // the frozen row below, inside the tile: no donor byte (row_in is false), not stored
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (px + j <= hi) ac[j] = ghost(c0 + j);
+        }
+    }
     *reinterpret_cast<float4 *>(&A[(tz + 1) * LP + LC + tx]) = make_float4(ac[0], ac[1], ac[2], ac[3]);
     if (tid < NRING) {
         int lz, lx;
@@ -208,7 +258,8 @@ __global__ __launch_bounds__(FT) void drainage_pass_kernel(const unsigned char *
         float v = 0.0f;
         if (inside(qx, qz)) {
             const size_t q = base + (size_t)qz * res + qx;
-            if constexpr (FIRST) v = rain_at(q);
+            if (WIN && (qz < win.r0 || qz >= win.r1)) v = ghost(q);
+            else if constexpr (FIRST) v = rain_at(q);
             else v = a_in[q];
         }
         A[lz * LP + lx] = v;
@@ -267,7 +318,12 @@ __global__ __launch_bounds__(FT) void drainage_pass_kernel(const unsigned char *
             a_out[c0 + j] = ac[j];
         }
     }
-    if (t0) close_tile<FIRST>(status, flags_out, me, pass, moved);
+    if (t0) {
+        close_tile<FIRST>(status, flags_out, me, pass, moved);
+        if constexpr (WIN) {
+            if (!FIRST && pass == 0 && moved) *win.changed_out = 1;
+        }
+    }
 }
 
 // all or nothing: the fixed point stands in `drainage` when the last pass that ran changed nothing (nz_drainage_area keeps
@@ -283,6 +339,19 @@ __global__ __launch_bounds__(256) void drainage_finalise_kernel(float *__restric
     drainage[i] = MAP ? rain * rain_map[i] : rain;
 }
 
+// the stripe's all or nothing on the owned rows, by the caller's verdict
+template <bool MAP>
+__global__ __launch_bounds__(256) void drainage_stripe_finalise_kernel(float *__restrict__ a, const float *__restrict__ rain_map,
+                                                                       const int *converged, float rain, int pitch, int cols,
+                                                                       int r0, int r1) {
+    const int x = blockIdx.x * 256 + threadIdx.x, z = r0 + blockIdx.y;
+    if (x >= cols || z >= r1 || *converged) return;
+    const size_t i = (size_t)z * pitch + x;
+    a[i] = MAP ? rain * rain_map[i] : rain;
+}
+
+const drain_win NO_WIN{};  // the tile forms
+
 }  // namespace
 
 int32_t nz_launch_drainage_mask(hipStream_t s, const float *h, unsigned char *donors, float sea, int res, int count) {
@@ -290,20 +359,35 @@ int32_t nz_launch_drainage_mask(hipStream_t s, const float *h, unsigned char *do
     const dim3 grid(tiles_x(res), tiles_z(res), count);
     const bool word = res % 4 == 0 && (reinterpret_cast<uintptr_t>(donors) & 3) == 0;
     const bool vec = res % 4 == 0 && (reinterpret_cast<uintptr_t>(h) & 15) == 0;
-    if (vec && word) NZ_LAUNCH((drainage_mask_kernel<true, true>), grid, dim3(FT), 0, s, h, donors, sea, res);
-    else if (word) NZ_LAUNCH((drainage_mask_kernel<false, true>), grid, dim3(FT), 0, s, h, donors, sea, res);
-    else NZ_LAUNCH((drainage_mask_kernel<false, false>), grid, dim3(FT), 0, s, h, donors, sea, res);
+    if (vec && word) NZ_LAUNCH((drainage_mask_kernel<true, true, false>), grid, dim3(FT), 0, s, h, donors, sea, res, NO_WIN);
+    else if (word) NZ_LAUNCH((drainage_mask_kernel<false, true, false>), grid, dim3(FT), 0, s, h, donors, sea, res, NO_WIN);
+    else NZ_LAUNCH((drainage_mask_kernel<false, false, false>), grid, dim3(FT), 0, s, h, donors, sea, res, NO_WIN);
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_drainage_stripe_mask(hipStream_t s, const float *h, unsigned char *donors, int *status, float sea,
+                                       const nz_geom &g, int zlo, int zhi) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    const dim3 grid(tiles_x(g.cols), tiles_z(g.or1 - g.or0), 1);
+    const bool word = g.cols % 4 == 0 && g.pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(donors) & 3) == 0;
+    const bool vec = word && (reinterpret_cast<uintptr_t>(h) & 15) == 0;  // every row starts 16-byte aligned
+    const drain_win win{g.cols - 1, zlo, zhi, g.or0, g.or1, 0, status, nullptr};
+    if (vec) NZ_LAUNCH((drainage_mask_kernel<true, true, true>), grid, dim3(FT), 0, s, h, donors, sea, g.pitch, win);
+    else if (word) NZ_LAUNCH((drainage_mask_kernel<false, true, true>), grid, dim3(FT), 0, s, h, donors, sea, g.pitch, win);
+    else NZ_LAUNCH((drainage_mask_kernel<false, false, true>), grid, dim3(FT), 0, s, h, donors, sea, g.pitch, win);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
 
 namespace {
-template <bool FIRST, bool VEC>
+// the form of a pass by <FIRST, VEC, MAP, WIN>
+template <bool FIRST, bool VEC, bool WIN>
 void launch_pass(bool map, dim3 grid, hipStream_t s, const unsigned char *donors, const float *rain_map, const float *a_in,
                  float *a_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain, int res,
-                 int pass, int sweeps) {
-    if (map) NZ_LAUNCH((drainage_pass_kernel<FIRST, VEC, true>), grid, dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps);
-    else NZ_LAUNCH((drainage_pass_kernel<FIRST, VEC, false>), grid, dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps);
+                 int pass, int sweeps, const drain_win &win) {
+    if (map) NZ_LAUNCH((drainage_pass_kernel<FIRST, VEC, true, WIN>), grid, dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, win);
+    else NZ_LAUNCH((drainage_pass_kernel<FIRST, VEC, false, WIN>), grid, dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, win);
 }
 }  // namespace
 
@@ -317,12 +401,44 @@ int32_t nz_launch_drainage_pass(hipStream_t s, const unsigned char *donors, cons
     const bool vec = (bits & 15) == 0 && res % 4 == 0;  // a row, and with it a tile of the batch, starts 16-byte aligned
     const bool map = rain_map != nullptr;
     if (pass == 0) {
-        if (vec) launch_pass<true, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps);
-        else launch_pass<true, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps);
+        if (vec) launch_pass<true, true, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
+        else launch_pass<true, false, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
     } else {
-        if (vec) launch_pass<false, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps);
-        else launch_pass<false, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps);
+        if (vec) launch_pass<false, true, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
+        else launch_pass<false, false, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
     }
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_drainage_stripe_pass(hipStream_t s, const unsigned char *donors, const float *rain_map, const float *a_in,
+                                       float *a_out, int *status, const unsigned char *flags_in,
+                                       unsigned char *flags_out, int *changed, float rain, const nz_geom &g, int zlo, int zhi,
+                                       int first, int pass, int sweeps) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    const dim3 grid(tiles_x(g.cols), tiles_z(g.or1 - g.or0), 1);
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(rain_map) | reinterpret_cast<uintptr_t>(a_in) |
+                           reinterpret_cast<uintptr_t>(a_out) | reinterpret_cast<uintptr_t>(donors);
+    const bool vec = (bits & 15) == 0 && g.cols % 4 == 0 && g.pitch % 4 == 0;  // every row starts 16-byte aligned
+    const bool map = rain_map != nullptr;
+    const drain_win win{g.cols - 1, zlo, zhi, g.or0, g.or1, first, status, changed};
+    if (first && pass == 0) {
+        if (vec) launch_pass<true, true, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
+        else launch_pass<true, false, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
+    } else {
+        if (vec) launch_pass<false, true, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
+        else launch_pass<false, false, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
+    }
+    NZ_HIP(hipGetLastError());
+    return NZ_OK;
+}
+
+int32_t nz_launch_drainage_stripe_finalise(hipStream_t s, float *a, const float *rain_map, const int *converged, float rain,
+                                           const nz_geom &g) {
+    if (g.or1 <= g.or0 || g.cols <= 0) return NZ_OK;
+    const dim3 grid((g.cols + 255) / 256, g.or1 - g.or0);
+    if (rain_map) NZ_LAUNCH(drainage_stripe_finalise_kernel<true>, grid, dim3(256), 0, s, a, rain_map, converged, rain, g.pitch, g.cols, g.or0, g.or1);
+    else NZ_LAUNCH(drainage_stripe_finalise_kernel<false>, grid, dim3(256), 0, s, a, rain_map, converged, rain, g.pitch, g.cols, g.or0, g.or1);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

@@ -418,6 +418,18 @@ int32_t nz_launch_drainage_pass(hipStream_t s, const unsigned char *donors, cons
                                 float *a_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain,
                                 int res, int count, int pass, int sweeps);
 int32_t nz_launch_drainage_finalise(hipStream_t s, float *drainage, const float *rain_map, int *status, float rain, size_t n);
+// the stripe form, one round (nz_drainage_stripe_round), between the fill stripe's round_begin and round_end launches: mask stores
+// the donor bytes of the owned rows [g.or0, g.or1) at the cells' plane indices, from heights up to two rows beyond them; a pass
+// works on the owned rows of stripe-shaped planes against the frozen rows or0 - 1 and or1 of the caller's plane -- a_in of an
+// even pass, a_out of an odd one -- or, with first, of rain_c; [zlo, zhi] the global grid in buffer rows; finalise is all or nothing on the owned rows by the caller's verdict
+int32_t nz_launch_drainage_stripe_mask(hipStream_t s, const float *h, unsigned char *donors, int *status, float sea,
+                                       const nz_geom &g, int zlo, int zhi);
+int32_t nz_launch_drainage_stripe_pass(hipStream_t s, const unsigned char *donors, const float *rain_map, const float *a_in,
+                                       float *a_out, int *status, const unsigned char *flags_in,
+                                       unsigned char *flags_out, int *changed, float rain, const nz_geom &g, int zlo, int zhi,
+                                       int first, int pass, int sweeps);
+int32_t nz_launch_drainage_stripe_finalise(hipStream_t s, float *a, const float *rain_map, const int *converged, float rain,
+                                           const nz_geom &g);
 
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid

@@ -593,6 +593,15 @@ extern "C" int32_t nz_debug_drainage_sweeps(int32_t sweeps) {
     return drainage_sweeps.exchange(sweeps > 0 ? sweeps : DRAINAGE_SWEEPS);
 }
 
+static int32_t check_drainage_desc(const nz_drainage_desc *d) {
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(std::isfinite(d->rain), "rain is not finite");
+    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(d->rain >= 0.0f, "rain %g < 0", (double)d->rain);
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    return NZ_OK;
+}
+
 static int32_t drainage_impl(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_desc *d, int res,
                              int count, nz_handle dep, nz_handle *out) {
     NZ_BEGIN(ctx, dep);
@@ -602,10 +611,7 @@ static int32_t drainage_impl(nz_ctx *ctx, const float *height, float *drainage, 
     NZ_REQUIRE(height, "height is NULL");
     NZ_REQUIRE(drainage, "drainage is NULL");
     NZ_REQUIRE(work, "work is NULL");
-    NZ_REQUIRE(std::isfinite(d->rain), "rain is not finite");
-    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
-    NZ_REQUIRE(d->rain >= 0.0f, "rain %g < 0", (double)d->rain);
-    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    NZ_TRY(check_drainage_desc(d));
     const drainage_layout L = drainage_layout_of(res, count);
     const size_t n = L.f.n;
     const nz_named_plane writes[] = {{"drainage", drainage, n}, {"work", work, L.total()}};
@@ -635,6 +641,88 @@ extern "C" int32_t nz_drainage_area_batch(nz_ctx *ctx, const float *height, floa
                                           const nz_drainage_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
                                           nz_handle *out) {
     return drainage_impl(ctx, height, drainage, work, desc, resolution, count, dep, out);
+}
+
+// ---- the stripe form (include/noize_hip.h): one round of passes on the owned rows against one frozen row of A on each side ----
+// `work` as in the tile form, the tile bytes counted over the owned rows: status words, two generations of tile bytes, one
+// donor byte per cell of the stripe's plane (at the cell's index; only the owned rows are used) and one A plane of the
+// stripe's shape, last.  The round's begin and end launches are the fill stripe's: they know status words and planes only.
+static drainage_layout drainage_stripe_layout(const nz_stripe &st) {
+    const fill_layout f = fill_stripe_layout(st);
+    return drainage_layout{f, (f.n + 15) / 16 * 4};
+}
+
+extern "C" int32_t nz_drainage_stripe_halo_rows(void) { return 2; }
+
+extern "C" size_t nz_drainage_stripe_work_floats(const nz_stripe *st) {
+    if (!nz_stripe_plane_floats(st) || st->own0 < 0 || st->own1 < st->own0) return 0;
+    return drainage_stripe_layout(*st).total();
+}
+
+// the two words of a stripe call are ints, not planes of floats: apart from every plane of the call and from each other
+static int32_t check_stripe_words(const int32_t *changed, const char *cname, const int32_t *other, const char *oname,
+                                  const nz_named_plane *planes, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        NZ_REQUIRE(!nz_bytes_overlap(changed, 4, planes[i].p, planes[i].floats * 4), "%s overlaps %s", cname, planes[i].name);
+        NZ_REQUIRE(!nz_bytes_overlap(other, 4, planes[i].p, planes[i].floats * 4), "%s overlaps %s", oname, planes[i].name);
+    }
+    NZ_REQUIRE(!nz_bytes_overlap(changed, 4, other, 4), "%s overlaps %s", cname, oname);
+    return NZ_OK;
+}
+
+extern "C" int32_t nz_drainage_stripe_round(nz_ctx *ctx, const float *height, float *a, float *work, const nz_stripe *st,
+                                      const nz_drainage_desc *desc, int32_t first, const int32_t *proceed, int32_t *changed,
+                                      nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_drainage_desc(desc));
+    NZ_TRY(nz_check_stripe(st, first ? 2 : 1));  // the heights at radius 2, A and the rain map at radius 1
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(a, "a is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(changed, "changed is NULL");
+    const nz_geom g = nz_geom_from_stripe(*st);
+    const drainage_layout L = drainage_stripe_layout(*st);
+    const size_t span = nz_stripe_span(*st);
+    const nz_named_plane writes[] = {{"a", a, span}, {"work", work, L.total()}};
+    const nz_named_plane reads[] = {{"height", height, span}, {"rainMap", desc->rainMap, span}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    const nz_named_plane all[] = {writes[0], writes[1], reads[0], reads[1]};
+    NZ_TRY(check_stripe_words(changed, "changed", proceed, "proceed", all, std::size(all)));
+    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
+    unsigned char *donors = reinterpret_cast<unsigned char *>(c.planes);
+    float *planes[2] = {a, c.planes + L.donor_floats};  // pass p reads plane p & 1 and writes the other
+    const int sweeps = drainage_sweeps.load(), passes = desc->maxPasses;
+    const int zlo = nz_stripe_grid_lo(*st), zhi = nz_stripe_grid_hi(*st) - 1;
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_fill_round_begin(ctx->stream, c.status, proceed, changed, first != 0));
+    if (first) NZ_TRY(nz_launch_drainage_stripe_mask(ctx->stream, height, donors, c.status, desc->seaLevel, g, zlo, zhi));
+    for (int p = 0; p < passes; p++) {
+        if (p == passes - 1 && !(passes & 1)) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_drainage_stripe_pass(ctx->stream, donors, desc->rainMap, planes[p & 1], planes[(p + 1) & 1],
+                                              c.status, c.flags[(p + 1) & 1], c.flags[p & 1], changed, desc->rain, g, zlo, zhi,
+                                              first != 0, p, sweeps));
+    }
+    if (passes & 1) {  // the last pass wrote the work plane
+        nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fill_round_end(ctx->stream, a, planes[1], c.status, passes, g));
+    }
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_stripe *st, const nz_drainage_desc *desc,
+                                               const int32_t *converged, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(check_drainage_desc(desc));
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(a, "a is NULL");
+    NZ_REQUIRE(converged, "converged is NULL");
+    const size_t span = nz_stripe_span(*st);
+    NZ_REQUIRE(!nz_planes_overlap(a, span, desc->rainMap, span), "a overlaps rainMap");
+    NZ_REQUIRE(!nz_bytes_overlap(converged, 4, a, span * 4), "converged overlaps a");
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_drainage_stripe_finalise(ctx->stream, a, desc->rainMap, converged, desc->rain, nz_geom_from_stripe(*st)));
+    return nz_ctx_finish(ctx, out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -7,6 +7,9 @@
 //          host_demo <resolution> <out.f32> fill        (DepressionFillStage with recordDepth on a simplex tile, then the SAME
 //                            stage on a batch of 64 tiles of resolution / 8 -- equal length, more 64 x 16 tiles: heights,
 //                            depth, batch heights back to back; "passes converged" of either run on stdout)
+//          host_demo <resolution> <out.f32> drainage-stripe   (a filled simplex tile as ONE row stripe through
+//                            DrainageAreaStage::ScheduleStripe with `first` and FinaliseStripe with a word of 1: heights,
+//                            drainage back to back; the round's `changed` word on stdout)
 //          host_demo <resolution> <out.f32> live <particles> <cycles>   (cellular fBm -> LiveErosion, seeds 3, 14, 25, ...:
 //                                                                         height, pool, flow planes back to back)
 //          host_demo <resolution> <out.f32> sharded <stripes> [mode overlap]   (ShardedPipeline on ONE rank: the grid as
@@ -41,6 +44,7 @@ int main(int argc, char **argv) {
     const bool reduce = argc > 3 && std::strcmp(argv[3], "reduce") == 0;
     const bool context = argc > 3 && std::strcmp(argv[3], "context") == 0;
     const bool fill = argc > 3 && std::strcmp(argv[3], "fill") == 0;
+    const bool drainage_stripe = argc > 3 && std::strcmp(argv[3], "drainage-stripe") == 0;
     const int batch = argc > 4 && std::strcmp(argv[3], "batch") == 0 ? std::atoi(argv[4]) : 0;
     // `rw`: the tile is a READ / WRITE plane pair and the stencil stages swap it instead of flushing (nz_*_rw)
     const bool live = argc > 5 && std::strcmp(argv[3], "live") == 0;
@@ -227,6 +231,41 @@ int main(int argc, char **argv) {
             pipe.RunToCompletion();
             std::printf("%d %d\n", lakes.passes(), lakes.converged() ? 1 : 0);
             tiles.CopyTo(host.data() + 2 * n);
+            FILE *f = std::fopen(argv[2], "wb");
+            if (!f || std::fwrite(host.data(), sizeof(float), host.size(), f) != host.size()) throw std::runtime_error("write failed");
+            std::fclose(f);
+            pipe.Destroy();
+        } else if (drainage_stripe) {
+            const size_t n = (size_t)res * res;
+            DeviceTile tile(ctx, n), area(ctx, n), words(ctx, 4);
+            NoiseStage noise(ctx);
+            noise.noiseType = FractalNoise::Simplex;
+            noise.hurst = 0.4f;
+            noise.octaves = 6;
+            noise.noiseSize = 300;
+            DepressionFillStage lakes(ctx);
+            BasePipeline pipe({&noise, &lakes});
+            GeneratorData gd;
+            gd.uuid = "host-demo-drainage-stripe";
+            gd.data = &tile;
+            gd.resolution = res;
+            gd.xpos = 37;
+            gd.zpos = 11;
+            pipe.Enqueue(&gd);
+            pipe.RunToCompletion();
+            const nz_stripe st{res, res, 0, res, 0, res, 0};  // the whole grid as one stripe: no cut, no ghost row
+            DeviceTile work(ctx, nz_drainage_stripe_work_floats(&st));
+            const int32_t start[4] = {-7, -7, 1, 0};  // changed, spare, the verdict
+            words.CopyFrom(reinterpret_cast<const float *>(start));
+            int32_t *w = reinterpret_cast<int32_t *>(words.ptr);
+            DrainageAreaStage rivers(ctx);
+            JobHandle h = rivers.ScheduleStripe(tile.ptr, area.ptr, work.ptr, nullptr, st, 64 + res / 4, true, nullptr, w, JobHandle());
+            rivers.FinaliseStripe(area.ptr, nullptr, st, w + 2, h).Complete();
+            std::vector<float> host(2 * n), got(4);
+            tile.CopyTo(host.data());
+            area.CopyTo(host.data() + n);
+            words.CopyTo(got.data());
+            std::printf("%d\n", reinterpret_cast<const int32_t *>(got.data())[0]);
             FILE *f = std::fopen(argv[2], "wb");
             if (!f || std::fwrite(host.data(), sizeof(float), host.size(), f) != host.size()) throw std::runtime_error("write failed");
             std::fclose(f);

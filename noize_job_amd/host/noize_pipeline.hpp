@@ -925,6 +925,29 @@ class DrainageAreaStage : public PipelineStage {
         }
         jobHandle = done(h);
     }
+    // The stage on one row stripe of a larger grid, one round (nz_drainage_stripe_round): at most `passes` passes with this stage's
+    // rain and sea level over the owned rows, against one frozen ghost row of A on each side.  The planes and words are the
+    // caller's (stripeWork: nz_drainage_stripe_work_floats; rainMapRows may be NULL), and so are the exchange before the call
+    // -- 2 rows of heightRows and of rainMapRows before the round with `first`, 1 row of aRows before every later one -- and
+    // the vote after it (nz_comm_allreduce_max_i32 on `changed`, which the next round takes as its `proceed`; NULL in the first).
+    JobHandle ScheduleStripe(const float *heightRows, float *aRows, float *stripeWork, const float *rainMapRows,
+                             const nz_stripe &st, int passes, bool first, const int32_t *proceed, int32_t *changed,
+                             JobHandle dependency) {
+        const nz_drainage_desc desc{rain, seaLevel, passes, rainMapRows};
+        nz_handle h = 0;
+        check(nz_drainage_stripe_round(ctx, heightRows, aRows, stripeWork, &st, &desc, first, proceed, changed, dependency.id, &h),
+              "nz_drainage_stripe_round");
+        return done(h);
+    }
+    // ... and the end of the rounds (nz_drainage_stripe_finalise): all or nothing on the owned rows by the device word
+    // `converged`, the verdict "the last vote was 0".  aRows then serves FluvialErosionStage's stripe form as its drainageIn.
+    JobHandle FinaliseStripe(float *aRows, const float *rainMapRows, const nz_stripe &st, const int32_t *converged,
+                             JobHandle dependency) {
+        const nz_drainage_desc desc{rain, seaLevel, 1, rainMapRows};
+        nz_handle h = 0;
+        check(nz_drainage_stripe_finalise(ctx, aRows, &st, &desc, converged, dependency.id, &h), "nz_drainage_stripe_finalise");
+        return done(h);
+    }
     const float *drainage() const { return !work ? nullptr : out ? out->ptr : plane->ptr; }  // nullptr before a payload
     size_t drainageLength() const { return (size_t)count * resolution * resolution; }
     int passes() const { return status(0); }                // -1 before the first run

@@ -482,6 +482,54 @@ def run_fill_lockstep(ops_list, plans, params, bufs_list, copy_rows):
                                copy_rows)
 
 
+# ---- drainage area on row stripes (nz_drainage_stripe_round) --------------------------------------------------------------------
+DRAINAGE_DEFAULTS = dict(rain=1.0, seaLevel=-3.4028234663852886e38, maxPasses=64, maxRounds=64)
+
+
+def drainage_steps(ops, plan, params, bufs):
+    """The drainage area on one rank's stripe as a generator like fill_steps: rounds of ops.drainage (at most maxPasses
+    passes over the owned rows against one frozen ghost row of A on each side), and between them
+      an exchange request (planes, n, n)   before round 0 the height plane -- and the rain map when given -- 2 rows (a
+                                           ghost-row cell's receiver looks one row further out); before every later round
+                                           the A plane, 1 row
+      a vote request (VOTE, word)          after every round, as in fill_steps
+    The rounds stop when the vote is 0 or after maxRounds; round r > 0 is handed the vote of round r - 1 as its `proceed`
+    word.  Then ops.drainage_finalise with the verdict vote == 0 on every rank: all or nothing.  bufs: "H" (the heights on
+    the owned rows; not modified), "A", "work" (nz_drainage_stripe_work_floats), "words" (int32[3]) and optionally
+    "rainMap" (owned rows filled); plan.halo >= 2.  Returns (A plane, rounds, converged); the A plane serves as
+    bufs["drainageIn"] of fluvial_steps as it stands."""
+    prm = _stage_params(DRAINAGE_DEFAULTS, "a parameter of the sharded drainage area", params)
+    assert plan.halo >= 2, "the heights need 2 ghost rows"
+    words, rain_map = bufs["words"], bufs.get("rainMap")
+    maps = dict(rainMap=rain_map) if rain_map is not None else {}
+    vote, rounds = 1, 0
+    while vote != 0 and rounds < prm["maxRounds"]:
+        if rounds == 0:
+            yield [bufs["H"]] + ([rain_map] if rain_map is not None else []), 2, 2
+        else:
+            yield [bufs["A"]], 1, 1
+        word = words[rounds & 1:(rounds & 1) + 1]
+        ops.drainage(bufs["H"], bufs["A"], bufs["work"], plan, prm, rounds == 0,
+                     None if rounds == 0 else words[(rounds - 1) & 1:((rounds - 1) & 1) + 1], word, **maps)
+        vote = yield VOTE, word
+        rounds += 1
+    words[2:3].fill_(1 if vote == 0 else 0)
+    ops.drainage_finalise(bufs["A"], plan, prm, words[2:3], **maps)
+    return bufs["A"], rounds, vote == 0
+
+
+def run_drainage(ops, comm, plan, params, bufs):
+    """drainage_steps on this rank: exchanges through comm.exchange, votes through comm.allreduce_max (TorchComm,
+    NativeComm, NoComm); returns (A plane, rounds, converged)."""
+    return _run_steps(drainage_steps(ops, plan, params, bufs), comm, plan)
+
+
+def run_drainage_lockstep(ops_list, plans, params, bufs_list, copy_rows):
+    """All ranks inside one process, as run_fill_lockstep; returns every rank's (A plane, rounds, converged)."""
+    return _run_steps_lockstep([drainage_steps(o, pl, params, b) for o, pl, b in zip(ops_list, plans, bufs_list)], plans,
+                               copy_rows)
+
+
 class HipStripeOps:
     """Stripe operations on device memory through the C ABI.  Buffers are objects with `.data_ptr()`
     (torch CUDA tensors used as plain HBM allocations); state buffers are indexable by plane."""
@@ -560,6 +608,22 @@ class HipStripeOps:
         st = plan.stripe(pitch)
         self._call("nz_fill_stripe_finalise", h.data_ptr(), w.data_ptr(), depth.data_ptr() if depth is not None else None,
                    C.byref(st), converged.data_ptr())
+
+    def _drainage_desc(self, prm, rainMap):
+        return N.DrainageDesc(prm["rain"], prm["seaLevel"], prm["maxPasses"], rainMap.data_ptr() if rainMap is not None else None)
+
+    def drainage(self, h, a, work, plan, prm, first, proceed, changed, rainMap=None, pitch=0):
+        """nz_drainage_stripe_round: one round, at most prm["maxPasses"] passes.  proceed: an int32 device word or None; changed: one."""
+        st = plan.stripe(pitch)
+        desc = self._drainage_desc(prm, rainMap)
+        self._call("nz_drainage_stripe_round", h.data_ptr(), a.data_ptr(), work.data_ptr(), C.byref(st), C.byref(desc), int(first),
+                   proceed.data_ptr() if proceed is not None else None, changed.data_ptr())
+
+    def drainage_finalise(self, a, plan, prm, converged, rainMap=None, pitch=0):
+        """nz_drainage_stripe_finalise on the owned rows, by the int32 device word `converged`."""
+        st = plan.stripe(pitch)
+        desc = self._drainage_desc(prm, rainMap)
+        self._call("nz_drainage_stripe_finalise", a.data_ptr(), C.byref(st), C.byref(desc), converged.data_ptr())
 
     def upsample_halo_rows(self, filter):
         return self.lib.nz_upsample_stripe_halo_rows(int(filter))
