@@ -681,6 +681,16 @@ int32_t nz_debug_chain_delay(int32_t item, int32_t sleeps);
 /* Test hook: polls (~2 us each) after which a tile of a chained launch gives up waiting for a producer; <= 0 restores the
  * default (2^21: seconds).  With a small limit and a long nz_debug_chain_delay the time-out path can be exercised. */
 int32_t nz_debug_chain_poll_limit(int32_t polls);
+/* Test hook: the kernel-filter stage on a grid that is a window of its two planes: `st` names it as a stripe whose owned
+ * rows are the whole grid (own0 + grow0 == 0, own1 + grow0 == grows): columns [0, cols) of buffer rows [own0, own1), rows
+ * `pitch` floats apart.  Cells of the planes outside the window are neither read nor written.  Runs the launches
+ * nz_kernel_filter_stage_rw runs on a square tile (chained under the same rules); *swapped = 1: the result is in `other`. */
+int32_t nz_debug_kernel_filter_window(nz_ctx *ctx, float *plane, float *other, const nz_stripe *st, int32_t filter,
+                                      int32_t iterations, int32_t *swapped, nz_handle dep, nz_handle *out);
+/* Context statistic: tile plans of chained filter launches this context has built and uploaded so far.  A context keeps the
+ * plans of its last four geometries (columns, row window, kernel size, launch depths), so a pipeline that calls a stage
+ * with the same geometry for every tile uploads once.  -1: ctx is NULL. */
+int32_t nz_ctx_chain_plan_uploads(nz_ctx *ctx);
 
 /* ---- upsample and downsample: coarse-to-fine terrain (new-framework feature) ------------------------------------------
  * The two changes of resolution the stage list lacks: erode a reduced copy of a tile, carry the change back up and add it

@@ -163,6 +163,8 @@ SIGNATURES = {
     "nz_smooth_blur_stage": (_i, [ctx_p, dev_ptr, dev_ptr, _i, _i, _i] + _tail),
     "nz_erosion_stage": (_i, [ctx_p, dev_ptr, dev_ptr, _i, _i] + _tail),
     "nz_debug_chain_delay": (_i, [_i, _i]),
+    "nz_ctx_chain_plan_uploads": (_i, [ctx_p]),
+    "nz_debug_kernel_filter_window": (_i, [ctx_p, dev_ptr, dev_ptr, stripe_p, _i, _i, C.POINTER(_i)] + _tail),
     "nz_ctx_set_pile_safe": (_i, [ctx_p, _i]),
     "nz_ctx_pile_retries": (_i, [ctx_p]),
     "nz_debug_pile_poll_limit": (_i, [_i]),

@@ -19,6 +19,7 @@
 #include <cstdlib>
 
 #include "nz_internal.hpp"
+#include "nz_chain_plan.hpp"
 
 namespace {
 
@@ -172,6 +173,7 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
     const int gx0 = lx0 + cg * 4, gzb = lz0 + rb * RBT;
     const bool inside = lx0 >= 0 && lx0 + TW <= g.cols && lz0 >= g.zc0 && lz0 + TH - 1 <= g.zc1;
     const bool fast = inside && aligned;
+    const bool edge16 = !inside && aligned && (g.cols & 3) == 0;
     NZ_PROBE_T(0);
     NZ_PROBE(14, (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)));   // HW_ID
     NZ_PROBE(15, (unsigned long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)));  // XCC_ID
@@ -185,6 +187,24 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
             v[r][0] = t.x; v[r][1] = t.y; v[r][2] = t.z; v[r][3] = t.w;
         }
         asm volatile("; 16-byte loads issued" ::: "memory");  // after the loads: they cannot be sunk into a common tail
+    } else if (edge16) {
+        // An edge tile of an aligned plane whose rows are whole groups of four columns: one 16-byte load per row, the row
+        // clamped into [zc0, zc1] as below, the column group clamped into the grid.  gx0 is a multiple of four (so are OW and
+        // HX), so a group lies wholly inside the grid or wholly outside it, and a group outside it now holds the grid's first
+        // / last group where the 4-byte form holds the border cell four times.  No cell inside the grid ever reads those
+        // values: the X pass reaches O <= 4 cells, one lane, to either side; the lane at gx0 == 0 replaces all it takes from
+        // its left neighbour (`if (gx0 == 0) ... w[o] = w[O]`), the lane of the last group (icx == O + 3) all it takes from
+        // its right one (`w[i] = (i > icx) ? wc : w[i]`), and the Z pass stays within a lane's columns.  The lanes outside
+        // the grid compute on and are never stored.
+        asm volatile("; clamped 16-byte loads of an edge tile" ::: "memory");
+        const int gxc = clampi(gx0, 0, g.cols - 4);
+#pragma unroll
+        for (int r = 0; r < RBT; r++) {
+            const size_t off = (size_t)clampi(gzb + r, g.zc0, g.zc1) * g.pitch + gxc;
+            float4 t = SC1 ? load16_sc1(src, off) : *reinterpret_cast<const float4 *>(src + off);
+            v[r][0] = t.x; v[r][1] = t.y; v[r][2] = t.z; v[r][3] = t.w;
+        }
+        asm volatile("; 16-byte edge loads issued" ::: "memory");
     } else {
         asm volatile("; clamped 4-byte loads of an edge tile" ::: "memory");
 #pragma unroll
@@ -197,6 +217,8 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
             }
         }
     }
+    // (chained grid: the loads are issued, the arithmetic runs at priority 0 -- see conv_chain_kernel)
+    if constexpr (SC1) __builtin_amdgcn_s_setprio(0);
 #ifdef NZ_CONV_PROBE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     NZ_PROBE_T(9);  // wave 0's tile rows have landed (the wait exists in this build only)
@@ -309,11 +331,23 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
     }
 
     // ---- store the interior
+    if constexpr (SC1) __builtin_amdgcn_s_setprio(3);
     if (fast) {  // whole tile inside the grid, 16-byte aligned rows: one 16-byte store per row
 #pragma unroll
         for (int r = 0; r < RBT; r++) {
             int lr = rb * RBT + r, gz = gzb + r;
             bool in = lr >= H && lr < H + OH && cg * 4 >= HX && cg * 4 < HX + OW && gz < g.or1;
+            if (in) {
+                if (SC1) store16_sc1(dst, (size_t)gz * g.pitch + gx0, make_float4(v[r][0], v[r][1], v[r][2], v[r][3]));
+                else *reinterpret_cast<float4 *>(dst + (size_t)gz * g.pitch + gx0) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
+            }
+        }
+    } else if (edge16) {  // whole groups again: a group that starts inside the grid ends inside it
+        asm volatile("; guarded 16-byte stores of an edge tile" ::: "memory");
+#pragma unroll
+        for (int r = 0; r < RBT; r++) {
+            int lr = rb * RBT + r, gz = gzb + r;
+            bool in = lr >= H && lr < H + OH && cg * 4 >= HX && cg * 4 < HX + OW && gz < g.or1 && gx0 < g.cols;
             if (in) {
                 if (SC1) store16_sc1(dst, (size_t)gz * g.pitch + gx0, make_float4(v[r][0], v[r][1], v[r][2], v[r][3]));
                 else *reinterpret_cast<float4 *>(dst + (size_t)gz * g.pitch + gx0) = make_float4(v[r][0], v[r][1], v[r][2], v[r][3]);
@@ -375,10 +409,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(K
 // (A persistent form -- resident workgroups that claim item after item and let a tile's stores drain behind the next
 // tile's loads -- was built and measured: 0.555 ms for Gauss5 x17 against 0.197 ms, the loop-carried state costs the
 // 80-register budget 39 spills.  One item per workgroup it stays.)
-constexpr int NZ_CHAIN_MAXL = 8;
+typedef int nz_v8i __attribute__((ext_vector_type(8)));
+static_assert(sizeof(nz_v8i) == sizeof(nz_chain_item) && offsetof(nz_chain_item, stride) == 28, "a record is loaded as eight dwords");
 struct nz_chain {
-    int L, total;
-    int T[NZ_CHAIN_MAXL], first[NZ_CHAIN_MAXL + 1], tiles_x[NZ_CHAIN_MAXL];
+    const nz_chain_item *items;  // the tile plan (nz_chain_plan.hpp): one record per workgroup, built and cached by the context
     unsigned epoch;
     int *flags;       // one per work item, indexed first[l] + tile
     float *plane[2];  // launch l reads plane[l & 1] and writes plane[(l + 1) & 1]
@@ -393,8 +427,6 @@ struct nz_chain {
     unsigned *err_epoch;  // device memory: the lowest epoch of a launch that gave up (which work the failure belongs to)
 };
 
-__host__ __device__ __forceinline__ int chain_class_count(int n, int c) { return n > c ? (n - c + 7) >> 3 : 0; }  // #{vb < n : vb % 8 == c}
-
 template <int KS, bool UNIT, int NT, bool FAST, int RBT>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(KS, NT, RBT)))) void conv_chain_kernel(nz_geom g, nz_kernel_taps taps,
                                                                                                                        nz_chain ch, int aligned) {
@@ -402,51 +434,34 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(K
     constexpr int TH = NT / 32 * RBT;
     constexpr int NBUF = conv_nbuf(O);
     __shared__ float4 s_edge[NBUF][TH / RBT][2][O][TW / 4];
+    // The phases that hand a tile over -- record, poll and the issue of the loads here, the stores, their drain and the flag
+    // at the end -- are a few dozen instructions that each gate a memory round trip of microseconds, on a SIMD whose other
+    // waves are deep in arithmetic: they run at priority 3, the arithmetic between them (conv_tile lowers and raises it) at 0.
+    // The poll sleeps between its loads, and a sleeping wave takes no issue slot from a producer whatever its priority.
     NZ_PB_INIT;
     NZ_PROBE_T(18);  // the workgroup's first instruction (after the kernel arguments' scalar loads)
-    int l = 0, tile = 0;
+    // Work item = position in the grid: the record of blockIdx.x says which tile that is and whom it waits for (the class rule,
+    // nz_chain_plan.hpp).  One 32-byte scalar load: the prologue holds no loop, no division and no dependent argument load.
+    // (Rounds 2 .. 4 drew the position within a class from an atomic ticket, which made the order within a class the order in
+    // which workgroups actually start -- and put a returning atomic, a write to LDS and a barrier in front of every tile: ~2 us
+    // of a tile's ~22, Gauss5 x17 0.203 -> 0.189 ms without it.  The dispatcher starts a grid's workgroups in index order, so
+    // within a class a lower position has started whenever a higher one runs; the hand-off already rested on that order ACROSS
+    // classes, and the wait is bounded either way.)
+    const nz_v8i rec = *reinterpret_cast<const nz_v8i *>(ch.items + blockIdx.x);  // (as a vector: ONE s_load_dwordx8)
+    // (raised behind the record's load: in front of it the compiler takes s_setprio for a possible store to the plan and
+    // loads the record through the vector memory path)
+    __builtin_amdgcn_s_setprio(3);
+    const nz_chain_item it = {rec[0], rec[1], rec[2], rec[3], rec[4], rec[5], rec[6], rec[7]};
+    const int l = it.tl >> 16, T = it.tl & 0xffff;
+    NZ_PROBE_T(7);  // the record is back
+    NZ_PROBE(13, ((unsigned long long)l << 32) | (unsigned)(it.item));
+    // Awaited (ny > 0: every launch but the first): the launch-(l-1) tiles whose interior meets this tile's input window
+    // (their stores are read here) or lies within THEIR halo of this tile's interior (they read the cells this tile
+    // overwrites: the ping-pong plane is shared) -- a rectangle of nx x ny <= 3 x 3 flags from dep0 on, one lane each.
     {
-        // Work item = position in the grid: vb = blockIdx.x, class = vb & 7 (the XCD that receives the workgroup), k = vb >> 3.
-        // (Rounds 2 .. 4 drew k from an atomic ticket per class, which made the order within a class the order in which
-        // workgroups actually start -- and put a returning atomic, a write to LDS and a barrier in front of every tile: ~2 us of
-        // a tile's ~22, Gauss5 x17 0.203 -> 0.189 ms without it.  The dispatcher starts a grid's workgroups in index order, so
-        // within a class a lower k has started whenever a higher one runs; the hand-off already rested on that order ACROSS
-        // classes, and the wait is bounded either way.)
-        const int vb = blockIdx.x;
-        const int cls = vb & 7;
-        while (l + 1 < ch.L && vb >= ch.first[l + 1]) l++;
-        // the class's share of launch l is a contiguous run of tiles: classes before it, then its own earlier items
-        int start = 0;
-        for (int c = 0; c < cls; c++) start += chain_class_count(ch.first[l + 1], c) - chain_class_count(ch.first[l], c);
-        // Odd classes walk their run backwards.  A run's first row of tiles reads the last row of the run before it:
-        // if every class walked forwards, each would start launch l + 1 on the tiles whose producers its neighbour
-        // finishes launch l with -- a row of workgroups spinning at every launch boundary.  Walking towards each
-        // other, neighbouring classes finish a launch on the rows they share and start the next one at the far ends.
-        const int mine = chain_class_count(ch.first[l + 1], cls) - chain_class_count(ch.first[l], cls);
-        const int j = chain_class_count(vb, cls) - chain_class_count(ch.first[l], cls);
-        tile = start + ((cls & 1) ? mine - 1 - j : j);
-    }
-    NZ_PROBE_T(7);  // the ticket is back
-    NZ_PROBE(13, ((unsigned long long)l << 32) | (unsigned)tile);
-    const int T = ch.T[l], H = T * O, HX = conv_hx(H);
-    const int OW = TW - 2 * HX, OH = TH - 2 * H;
-    const int by = tile / ch.tiles_x[l], bx = tile - by * ch.tiles_x[l];
-    const int ox0 = bx * OW, oz0 = g.or0 + by * OH;
-    if (l > 0) {
-        const int Tp = ch.T[l - 1], Hp = Tp * O, HXp = conv_hx(Hp);
-        const int OWp = TW - 2 * HXp, OHp = TH - 2 * Hp;
-        // Awaited: the launch-(l-1) tiles whose interior meets this tile's input window (their stores are read here) or
-        // lies within THEIR halo of this tile's interior (they read the cells this tile overwrites: the ping-pong plane
-        // is shared).  The second set is inside the first while H(l-1) <= H(l), which the host guarantees; the window is
-        // widened to the larger halo all the same, so the protocol does not rest on that order.
-        const int Hw = max(H, Hp), HXw = max(HX, HXp);
-        const int ix0 = max(ox0 - HXw, 0), ix1 = min(ox0 + OW + HXw - 1, g.cols - 1);
-        const int iz0 = max(oz0 - Hw, g.or0), iz1 = min(oz0 + OH + Hw - 1, g.or1 - 1);
-        const int px0 = ix0 / OWp, px1 = ix1 / OWp, py0 = (iz0 - g.or0) / OHp, py1 = (iz1 - g.or0) / OHp;
-        const int nx = px1 - px0 + 1, nd = nx * (py1 - py0 + 1);
-        if ((int)threadIdx.x < nd) {
-            const int dep = (py0 + (int)threadIdx.x / nx) * ch.tiles_x[l - 1] + px0 + (int)threadIdx.x % nx;
-            const int *f = ch.flags + ch.first[l - 1] + dep;
+        const int tid = threadIdx.x, dr = tid >= 6 ? 2 : tid >= 3 ? 1 : 0, dc = tid - 3 * dr;
+        if (tid < 9 && dr < it.ny && dc < it.nx) {
+            const int *f = ch.flags + it.dep0 + dr * it.stride + dc;
             int spins = 0;
             while ((unsigned)__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != ch.epoch) {
                 __builtin_amdgcn_s_sleep(32);
@@ -458,18 +473,18 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(K
                 }
             }
         }
-        __syncthreads();
+        if (it.ny > 0) __syncthreads();
     }
     NZ_PROBE_T(8);  // the producers' flags are up
-    if (ch.first[l] + tile == ch.delay_item)
+    if (it.item == ch.delay_item)
         for (int i = 0; i < ch.delay_sleeps; i++) __builtin_amdgcn_s_sleep(127);  // 127 x 64 clocks ~ 3.4 us
-    conv_tile<KS, UNIT, NT, true, FAST, RBT>(ch.plane[l & 1], ch.plane[(l + 1) & 1], g, taps, T, aligned, ox0, oz0, &s_edge[0][0][0][0][0] NZ_PB_ARG);
+    conv_tile<KS, UNIT, NT, true, FAST, RBT>(ch.plane[l & 1], ch.plane[(l + 1) & 1], g, taps, T, aligned, it.ox0, it.oz0, &s_edge[0][0][0][0][0] NZ_PB_ARG);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores have left
     NZ_PROBE_T(10);  // wave 0's stores are acknowledged
     __syncthreads();
     NZ_PROBE_T(11);  // everybody's are
     if (threadIdx.x == 0) {
-        __hip_atomic_store(&ch.flags[ch.first[l] + tile], (int)ch.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&ch.flags[it.item], (int)ch.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -880,25 +895,11 @@ int32_t launch_fused(hipStream_t s, const float *src, float *dst, const nz_geom 
 int g_chain_delay_item = -1, g_chain_delay_sleeps = 0;  // nz_debug_chain_delay
 int g_chain_spin_limit = 1 << 21;                         // nz_debug_chain_poll_limit
 
-// the work items of L <= NZ_CHAIN_MAXL chained launches: launch l's tiles are items first[l] .. first[l + 1] - 1
 template <int KS, int NT, int RBT>
-nz_chain conv_chain_plan(const nz_geom &g, const int *Ts, int L) {
+int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k,
+                        const nz_chain_item *items, int total, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
     nz_chain ch{};
-    ch.L = L;
-    for (int l = 0; l < L; l++) {
-        const conv_tiling t = conv_tiles<KS, NT, RBT>(g, Ts[l]);
-        ch.T[l] = Ts[l];
-        ch.tiles_x[l] = t.x;
-        ch.first[l + 1] = ch.first[l] + t.x * t.y;
-    }
-    ch.total = ch.first[L];
-    return ch;
-}
-
-template <int KS, int NT, int RBT>
-int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k, const int *Ts,
-                        int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
-    nz_chain ch = conv_chain_plan<KS, NT, RBT>(g, Ts, L);
+    ch.items = items;
     ch.epoch = epoch;
     ch.flags = flags;
     ch.plane[0] = plane0;
@@ -910,23 +911,18 @@ int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_ge
     ch.err_epoch = err_epoch;
     int aligned = ((reinterpret_cast<uintptr_t>(plane0) | reinterpret_cast<uintptr_t>(plane1) | (uintptr_t)(g.pitch * 4)) & 15) == 0;
     nz_with_unit_fast(k, [&](auto unit, auto fast) {
-        NZ_LAUNCH((conv_chain_kernel<KS, unit, NT, fast, RBT>), dim3((unsigned)ch.total), dim3(NT), 0, s, g, k, ch, aligned);
+        NZ_LAUNCH((conv_chain_kernel<KS, unit, NT, fast, RBT>), dim3((unsigned)total), dim3(NT), 0, s, g, k, ch, aligned);
     });
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
 
 template <int KS>
-int32_t launch_chain(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k, const int *Ts,
-                     int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
+int32_t launch_chain(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k,
+                     const nz_chain_item *items, int total, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
     return with_conv_shape<KS>(conv_shape_of(KS, g), [&](auto nt, auto rbt) {
-        return launch_chain_nt<KS, nt, rbt>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
+        return launch_chain_nt<KS, nt, rbt>(s, plane0, plane1, g, k, items, total, flags, epoch, err_host, err_epoch);
     });
-}
-
-template <int KS>
-int chain_items(const nz_geom &g, const int *Ts, int L) {
-    return with_conv_shape<KS>(conv_shape_of(KS, g), [&](auto nt, auto rbt) { return conv_chain_plan<KS, nt, rbt>(g, Ts, L).total; });
 }
 
 }  // namespace
@@ -936,38 +932,53 @@ bool nz_conv_small_grid(int ksize, const nz_geom &g) { return conv_small_grid(ks
 // ... and so small that a launch is at most a workgroup per CU (the 5-tap kernel then fuses nine applications, nz_stages.cpp)
 bool nz_conv_tiny_grid(int ksize, const nz_geom &g) { return conv_shape_of(ksize, g) == CONV_TINY; }
 
+// what the tile plan of L chained launches on this geometry depends on (nz_chain_plan.hpp): the tile shape is the one
+// nz_launch_conv_chain launches (conv_shape_of)
+bool nz_conv_chain_key(int ksize, const nz_geom &g, const int *Ts, int L, nz_chain_key *key) {
+    if (L < 1 || L > NZ_CHAIN_MAXL || (ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9)) return false;
+    for (int l = 0; l < L; l++)
+        if (Ts[l] < 1 || Ts[l] > nz_conv_max_fused(ksize)) return false;
+    const conv_shape sh = conv_shape_of(ksize, g);
+    auto rows = [](auto nt, auto rbt) { return (int)nt / 32 * (int)rbt; };
+    *key = nz_chain_key{};
+    key->O = (ksize - 1) / 2;
+    key->TH = ksize == 5 ? with_conv_shape<5>(sh, rows) : ksize == 3 ? with_conv_shape<3>(sh, rows) : with_conv_shape<7>(sh, rows);
+    key->TW = TW;
+    key->cols = g.cols;
+    key->or0 = g.or0;
+    key->or1 = g.or1;
+    key->L = L;
+    for (int l = 0; l < L; l++) key->T[l] = Ts[l];
+    return true;
+}
+
 // work items (= flags) the chained form of L launches needs on this geometry: the grid nz_launch_conv_chain launches
 int nz_conv_chain_items(int ksize, const nz_geom &g, const int *Ts, int L) {
-    if (L < 1 || L > NZ_CHAIN_MAXL) return 0;
-    switch (ksize) {
-        case 3: return chain_items<3>(g, Ts, L);
-        case 5: return chain_items<5>(g, Ts, L);
-        case 7: return chain_items<7>(g, Ts, L);
-        case 9: return chain_items<9>(g, Ts, L);
-    }
-    return 0;
+    nz_chain_key key;
+    return nz_conv_chain_key(ksize, g, Ts, L, &key) ? nz_chain_layout_of(key).total : 0;
 }
 
 // L <= 8 fused launches as ONE grid with tile-level dependencies (conv_chain_kernel): launch l reads plane (l & 1) and
 // writes the other one, so the result is in plane0 when L is even.  One grid of the geometry (g.count == 1), planes
-// below 4 GiB.  flags: nz_conv_chain_items() ints, never cleared (they carry an epoch).
+// below 4 GiB.  items: the plan of nz_conv_chain_key(ksize, g, Ts, L) in device memory, `total` records (nz_ctx_chain_plan);
+// flags: `total` ints, never cleared (they carry an epoch).
 int32_t nz_launch_conv_chain(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k,
-                             const int *Ts, int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch) {
-    if (L < 1 || L > NZ_CHAIN_MAXL || g.count != 1 || (size_t)g.rows * g.pitch * 4 >= ((size_t)1 << 32)) {
-        nz_set_error("conv_chain: %d launches / %d grids / plane of %zu bytes unsupported", L, g.count, (size_t)g.rows * g.pitch * 4);
+                             const nz_chain_item *items, int total, int *flags, unsigned epoch, unsigned *err_host,
+                             unsigned *err_epoch) {
+    if (g.count != 1 || (size_t)g.rows * g.pitch * 4 >= ((size_t)1 << 32)) {
+        nz_set_error("conv_chain: %d grids / plane of %zu bytes unsupported", g.count, (size_t)g.rows * g.pitch * 4);
         return NZ_ERR_INVALID;
     }
-    for (int l = 0; l < L; l++)
-        if (Ts[l] < 1 || Ts[l] > nz_conv_max_fused(k.ksize)) {
-            nz_set_error("conv_chain: T=%d unsupported for kernelSize %d", Ts[l], k.ksize);
-            return NZ_ERR_INVALID;
-        }
     if (g.or1 <= g.or0) return NZ_OK;
+    if (!items || total < 1) {
+        nz_set_error("conv_chain: no tile plan");
+        return NZ_ERR_INVALID;
+    }
     switch (k.ksize) {
-        case 3: return launch_chain<3>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
-        case 5: return launch_chain<5>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
-        case 7: return launch_chain<7>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
-        case 9: return launch_chain<9>(s, plane0, plane1, g, k, Ts, L, flags, epoch, err_host, err_epoch);
+        case 3: return launch_chain<3>(s, plane0, plane1, g, k, items, total, flags, epoch, err_host, err_epoch);
+        case 5: return launch_chain<5>(s, plane0, plane1, g, k, items, total, flags, epoch, err_host, err_epoch);
+        case 7: return launch_chain<7>(s, plane0, plane1, g, k, items, total, flags, epoch, err_host, err_epoch);
+        case 9: return launch_chain<9>(s, plane0, plane1, g, k, items, total, flags, epoch, err_host, err_epoch);
     }
     return NZ_ERR_INVALID;
 }

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/noize_hip.h"
+#include "nz_chain_plan.hpp"  // the chained filter grid's tile plan (plain C++)
 #include "nz_planes.hpp"  // nz_set_error, NZ_REQUIRE, nz_check_stripe: the host-only geometry and aliasing helpers
 
 // ---- error plumbing -------------------------------------------------------------------------
@@ -58,6 +59,19 @@ struct nz_ctx {
     // did -- one word per kind, so neither overwrites the other), and their device address
     unsigned *chain_err = nullptr, *chain_err_dev = nullptr;
     unsigned chain_epoch = 0;
+    // ... and their tile plans (nz_chain_plan.hpp): a pipeline calls the stage with the same geometry for every tile, so a
+    // plan is built and uploaded once (nz_ctx_chain_plan).  Four plans, the least recently used one is replaced.  Every slot
+    // owns its pinned staging copy, so a replacement waits for that slot's own last upload (`uploaded`) and nothing else.
+    struct chain_plan_slot {
+        nz_chain_key key{};
+        int total = 0;  // 0: empty
+        nz_chain_item *dev = nullptr, *pinned = nullptr;
+        size_t cap = 0;  // records both buffers hold
+        hipEvent_t uploaded = nullptr;
+        uint64_t used = 0;  // chain_plan_clock at the last hit
+    };
+    chain_plan_slot chain_plans[4];
+    uint64_t chain_plan_clock = 0, chain_plan_uploads = 0;
     bool chain_off = false;  // a chained launch once timed out on this context: separate launches from then on
     // Which work a chained launch's time-out belongs to: a failing tile lowers *chain_err_epoch (device memory, atomicMin) to
     // its launch's epoch before it raises the flag; the host remembers the handle sequence number each of its last chained
@@ -299,8 +313,12 @@ int nz_conv_chain_items(int ksize, const nz_geom &g, const int *Ts, int L);
 int nz_cu_count();  // compute units of the current device (256 on MI355X): a launch of at most this many workgroups is one round
 bool nz_conv_small_grid(int ksize, const nz_geom &g);  // 64-row tiles
 bool nz_conv_tiny_grid(int ksize, const nz_geom &g);
+bool nz_conv_chain_key(int ksize, const nz_geom &g, const int *Ts, int L, nz_chain_key *key);  // false: no chained form
 int32_t nz_launch_conv_chain(hipStream_t s, float *plane0, float *plane1, const nz_geom &g, const nz_kernel_taps &k,
-                             const int *Ts, int L, int *flags, unsigned epoch, unsigned *err_host, unsigned *err_epoch);
+                             const nz_chain_item *items, int total, int *flags, unsigned epoch, unsigned *err_host,
+                             unsigned *err_epoch);
+// the plan of `key` in device memory, uploaded on the context's stream unless the context already holds it
+int32_t nz_ctx_chain_plan(nz_ctx *ctx, const nz_chain_key &key, const nz_chain_item **items, int *total);
 int32_t nz_ctx_chain_state(nz_ctx *ctx, size_t items, int **flags, unsigned *epoch, unsigned **err_host, unsigned **err_epoch);
 int32_t nz_ctx_error_word(nz_ctx *ctx, unsigned **err_host);  // mapped host memory, device address: [0] chained filter, [1] pile solver
 // one whole application of a wide odd kernel (11..25 taps), src -> dst

@@ -244,6 +244,11 @@ extern "C" int32_t nz_ctx_destroy(nz_ctx *ctx) {
     if (ctx->chain_flags) (void)hipFree(ctx->chain_flags);
     if (ctx->chain_err) (void)hipHostFree(ctx->chain_err);
     if (ctx->chain_err_epoch) (void)hipFree(ctx->chain_err_epoch);
+    for (auto &p : ctx->chain_plans) {
+        if (p.dev) (void)hipFree(p.dev);
+        if (p.pinned) (void)hipHostFree(p.pinned);
+        if (p.uploaded) (void)hipEventDestroy(p.uploaded);
+    }
     if (ctx->pool_ctl) (void)hipFree(ctx->pool_ctl);
     if (ctx->pool_hint) (void)hipHostFree(ctx->pool_hint);
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
@@ -468,6 +473,67 @@ int32_t nz_ctx_chain_state(nz_ctx *ctx, size_t items, int **flags, unsigned *epo
     *err_epoch = ctx->chain_err_epoch;
     return NZ_OK;
 }
+
+// The tile plan of a chained launch.  A hit costs a comparison of keys: no allocation, no copy, no synchronisation.  A miss
+// takes the least recently used slot, builds the plan into the slot's pinned copy and uploads it with one hipMemcpyAsync on
+// the context's stream, ahead of the launch that reads it.  The slot's earlier plan may still be read by a launch in flight:
+// the upload is ordered behind it on the stream; only the host's writes to the pinned copy have to wait, for the slot's own
+// last upload.
+int32_t nz_ctx_chain_plan(nz_ctx *ctx, const nz_chain_key &key, const nz_chain_item **items, int *total) {
+    ctx->chain_plan_clock++;
+    nz_ctx::chain_plan_slot *lru = &ctx->chain_plans[0];
+    for (auto &p : ctx->chain_plans) {
+        if (p.total > 0 && nz_chain_key_equal(p.key, key)) {
+            p.used = ctx->chain_plan_clock;
+            *items = p.dev;
+            *total = p.total;
+            return NZ_OK;
+        }
+        if (p.used < lru->used) lru = &p;
+    }
+    const int n = nz_chain_layout_of(key).total;
+    if (n < 1) {
+        nz_set_error("conv_chain: no tile plan for %d launches on %d columns x rows [%d, %d)", key.L, key.cols, key.or0, key.or1);
+        return NZ_ERR_INVALID;
+    }
+    nz_ctx::chain_plan_slot &p = *lru;
+    p.total = 0;
+    if (!p.uploaded) NZ_HIP(hipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming));
+    if ((size_t)n > p.cap) {
+        if (p.dev) {
+            NZ_TRY_(ctx_sync_all(ctx));  // a launch in flight may read the old buffer
+            NZ_HIP(hipFree(p.dev));
+            p.dev = nullptr;
+        }
+        if (p.pinned) {
+            NZ_HIP(hipHostFree(p.pinned));
+            p.pinned = nullptr;
+        }
+        p.cap = 0;
+        const size_t cap = (size_t)n + (size_t)n / 2 + 256;
+        NZ_HIP(hipHostMalloc((void **)&p.pinned, cap * sizeof(nz_chain_item), hipHostMallocDefault));
+        NZ_HIP(hipMalloc((void **)&p.dev, cap * sizeof(nz_chain_item)));
+        p.cap = cap;
+    } else {
+        NZ_HIP(hipEventSynchronize(p.uploaded));
+    }
+    if (!nz_chain_plan_build(key, p.pinned)) {
+        nz_set_error("conv_chain: a tile of these %d launches would wait for more than %d x %d producers", key.L, NZ_CHAIN_MAXDEP,
+                     NZ_CHAIN_MAXDEP);
+        return NZ_ERR_INVALID;
+    }
+    NZ_HIP(hipMemcpyAsync(p.dev, p.pinned, (size_t)n * sizeof(nz_chain_item), hipMemcpyHostToDevice, ctx->stream));
+    NZ_HIP(hipEventRecord(p.uploaded, ctx->stream));
+    ctx->chain_plan_uploads++;
+    p.key = key;
+    p.total = n;
+    p.used = ctx->chain_plan_clock;
+    *items = p.dev;
+    *total = n;
+    return NZ_OK;
+}
+
+extern "C" int32_t nz_ctx_chain_plan_uploads(nz_ctx *ctx) { return ctx ? (int32_t)(ctx->chain_plan_uploads & 0x7fffffff) : -1; }
 
 // A kernel whose bounded wait gave up has raised one of the context's error words (mapped host memory: no device-to-host
 // copy on the host's wait path): reported wherever the host waits for work the failure can have touched.  `waited_seq`: the

@@ -243,11 +243,15 @@ static int32_t conv_iterations(nz_ctx *ctx, float *src, float *tmp, const nz_geo
         // that read that region are all among the awaited ones only while H(l) <= H(l + 1) (write after read)
         int Tc[8];
         for (int i = 0; i < L; i++) Tc[i] = Ts[L - 1 - i];
-        int *flags = nullptr;
+        int *flags = nullptr, total = 0;
         unsigned epoch = 0, *err_host = nullptr, *err_epoch = nullptr;
-        NZ_TRY_(nz_ctx_chain_state(ctx, (size_t)nz_conv_chain_items(t.ksize, g, Tc, L), &flags, &epoch, &err_host, &err_epoch));
+        nz_chain_key key;
+        const nz_chain_item *items = nullptr;
+        NZ_REQUIRE(nz_conv_chain_key(t.ksize, g, Tc, L, &key), "conv_chain: no chained form of this series");
+        NZ_TRY_(nz_ctx_chain_plan(ctx, key, &items, &total));  // (before the epoch moves: a refused plan leaves no mark)
+        NZ_TRY_(nz_ctx_chain_state(ctx, (size_t)total, &flags, &epoch, &err_host, &err_epoch));
         nz_ctx_arm_last_launch(ctx);  // (one launch; no copy follows in either form: an even count or a pair)
-        NZ_TRY_(nz_launch_conv_chain(ctx->stream, src, tmp, g, t, Tc, L, flags, epoch, err_host, err_epoch));
+        NZ_TRY_(nz_launch_conv_chain(ctx->stream, src, tmp, g, t, items, total, flags, epoch, err_host, err_epoch));
         if (swapped) *swapped = (L & 1) != 0;
         return NZ_OK;
     }
@@ -862,6 +866,26 @@ extern "C" int32_t nz_kernel_filter_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, int3
     nz_kernel_taps t;
     NZ_TRY(filter_taps(filter, &t));
     return conv_rw(ctx, tile, t, iterations, out);
+}
+
+// Test hook: the filter stage on a grid that is a WINDOW of its planes -- `st` with the whole grid as owned rows (columns
+// [0, cols) of rows [own0, own1), pitch floats apart; whatever else the planes hold is neither read nor written).  The same
+// series of launches as nz_kernel_filter_stage_rw runs on a square tile, chained where that one chains, so every launch form
+// can be held against the oracle on grids that are not square, not aligned, or pitched.  *swapped: the result is in `other`.
+extern "C" int32_t nz_debug_kernel_filter_window(nz_ctx *ctx, float *plane, float *other, const nz_stripe *st, int32_t filter,
+                                                 int32_t iterations, int32_t *swapped, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(swapped, "swapped is NULL");
+    NZ_REQUIRE(filter != NZ_SOBEL3_2D, "Sobel3_2D keeps a third plane: use nz_kernel_filter_stage");
+    nz_kernel_taps t;
+    NZ_TRY(filter_taps(filter, &t));
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(st->own0 + st->grow0 == 0 && st->own1 + st->grow0 == st->grows, "the owned rows must be the whole grid");
+    bool sw = false;
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(conv_iterations(ctx, plane, other, nz_geom_from_stripe(*st), t, iterations, &sw));
+    *swapped = sw ? 1 : 0;
+    return nz_ctx_finish(ctx, out);
 }
 
 extern "C" int32_t nz_gauss_blur_stage_rw(nz_ctx *ctx, nz_rw_tile *tile, int32_t width, int32_t sigma,

@@ -54,7 +54,7 @@ for l in sorted(set(launch.tolist())):
     start = q[:, 7] if chained else q[:, 0]
     ph = collections.OrderedDict()
     if chained:
-        ph["entry -> ticket back"] = us(q[:, 7] - q[:, 18])
+        ph["entry -> record back"] = us(q[:, 7] - q[:, 18])
         ph["flag wait"] = us(q[:, 8] - q[:, 7])
         ph["load (issue -> landed)"] = us(q[:, 9] - q[:, 8])
     else:
