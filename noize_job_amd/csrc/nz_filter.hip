@@ -17,6 +17,7 @@
 // (KernelOperators.cs:34-40,59-65), product then add (no FMA contraction), then * factor.
 // Clamp-to-edge (TileData.cs:72-77) is applied per pass when a window is assembled.
 #include <cstdlib>
+#include <cstring>
 
 #include "nz_internal.hpp"
 #include "nz_chain_plan.hpp"
@@ -151,7 +152,14 @@ __device__ __forceinline__ float tap_first(float v, float k) {
     return FAST ? __builtin_fmaf(v, k, 0.0f) : SEED ? 0.0f + v * k : v * k;
 }
 
-template <int KS, bool UNIT, int NT, bool SC1, bool FAST, int RBT>
+// SYM (5 taps, strict; the launcher has compared the taps' bits: kx[0] == kx[4], kx[1] == kx[3], the same for kz): in strict
+// mode every product is an instruction of its own, and a mirror-symmetric table forms the same product RN(v * k) twice
+// wherever one value feeds two outputs of a thread.  The SYM form computes each product once -- X pass: 18 per row of four
+// outputs instead of 20, Z pass: 30 per column of eight instead of 40 -- and adds them in the order of the generic form,
+// so every sum is the same sequence of the same rounded values.  With only three X taps, they fit in VGPRs, and the
+// neighbour lanes' values are multiplied straight through DPP (v_mul_f32_dpp: its second operand cannot be an SGPR): the
+// shifted values themselves are never materialised.
+template <int KS, bool UNIT, int NT, bool SC1, bool FAST, int RBT, bool SYM = false>
 __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *__restrict__ dst, const nz_geom &g,
                                           const nz_kernel_taps &taps, int T, int aligned, int ox0, int oz0,
                                           float4 *s_edge_raw NZ_PB_PARAM) {
@@ -160,6 +168,7 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
     constexpr int ZN = RBT + 2 * O;  // Z window
     constexpr int TH = NT / 32 * RBT;  // tile rows: one RBT-row block per 32 threads (shadows the file-level TH)
     static_assert(O <= RBT, "a block's window reaches into the neighbouring blocks only");
+    static_assert(!SYM || (KS == 5 && !FAST), "the shared-product form is the strict 5-tap kernel's");
     // boundary rows of every 8-row block: [parity][block][top|bottom][o][column group].  Double buffered
     // (one barrier per application) for the 3-tap kernel; the others keep one buffer and pay a second barrier
     // instead of giving up a resident workgroup (5 taps: 3 x 32 KB; 7/9 taps: 2 x 48/64 KB).
@@ -227,10 +236,64 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
     const int icx = g.cols - 1 - gx0 + O;
     const int iz0 = g.zc0 - gzb + O, iz1 = g.zc1 - gzb + O;
 
+    // SYM: the three distinct X taps in VGPRs (the empty asm keeps them there: a DPP multiply takes no SGPR)
+    float kx0 = taps.kx[0], kx1 = taps.kx[1], kx2 = taps.kx[2];
+    if constexpr (SYM) asm volatile("" : "+v"(kx0), "+v"(kx1), "+v"(kx2));
+
     for (int t = 0; t < T; t++) {
         // ---- X pass (KernelSampleXOperator: taps k ascending), in place row by row
 #pragma unroll
         for (int r = 0; r < RBT; r++) {
+            if constexpr (SYM) {
+                // window cell i (0 .. 7; 0, 1 from the lane to the left, 6, 7 from the lane to the right) times k0 / k1 / k2 ->
+                // p0[i] (all eight), p1[i] (1 .. 6), p2[i] (2 .. 5); output e = p0[e] + p1[e+1] + p2[e+2] + p1[e+3] + p0[e+4]
+                const float l2 = dpp_prev(v[r][2]), l3 = dpp_prev(v[r][3]), n0 = dpp_next(v[r][0]), n1 = dpp_next(v[r][1]);
+                float p0[WN], p1[WN], p2[WN];
+                p0[0] = l2 * kx0;
+                p0[1] = l3 * kx0; p1[1] = l3 * kx1;
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    p0[2 + e] = v[r][e] * kx0; p1[2 + e] = v[r][e] * kx1; p2[2 + e] = v[r][e] * kx2;
+                }
+                p0[6] = n0 * kx0; p1[6] = n0 * kx1;
+                p0[7] = n1 * kx0;
+                if (!inside) {
+                    // the clamps of the generic form below, applied to the products: a clamped cell's product is the
+                    // product of the cell it is clamped to (the same tap), which this lane has formed
+                    asm volatile("; clamps of an edge tile's products");  // a real branch: never if-converted into the interior path
+                    if (gx0 == 0) {
+                        p0[0] = p0[2]; p0[1] = p0[2]; p1[1] = p1[2];
+                    }
+                    if (icx >= O && icx < WN - 1) {
+                        float c0 = p0[2], c1 = p1[2], c2 = p2[2];
+#pragma unroll
+                        for (int i = 3; i < WN; i++) {
+                            c0 = (i == icx) ? p0[i] : c0;
+                            if (i <= 6) c1 = (i == icx) ? p1[i] : c1;
+                            if (i <= 5) c2 = (i == icx) ? p2[i] : c2;
+                        }
+#pragma unroll
+                        for (int i = 3; i < WN; i++) {
+                            p0[i] = (i > icx) ? c0 : p0[i];
+                            if (i <= 6) p1[i] = (i > icx) ? c1 : p1[i];
+                            if (i <= 5) p2[i] = (i > icx) ? c2 : p2[i];
+                        }
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    float total = p0[e];
+                    total += p1[e + 1];
+                    total += p2[e + 2];
+                    total += p1[e + 3];
+                    total += p0[e + 4];
+                    v[r][e] = UNIT ? total : total * taps.factor;
+                }
+                // the row's sums stay in the row: left to itself the compiler sinks all eight rows' additions behind the
+                // last row's branch and keeps 18 products per row alive until then (116 spilled registers)
+                asm volatile("" : "+v"(v[r][0]), "+v"(v[r][1]), "+v"(v[r][2]), "+v"(v[r][3]));
+                continue;
+            }
             float w[WN];
 #pragma unroll
             for (int o = 0; o < O; o++) {
@@ -308,8 +371,36 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
             }
         }
         // ---- Z pass (KernelSampleZOperator: k descending, Kernel[k_off - k])
+        if constexpr (SYM) {
+            // a column's ZN window rows times kz0 (all), kz1 (1 .. ZN - 2) and kz2 (2 .. ZN - 3), each once, after the clamps;
+            // row r = [+0 seed] + q0[r+4] + q1[r+3] + q2[r+2] + q1[r+1] + q0[r].  Formed row by row as the sums reach them: a
+            // k0 product lives for four rows, a k1 product for two
+            const float kz0 = taps.kz[0], kz1 = taps.kz[1], kz2 = taps.kz[2];
 #pragma unroll
-        for (int r = 0; r < RBT; r++) {
+            for (int e = 0; e < 4; e++) {
+                float q0[ZN], q1[ZN];
+#pragma unroll
+                for (int i = 0; i < 4; i++) q0[i] = z[i][e] * kz0;
+                q1[1] = z[1][e] * kz1;
+                q1[2] = z[2][e] * kz1;
+#pragma unroll
+                for (int r = 0; r < RBT; r++) {
+                    q0[r + 4] = z[r + 4][e] * kz0;
+                    q1[r + 3] = z[r + 3][e] * kz1;
+                    float total = !UNIT ? 0.0f + q0[r + 4] : q0[r + 4];  // tap_first<false, !UNIT>
+                    total += q1[r + 3];
+                    total += z[r + 2][e] * kz2;
+                    total += q1[r + 1];
+                    total += q0[r];
+                    v[r][e] = UNIT ? total : total * taps.factor;
+                }
+                // column by column: the products that wait for their second use (six at a time) are one column's, not four's
+                if constexpr (RBT == 8)
+                    asm volatile("" : "+v"(v[0][e]), "+v"(v[1][e]), "+v"(v[2][e]), "+v"(v[3][e]), "+v"(v[4][e]), "+v"(v[5][e]), "+v"(v[6][e]), "+v"(v[7][e]));
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < (SYM ? 0 : RBT); r++) {
 #pragma unroll
             for (int e = 0; e < 4; e++) {
                 float total = tap_first<FAST, !UNIT>(z[r + 2 * O][e], taps.kz[0]);
@@ -372,7 +463,7 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
     NZ_PROBE_T(12);
 }
 
-template <int KS, bool UNIT, int NT, bool FAST, int RBT>
+template <int KS, bool UNIT, int NT, bool FAST, int RBT, bool SYM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(KS, NT, RBT)))) void conv_reg_kernel(const float *__restrict__ src, float *__restrict__ dst, nz_geom g,
                                                      nz_kernel_taps taps, int T, int aligned) {
     constexpr int O = (KS - 1) / 2;
@@ -385,7 +476,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(K
     int ox0, oz0;
     tile_origin(g, TW - 2 * HX, TH - 2 * H, ox0, oz0);
     NZ_PB_INIT;
-    conv_tile<KS, UNIT, NT, false, FAST, RBT>(src, dst, g, taps, T, aligned, ox0, oz0, &s_edge[0][0][0][0][0] NZ_PB_ARG);
+    conv_tile<KS, UNIT, NT, false, FAST, RBT, SYM>(src, dst, g, taps, T, aligned, ox0, oz0, &s_edge[0][0][0][0][0] NZ_PB_ARG);
 }
 
 // ---- the launches of a stage as ONE grid with tile-level dependencies -------------------------------------------------
@@ -427,7 +518,7 @@ struct nz_chain {
     unsigned *err_epoch;  // device memory: the lowest epoch of a launch that gave up (which work the failure belongs to)
 };
 
-template <int KS, bool UNIT, int NT, bool FAST, int RBT>
+template <int KS, bool UNIT, int NT, bool FAST, int RBT, bool SYM>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(KS, NT, RBT)))) void conv_chain_kernel(nz_geom g, nz_kernel_taps taps,
                                                                                                                        nz_chain ch, int aligned) {
     constexpr int O = (KS - 1) / 2;
@@ -478,7 +569,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(conv_waves(K
     NZ_PROBE_T(8);  // the producers' flags are up
     if (it.item == ch.delay_item)
         for (int i = 0; i < ch.delay_sleeps; i++) __builtin_amdgcn_s_sleep(127);  // 127 x 64 clocks ~ 3.4 us
-    conv_tile<KS, UNIT, NT, true, FAST, RBT>(ch.plane[l & 1], ch.plane[(l + 1) & 1], g, taps, T, aligned, it.ox0, it.oz0, &s_edge[0][0][0][0][0] NZ_PB_ARG);
+    conv_tile<KS, UNIT, NT, true, FAST, RBT, SYM>(ch.plane[l & 1], ch.plane[(l + 1) & 1], g, taps, T, aligned, it.ox0, it.oz0, &s_edge[0][0][0][0][0] NZ_PB_ARG);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every wave: its stores have left
     NZ_PROBE_T(10);  // wave 0's stores are acknowledged
     __syncthreads();
@@ -875,13 +966,30 @@ conv_tiling conv_tiles(const nz_geom &g, int T) {
     return {(g.cols + OW - 1) / OW, (g.or1 - g.or0 + OH - 1) / OH};
 }
 
+// The strict 5-tap kernel's shared-product form (conv_tile<SYM>): both tables mirror-symmetric, compared as bit patterns
+// (-0 is not +0 and a NaN tap equals itself: the form reuses a product only where the generic form would compute the very
+// same one).  NZ_CONV_SYM=0 forces the generic form: the filter enum has no asymmetric 5-tap table that would run it.
+static bool conv_sym(const nz_kernel_taps &k) {
+    static const int env = getenv("NZ_CONV_SYM") ? atoi(getenv("NZ_CONV_SYM")) : 1;
+    if (env == 0 || k.ksize != 5) return false;
+    return memcmp(&k.kx[0], &k.kx[4], 4) == 0 && memcmp(&k.kx[1], &k.kx[3], 4) == 0 && memcmp(&k.kz[0], &k.kz[4], 4) == 0 &&
+           memcmp(&k.kz[1], &k.kz[3], 4) == 0;
+}
+
 template <int KS, int NT, int RBT>
 int32_t launch_fused_nt(hipStream_t s, const float *src, float *dst, const nz_geom &g, const nz_kernel_taps &k, int T) {
     const conv_tiling t = conv_tiles<KS, NT, RBT>(g, T);
     const long long blocks = (long long)t.x * t.y;
     int aligned = ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | (uintptr_t)(g.pitch * 4)) & 15) == 0;
+    const bool sym = conv_sym(k);
     nz_with_unit_fast(k, [&](auto unit, auto fast) {
-        NZ_LAUNCH((conv_reg_kernel<KS, unit, NT, fast, RBT>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, T, aligned);
+        if constexpr (KS == 5 && !fast) {
+            if (sym) {
+                NZ_LAUNCH((conv_reg_kernel<KS, unit, NT, fast, RBT, true>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, T, aligned);
+                return;
+            }
+        }
+        NZ_LAUNCH((conv_reg_kernel<KS, unit, NT, fast, RBT, false>), dim3((unsigned)blocks, g.count), dim3(NT), 0, s, src, dst, g, k, T, aligned);
     });
     NZ_HIP(hipGetLastError());
     return NZ_OK;
@@ -910,8 +1018,15 @@ int32_t launch_chain_nt(hipStream_t s, float *plane0, float *plane1, const nz_ge
     ch.err_host = err_host;
     ch.err_epoch = err_epoch;
     int aligned = ((reinterpret_cast<uintptr_t>(plane0) | reinterpret_cast<uintptr_t>(plane1) | (uintptr_t)(g.pitch * 4)) & 15) == 0;
+    const bool sym = conv_sym(k);
     nz_with_unit_fast(k, [&](auto unit, auto fast) {
-        NZ_LAUNCH((conv_chain_kernel<KS, unit, NT, fast, RBT>), dim3((unsigned)total), dim3(NT), 0, s, g, k, ch, aligned);
+        if constexpr (KS == 5 && !fast) {
+            if (sym) {
+                NZ_LAUNCH((conv_chain_kernel<KS, unit, NT, fast, RBT, true>), dim3((unsigned)total), dim3(NT), 0, s, g, k, ch, aligned);
+                return;
+            }
+        }
+        NZ_LAUNCH((conv_chain_kernel<KS, unit, NT, fast, RBT, false>), dim3((unsigned)total), dim3(NT), 0, s, g, k, ch, aligned);
     });
     NZ_HIP(hipGetLastError());
     return NZ_OK;

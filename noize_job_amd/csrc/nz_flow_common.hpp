@@ -13,6 +13,21 @@ struct flux4 {
     float w, e, s, n;
 };
 
+// Additions of +0 the flow map does not need (strict mode: the instruction stream is the cost).  0 + x is x bit for bit
+// unless x is -0 (0 + -0 = +0; a NaN keeps its payload, and every x below is the result of an arithmetic instruction,
+// so it is quiet already).  No value these sums meet is ever -0, by induction over the iterations:
+//   * water is 1e-4 (fillStage), +0 (a row outside a stage's window) or fmaxf(0, water + delta * dt): a sum is -0 only
+//     when BOTH operands are, so the new water is -0 only if the old one was -- whichever zero fmaxf(+0, -0) returns,
+//     the argument does not lean on how v_max_f32 orders zeros;
+//   * a total height is water + height: not -0 since the water is not, even over a plane of -0;
+//   * a height difference d = total - neighbour is -0 only for total == -0 (x - y is -0 only as -0 - +0): never;
+//   * a flux is fmaxf(0, old + d), one of its operands (+0 for a NaN): -0 only if old and d both were; scaled by
+//     K = fmaxf(0, fminf(1, water / (sum * dt))) with water >= +0 or NaN and sum >= +0, K is +0 .. 1 and the product
+//     of two non-negative numbers is not -0.
+// So `flowIN = 0; flowIN += fE` is fE, and the first iteration's `old + d` with old == +0 is d.
+template <bool FIRST>
+__device__ __forceinline__ float flux_sum(float old, float d) { return FIRST ? d : old + d; }
+
 // ComputeFlowStep.CalculateCell, FlowMapComponents.cs:20-65
 __device__ __forceinline__ flux4 compute_flow(float totalHt, float water_0, float tW, float tE, float tS, float tN,
                                               flux4 old) {
@@ -36,14 +51,16 @@ __device__ __forceinline__ flux4 compute_flow(float totalHt, float water_0, floa
 // The same without the branch, bit for bit.  Every f is fmaxf(0, .), so f is in [0, +inf] (never NaN: fmaxf returns its
 // other operand) and sum_ is in [0, +inf]: `sum_ > 0` fails only when all four are +0.  Then water_0 / 0 is +-inf or NaN,
 // which the clamp turns into a K of 0 or 1 (fminf(1, NaN) = 1), and +0 * K = +0 -- the zeros the else branch stores.
+// FIRST: the map's first iteration, old == +0 (flux_sum)
+template <bool FIRST = false>
 __device__ __forceinline__ flux4 compute_flow_nb(float totalHt, float water_0, float tW, float tE, float tS, float tN,
                                                  flux4 old) {
     float dW = totalHt - tW, dE = totalHt - tE, dS = totalHt - tS, dN = totalHt - tN;
     flux4 f;
-    f.w = fmaxf(0.0f, old.w + dW);
-    f.e = fmaxf(0.0f, old.e + dE);
-    f.s = fmaxf(0.0f, old.s + dS);
-    f.n = fmaxf(0.0f, old.n + dN);
+    f.w = fmaxf(0.0f, flux_sum<FIRST>(old.w, dW));
+    f.e = fmaxf(0.0f, flux_sum<FIRST>(old.e, dE));
+    f.s = fmaxf(0.0f, flux_sum<FIRST>(old.s, dS));
+    f.n = fmaxf(0.0f, flux_sum<FIRST>(old.n, dN));
     float sum_ = (f.w + f.e) + (f.s + f.n);
     float K = water_0 / (sum_ * TIMESTEP);
     K = fmaxf(0.0f, fminf(1.0f, K));
@@ -74,10 +91,10 @@ __device__ __forceinline__ float update_water(float water, flux4 own, float fE_w
 // therefore still agree bit for bit within the mode.  The map amplifies one ulp (total = water + height rounds the water to
 // the height's ulp), so these forms leave the strict result's 1e-5 band in ~1e-4 of the cells: a mode of its own
 // (include/noize_hip.h), NZ_FLOAT_FAST runs the strict forms.
-template <bool FAST>
+template <bool FAST, bool FIRST = false>
 __device__ __forceinline__ flux4 compute_flow_m(float totalHt, float water_0, float tW, float tE, float tS, float tN, flux4 old,
                                                 bool branch_free) {
-    if (!FAST) return branch_free ? compute_flow_nb(totalHt, water_0, tW, tE, tS, tN, old) : compute_flow(totalHt, water_0, tW, tE, tS, tN, old);
+    if (!FAST) return branch_free ? compute_flow_nb<FIRST>(totalHt, water_0, tW, tE, tS, tN, old) : compute_flow(totalHt, water_0, tW, tE, tS, tN, old);
     float dW = totalHt - tW, dE = totalHt - tE, dS = totalHt - tS, dN = totalHt - tN;
     flux4 f;
     f.w = fmaxf(0.0f, old.w + dW);
@@ -95,9 +112,9 @@ __device__ __forceinline__ flux4 compute_flow_m(float totalHt, float water_0, fl
 template <bool FAST>
 __device__ __forceinline__ float update_water_m(float water, flux4 own, float fE_west, float fW_east, float fN_south,
                                                 float fS_north) {
-    if (!FAST) return update_water(water, own, fE_west, fW_east, fN_south, fS_north);
     float flowOUT = own.w + own.e + own.s + own.n;
-    float flowIN = ((fE_west + fW_east) + fN_south) + fS_north;  // (0 + a is a)
+    float flowIN = ((fE_west + fW_east) + fN_south) + fS_north;  // without update_water's `0 +`: no flux is -0 (flux_sum)
+    if (!FAST) return fmaxf(0.0f, water + ((flowIN - flowOUT) * TIMESTEP));
     return fmaxf(0.0f, __builtin_fmaf(flowIN - flowOUT, TIMESTEP, water));
 }
 

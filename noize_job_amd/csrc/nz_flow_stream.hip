@@ -134,7 +134,8 @@ __device__ __forceinline__ void fs_step(fs_state<NST, NC> &st, const int t, cons
                 if (i == 0) old = flux4{0.0f, 0.0f, 0.0f, 0.0f};
                 else old = flux4{st.FA[i > 0 ? i - 1 : 0][e][0], st.FA[i > 0 ? i - 1 : 0][e][1],
                                  st.FA[i > 0 ? i - 1 : 0][e][2], st.FA[i > 0 ? i - 1 : 0][e][3]};
-                const flux4 f = compute_flow_m<FAST>(self, st.W0[i][e], tW, tE, tS, tN, old, true);
+                const flux4 f = i == 0 ? compute_flow_m<FAST, !FAST>(self, st.W0[i][e], tW, tE, tS, tN, old, true)
+                                       : compute_flow_m<FAST>(self, st.W0[i][e], tW, tE, tS, tN, old, true);
                 FC[e][0] = f.w; FC[e][1] = f.e; FC[e][2] = f.s; FC[e][3] = f.n;
             }
         } else {

@@ -540,7 +540,8 @@ template <int VEC, bool FAST, int SHAPE>
 __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restrict__ dst, int rows, int cols, int pitch,
                                                                  int blocks_per_row, nz_fractal_kparams p,
                                                                  const int *__restrict__ t1g,
-                                                                 const float4 *__restrict__ t2g, nz_ridge_params rp) {
+                                                                 const float4 *__restrict__ t2g, nz_ridge_params rp,
+                                                                 nz_octave_table oct) {
     __shared__ int s_t1[NZ_T1_N];
     __shared__ float4 s_t2[FAST ? 1 : NZ_T2_N];
     __shared__ float2 s_t2f[FAST ? NZ_T2_N : 1];  // tolerance mode: {a0, h} * norm, 8-byte entries (T1 staged as 8 * permute)
@@ -597,6 +598,21 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
             }
 #pragma unroll
             for (int c = 0; c < VEC; c++) t[c] += bias;
+        } else if (p.fmax * reach < NZ_TAB_LIMIT && oct.n > 0) {
+            // ... and the host has run the wave-uniform recurrence (nz_octave_table: the same fp32 operations, so the same
+            // bits): f and a are scalar loads from the kernel arguments, issued one octave ahead of their use
+            float fn = oct.f[0], an = oct.a[0];
+            for (int i = 0; i < oct.n; i++) {
+                f = fn; a = an;
+                const int nx = min(i + 1, NZ_OCT_TAB - 1);
+                fn = oct.f[nx]; an = oct.a[nx];
+                float zV = f * zi;
+#pragma unroll
+                for (int c = 0; c < VEC; c++) {
+                    float xV = f * xi[c];
+                    octave_add<SHAPE>(t[c], w[c], a, rectify_half(snoise2_tab(xV, zV, s_t1, s_t2)), rp);
+                }
+            }
         } else if (p.fmax * reach < NZ_TAB_LIMIT) {  // every octave of this row stays inside the tables' range
             for (int i = 0; i < p.octaves; i++) {
                 float zV = f * zi;
@@ -1059,10 +1075,10 @@ int32_t launch_shaped(hipStream_t s, int noiseType, float *dst, int rows, int co
         const float4 *t2 = reinterpret_cast<const float4 *>(t1 + NZ_T1_N);
         if (nz_tls_float_mode >= NZ_FLOAT_FAST)
             NZ_LAUNCH((fractal_simplex_tab_kernel<VEC, true, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows, cols,
-                      pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
+                      pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge, p.oct);
         else
             NZ_LAUNCH((fractal_simplex_tab_kernel<VEC, false, SHAPE>), dim3((unsigned)blocks, count), dim3(256), 0, s, dst, rows, cols,
-                      pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge);
+                      pitch, bpr, static_cast<const nz_fractal_kparams &>(p), t1, t2, p.ridge, p.oct);
         NZ_HIP(hipGetLastError());
         return NZ_OK;
     }

@@ -154,8 +154,19 @@ struct nz_fractal_kparams {
 struct nz_ridge_params {
     float offset = 1.0f, gain = 2.0f;
 };
+// The octaves' frequencies and amplitudes, f_0 = 1, f_{i+1} = f_i * (stepdown - detune_{i+1}), a_0 = amp, a_{i+1} = a_i * G:
+// wave-uniform, and gfx9 has no scalar float ALU, so a kernel that runs the recurrence pays three VALU instructions per
+// wave and octave for values the host knows.  fractal_impl fills them with the kernels' own fp32 operation sequence
+// (nz_stages.cpp is compiled without contraction) for up to NZ_OCT_TAB octaves; `n` is 0 beyond that, and the kernel keeps
+// its recurrence.  A trailing kernel argument of the simplex table kernel, read with scalar loads.
+constexpr int NZ_OCT_TAB = 16;
+struct nz_octave_table {
+    float f[NZ_OCT_TAB], a[NZ_OCT_TAB];
+    int n = 0;  // entries filled: the octave count, or 0 (no table)
+};
 struct nz_fractal_params : nz_fractal_kparams {
     nz_ridge_params ridge;  // NZ_SHAPE_RIDGED only
+    nz_octave_table oct;
 };
 // the domain warp's constants (nz_fractal_warped*): a trailing kernel argument of the warped kernels.  norm / fmax are the
 // displacement loop's CalcFractalNormValue and max |frequency| (as fractal_impl computes them for the main loop); the

@@ -34,6 +34,22 @@ static float fractal_fmax(float stepdown, float detune, int octaves) {
     return fmax;
 }
 
+// the same recurrence, amplitudes included, octave by octave: what the simplex table kernel would compute itself
+// (fractal_simplex_tab_kernel: `detune += rate; f *= stepdown - detune; a *= G`, every step one fp32 rounding)
+static void fractal_octave_table(float amp, float G, float stepdown, float detune, int octaves, nz_octave_table *t) {
+    *t = nz_octave_table{};
+    if (octaves < 1 || octaves > NZ_OCT_TAB) return;
+    float f = 1.0f, a = amp, det = 0.0f;
+    for (int i = 0; i < NZ_OCT_TAB; i++) {  // (the entries behind the last octave are never used: a kernel reads one ahead)
+        t->f[i] = f;
+        t->a[i] = a;
+        det += detune;
+        f *= (stepdown - det);
+        a *= G;
+    }
+    t->n = octaves;
+}
+
 static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, float *dst, int rows, int cols, int pitch,
                             float hurst,
                             float amp, float stepdown, float detune, int octaves, int xpos, int zpos_first_row,
@@ -58,6 +74,7 @@ static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, floa
     p.ridge.offset = ridgeOffset;
     p.ridge.gain = ridgeGain;
     p.fmax = fractal_fmax(stepdown, detune, octaves);
+    fractal_octave_table(amp, p.G, stepdown, detune, octaves, &p.oct);
     // domain warp: the displacement loop's norm and frequency bound, the same two values for warp->octaves
     nz_warp_params wp;
     if (warp) {

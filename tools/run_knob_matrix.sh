@@ -3,9 +3,9 @@
 #   tools/run_knob_matrix.sh [first [last]]   -- knobs first..last of the list (0-based), default all
 # Stops at the first knob whose pytest run exits with anything but 0 or 1 (a time limit or a crash).
 cd "$(dirname "$0")/.."
-# Eleven knobs are left: NZ_RCCL_LIB names a library; the other ten FORCE a launch form at sizes where it is not
+# Twelve knobs are left: NZ_RCCL_LIB names a library; the other eleven FORCE a launch form at sizes where it is not
 # the default, so that the small-grid parity tests cover every form that is the default somewhere.
-KNOBS=(NZ_CONV_CHAIN=0 NZ_CONV_CHAIN=2 NZ_CONV_STREAM=0 NZ_CONV_STREAM=2 NZ_CONV_SMALL=0 NZ_CONV_SMALL=2 "NZ_CONV_SMALL=2 NZ_CONV_CHAIN=2"
+KNOBS=(NZ_CONV_SYM=0 "NZ_CONV_SYM=0 NZ_CONV_SMALL=0" NZ_CONV_CHAIN=0 NZ_CONV_CHAIN=2 NZ_CONV_STREAM=0 NZ_CONV_STREAM=2 NZ_CONV_SMALL=0 NZ_CONV_SMALL=2 "NZ_CONV_SMALL=2 NZ_CONV_CHAIN=2"
        NZ_FLOW_STREAM=0 NZ_FLOW_STREAM=2 NZ_FLOW_TINY=0 NZ_FLOW_TINY=2 NZ_FLOW_TINY=3 NZ_FLOW_NMAX=1 NZ_FLOW_NMAX=3
        NZ_EROSION_EMAX=1 NZ_EROSION_EMAX=4 NZ_POOL_RUNS=0 NZ_POOL_SPARSE=0 NZ_POOL_SPARSE=2 NZ_PILE_TICKET=0)
 first=${1:-0}; last=${2:-$((${#KNOBS[@]} - 1))}
