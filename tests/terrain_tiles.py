@@ -1,4 +1,5 @@
-"""Adversarial height tiles for the terrain stages (hydraulic erosion plain and _ex, fluvial erosion, depression filling):
+"""Adversarial height tiles for the terrain stages (hydraulic erosion plain and _ex, fluvial erosion, depression filling,
+drainage area) and their stripe entries:
 plain numpy, no GPU and no oracle, so this module and tests/test_terrain_tiles.py import without a build.  Every generator
 takes (res, rng) and returns a contiguous float32 res x res plane indexed [z, x].  tests/test_terrain_tiles.py checks with
 the numpy models alone that each one does what its name says; tests/test_gpu_sweep_terrain.py runs the kernels on them.
@@ -19,7 +20,9 @@ the numpy models alone that each one does what its name says; tests/test_gpu_swe
                            mouth: the way out of the far end is back along every corridor, so the fill's front comes
                            through the same 64 x 16 tiles again and again
     plain    relief, noisy, uniform, wide: a smooth relief in [0, 1], the same with N(0, 0.01) on it, uniform random cells,
-                           and both signs over a random power of ten (as tests/test_gpu_sweep.py)"""
+                           and both signs over a random power of ten (as tests/test_gpu_sweep.py)
+
+cut_rows, cut_ties and cut_subnormal say what a tile holds across the cuts of a split into row stripes."""
 import functools
 
 import numpy as np
@@ -149,3 +152,31 @@ def sea_at(h, q=0.3):
     """The cell value at the q quantile of the tile: a value the tile holds, so `h <= seaLevel` decides whole plateaus."""
     flat = np.sort(np.asarray(h, f32).reshape(-1))
     return float(flat[int(q * (flat.size - 1))])
+
+
+def cut_rows(rows, world):
+    """The first owned row of the ranks 1 .. world - 1 of noize_job_amd.sharded.StripePlan: the cuts of `rows` rows."""
+    base, rem = divmod(rows, world)
+    return [k * base + min(k, rem) for k in range(1, world)]
+
+
+def _across(h, world, test):
+    out = []
+    for r in cut_rows(h.shape[0], world):
+        a, b = h[r - 1], h[r]
+        out.append(int(test(a, b).sum() + test(a[1:], b[:-1]).sum() + test(a[:-1], b[1:]).sum()))
+    return out
+
+
+def cut_ties(h, world):
+    """Per cut: the pairs of cells either side of it, straight or diagonal, of equal height -- a receiver of a first or
+    last owned row is then chosen among equal drops, some of them in a ghost row."""
+    return _across(np.asarray(h, f32), world, lambda a, b: a == b)
+
+
+def cut_subnormal(h, world):
+    """Per cut: the pairs either side of it, straight or diagonal, whose heights differ by a subnormal amount."""
+    def test(a, b):
+        d = np.abs(a.astype(np.float64) - b.astype(np.float64))
+        return (d > 0) & (d < 2.0 ** -126)
+    return _across(np.asarray(h, f32), world, test)

@@ -13,7 +13,10 @@ that is what a wrong DIAG, or a DIAG on a cardinal, turns over.  The figures (pr
                    cheb_cone 0.97 / 0.98, manh_cone 0.97 / 1.00, cheb_pit 1.00 / 1.00, manh_pit 1.00 / 1.00 equal-drop share
     tiny           0.78 / 0.77 of the non-zero drops are subnormal at 66 / 97
     metres         66: 3 pits, 106 after a fill with epsilon 1e-4, 0 with 1e-2;  97: 10, 2074 and 0
-    serpentine     97 cells, pitch 6: 96 passes with 16 sweeps, 505 with 3, 1506 with 1; one tile wakes up 7 times"""
+    serpentine     97 cells, pitch 6: 96 passes with 16 sweeps, 505 with 3, 1506 with 1; one tile wakes up 7 times
+    cuts           the splits of the stripe sweep (65 rows over 3 and 8 ranks, 130 over 3, and 2 / 8 ranks beside them): every
+                   tie tile and `zeros` have at least 18 pairs of equal heights across every cut, straight or diagonal, and
+                   `tiny` at least 129 pairs a subnormal amount apart"""
 import numpy as np
 import pytest
 
@@ -176,3 +179,38 @@ def test_the_record_leaves_the_tiled_model_alone():
     record = []
     a, b = L.tiled(h, 1e-4, tile=(16, 8), sweeps=4), L.tiled(h, 1e-4, tile=(16, 8), sweeps=4, record=record)
     assert L.same(a[0], b[0]) and a[1] == b[1] == len(record) - 1 and record[0].shape == (5, 3)
+
+
+# the stripe sweep (tests/sweep_stripe_cases.py) takes its tiles to tie across every cut of its splits
+def test_cut_rows_are_the_stripe_plans():
+    from noize_job_amd import sharded as sh
+    for rows, world in ((65, 3), (65, 8), (130, 3), (67, 3), (70, 16), (8, 8)):
+        assert T.cut_rows(rows, world) == [sh.StripePlan(r, world, rows, 4, 0).g0 for r in range(1, world)]
+    h = np.arange(36, dtype=f32).reshape(6, 6)
+    assert T.cut_ties(h, 2) == [0] and T.cut_subnormal(h, 3) == [0, 0]
+    h[3, 2] = h[2, 3]   # a diagonal pair across the cut at row 3
+    h[3, 5] = h[2, 5]   # and a straight one
+    assert T.cut_ties(h, 2) == [2] and T.cut_ties(h, 3) == [0, 0]
+    h[3, 0], h[4, 0] = f32(2e-38), f32(2e-38) + f32(1e-40)  # normal numbers a subnormal amount apart, across the cut at row 4
+    assert T.cut_subnormal(h, 3) == [0, 1] and T.cut_subnormal(h, 2) == [0]
+
+
+@pytest.mark.parametrize("res,world", [(65, 3), (65, 8), (130, 3), (65, 2), (130, 2), (130, 8)])
+@pytest.mark.parametrize("name", list(T.TIES) + ["zeros", "tiny"])
+def test_the_stripe_tiles_tie_across_every_cut(name, res, world):
+    """(65, 3), (65, 8) and (130, 3) are the splits of the stripe sweep; every tile of it has equal heights across every cut,
+    straight or diagonal -- `tiny` instead heights that differ by a subnormal amount."""
+    h = make(name, res)
+    assert len(T.cut_rows(res, world)) == world - 1
+    if name == "tiny":
+        counts = T.cut_subnormal(h, world)
+        print("tiny %d over %d: subnormal differences across the cuts %s" % (res, world, counts))
+        assert max(counts) >= 1
+    else:
+        counts = T.cut_ties(h, world)
+        print("%s %d over %d: equal pairs across the cuts %s" % (name, res, world, counts))
+        assert min(counts) >= 1
+
+
+def test_the_pitched_stripe_tile_ties_across_its_cuts():
+    assert min(T.cut_ties(make("terraces16", 67), 3)) >= 1
