@@ -99,6 +99,11 @@ __device__ unsigned long long *nz_probe_buf = nullptr;  // [workgroup][24]
 // 512-thread workgroups per CU (6 waves per SIMD, 80 VGPRs, one edge buffer of 32 KB each) so one workgroup's
 // load/store phase overlaps the others' VALU phases: 5 % faster than two workgroups at 121 VGPRs; the 7- and
 // 9-tap windows do not fit 80 registers without spilling and stay at two.
+// (The same 128-row tile held by 256 threads x 16 rows -- 107 VGPRs, nothing spilled, 16 KB of edge rows, FOUR workgroups per CU at
+// 4 waves per SIMD, 9 % fewer VALU instructions per launch -- was built and measured: Gauss5 x17 at 4096^2 0.147 against 0.139 ms,
+// 0.149 with two edge buffers and one barrier per application.  A workgroup is then ONE wave per SIMD, and a lone wave issues a
+// VALU instruction every 4 cycles where the SIMD takes one every 2: a tile no longer fills its SIMDs by itself, and the issue
+// fraction fell from 0.70 to 0.60.  HISTORY.md, "256 threads x 16 rows".)
 constexpr int conv_waves(int ks, int nt, int rbt) { return rbt < RB ? 4 : ks == 5 ? 6 : (nt >= 512 || ks >= 7) ? 4 : 6; }
 // edge-row buffers: two (one barrier per application) for the 3-tap kernel, one (two barriers) for the others -- see conv_tile.
 // (Two for the 5-tap kernel costs a resident workgroup: 64 KB of LDS.  The small grids' shapes with two: Gauss5 x17 512^2
@@ -349,24 +354,30 @@ __device__ __forceinline__ void conv_tile(const float *__restrict__ src, float *
 #pragma unroll
             for (int e = 0; e < 4; e++) z[O + r][e] = v[r][e];
         if (!inside) {
-            if (iz0 > 0 && iz0 < ZN) {
+            // The row clamps compare against copies of iz0 / iz1 the compiler cannot see through, so an edge tile forms its
+            // 4 x ZN lane masks in every application (a v_cmp each, where it reloaded a spilled mask with two v_readlane).
+            // Left loop-invariant, the compiler hoists all of them in front of the loop, where EVERY tile computes them and spills
+            // them to VGPR lanes: ~120 of an interior 5-tap tile's ~2 500 VALU instructions, for masks it never reads.
+            int jz0 = iz0, jz1 = iz1;
+            asm volatile("" : "+v"(jz0), "+v"(jz1));
+            if (jz0 > 0 && jz0 < ZN) {
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
                     float c = z[0][e];
 #pragma unroll
-                    for (int i = 1; i < ZN; i++) c = (i == iz0) ? z[i][e] : c;
+                    for (int i = 1; i < ZN; i++) c = (i == jz0) ? z[i][e] : c;
 #pragma unroll
-                    for (int i = 0; i < ZN - 1; i++) z[i][e] = (i < iz0) ? c : z[i][e];
+                    for (int i = 0; i < ZN - 1; i++) z[i][e] = (i < jz0) ? c : z[i][e];
                 }
             }
-            if (iz1 >= 0 && iz1 < ZN - 1) {
+            if (jz1 >= 0 && jz1 < ZN - 1) {
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
                     float c = z[0][e];
 #pragma unroll
-                    for (int i = 1; i < ZN; i++) c = (i == iz1) ? z[i][e] : c;
+                    for (int i = 1; i < ZN; i++) c = (i == jz1) ? z[i][e] : c;
 #pragma unroll
-                    for (int i = 1; i < ZN; i++) z[i][e] = (i > iz1) ? c : z[i][e];
+                    for (int i = 1; i < ZN; i++) z[i][e] = (i > jz1) ? c : z[i][e];
                 }
             }
         }
