@@ -647,6 +647,19 @@ int32_t nz_erode_height_maps_and_flow(nz_ctx *ctx, float *height, nz_erosive_eve
 int32_t nz_pool_automata_job(nz_ctx *ctx, float *pool, const float *height, nz_particle_queue *particleQueue,
                              const nz_erosion_params *ep, const nz_tile_set_meta *tm, int32_t iterations, int32_t res,
                              int32_t drainParticles, nz_handle dep, nz_handle *out);
+/* Test hooks of the pool automaton (both entries above), whose job runs in one of several launch forms with the same results.
+ * nz_debug_pool_forms sets the two process-wide switches for jobs enqueued after the call: runs == 0 = one lane per row, no
+ * masks (NZ_POOL_RUNS=0); sparse == 0 = dense runs with no list and no control block, 1 = the default rule, 2 = always the
+ * one-workgroup launch (NZ_POOL_SPARSE).  A negative argument restores what the environment gave (default 1 / 1); sparse
+ * above 2 is NZ_ERR_INVALID.  Atomic, like nz_debug_fill_sweeps.
+ * nz_debug_pool_last_job synchronises the context and reports how its last pool job (of one iteration or more) ran, six ints:
+ *   [0] runs and [1] sparse as the job read them; [2] 1 if the host enqueued the dense launches; [3] 1 if the one-workgroup
+ *   launch took the whole job; [4] 1 if the dense passes walked whole rows (at least seven steps in eight acted); [5] the
+ *   non-empty mask words the one-workgroup launch reported for THIS job (what the next job's choice rests on), -1 if the
+ *   report is another job's or there was no such launch.  With runs == 0 or sparse == 0: [3] = [4] = 0, [5] = -1.
+ * NZ_ERR_INVALID: a NULL argument, or a context that has run no pool job. */
+int32_t nz_debug_pool_forms(int32_t runs, int32_t sparse);
+int32_t nz_debug_pool_last_job(nz_ctx *ctx, int32_t *info);
 /* CurvitureMapJob.ScheduleRun(texture, height, tm, target, res, deps), :413-435: `texture` = device RGBA32 pixels of a
  * meshRes^2 texture (4 bytes per pixel), target = ColorChannelByte {R, G, B, A} */
 int32_t nz_curviture_map(nz_ctx *ctx, uint8_t *texture, const float *height, const nz_tile_set_meta *tm, int32_t target,

@@ -249,6 +249,8 @@ SIGNATURES = {
     "nz_erode_height_maps": (_i, [ctx_p, dev_ptr, C.c_void_p, ep_p, tm_p, _i] + _tail),
     "nz_erode_height_maps_and_flow": (_i, [ctx_p, dev_ptr, C.c_void_p, dev_ptr, dev_ptr, dev_ptr, ep_p, tm_p, _i] + _tail),
     "nz_pool_automata_job": (_i, [ctx_p, dev_ptr, dev_ptr, C.c_void_p, ep_p, tm_p, _i, _i, _i] + _tail),
+    "nz_debug_pool_forms": (_i, [_i, _i]),
+    "nz_debug_pool_last_job": (_i, [ctx_p, C.POINTER(_i)]),
     "nz_curviture_map": (_i, [ctx_p, dev_ptr, dev_ptr, tm_p, _i, _i, _i] + _tail),
     "nz_set_rgba32": (_i, [ctx_p, dev_ptr, dev_ptr, _i, _i, _i, _f] + _tail),
     "nz_crop_job": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

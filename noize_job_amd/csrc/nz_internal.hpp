@@ -95,6 +95,9 @@ struct nz_ctx {
     int *pool_ctl = nullptr;
     unsigned long long *pool_hint = nullptr, *pool_hint_dev = nullptr;
     unsigned long long pool_seq = 0;
+    // how the last pool job ran (nz_debug_pool_last_job): the two switches as it read them, and whether the host enqueued the
+    // dense launches; -1: no job yet
+    int pool_last_runs = -1, pool_last_sparse = -1, pool_last_dense = 0;
     int float_mode = NZ_FLOAT_STRICT;  // nz_ctx_set_float_mode
 };
 int32_t nz_ctx_pool_state(nz_ctx *ctx);  // allocates the three on first use

@@ -1,5 +1,6 @@
 // nz_stages.cpp -- the extern "C" stage entry points of libnoize_hip.so (one per reference job delegate or
 // PipelineStage.Schedule body, include/noize_hip.h) and the launch planners behind them.
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -1129,9 +1130,22 @@ extern "C" int32_t nz_update_flow_from_track(nz_ctx *ctx, float *pool, float *fl
 //       * the dense form otherwise: the sparse launch first (it still takes a job with few words and then turns the dense
 //         launches into no-ops; and it reports), then 4 launches per iteration and a clean between iterations.
 //   NZ_POOL_SPARSE=0: never the sparse launch; =2: always, and nothing follows it (the test matrix).
+// Both switches are process-wide atomics that start from the environment; nz_debug_pool_forms sets them at run time (a job
+// keeps the pair it read when it was enqueued), and nz_debug_pool_last_job says how the context's last job ran.
+static int pool_env(const char *name) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : 1;
+}
+static int pool_env_runs() { static const int v = pool_env("NZ_POOL_RUNS"); return v; }
+static int pool_env_sparse() { static const int v = pool_env("NZ_POOL_SPARSE"); return v; }
+static std::atomic<int> pool_runs{pool_env_runs()}, pool_sparse{pool_env_sparse()};
+
 static int32_t pool_job(nz_ctx *ctx, float *pool, const float *height, int res, int iterations, int32_t *hdr, nz_particle *data) {
-    static const int runs = [] { const char *e = getenv("NZ_POOL_RUNS"); return e ? atoi(e) : 1; }();
-    static const int sparse = [] { const char *e = getenv("NZ_POOL_SPARSE"); return e ? atoi(e) : 1; }();
+    const int runs = pool_runs.load(), sparse = pool_sparse.load();
+    if (iterations == 0) return NZ_OK;  // no launch, and nothing for nz_debug_pool_last_job to report
+    ctx->pool_last_runs = runs;
+    ctx->pool_last_sparse = sparse;
+    ctx->pool_last_dense = 0;
     if (!runs) {
         for (int i = 0; i < iterations; i++)
             for (int xoff = 0; xoff < 2; xoff++)
@@ -1139,7 +1153,6 @@ static int32_t pool_job(nz_ctx *ctx, float *pool, const float *height, int res, 
                     NZ_TRY(nz_launch_pool_automata_pass(ctx->stream, pool, height, res, xoff, zoff, hdr, data, nullptr, nullptr));
         return NZ_OK;
     }
-    if (iterations == 0) return NZ_OK;
     float *p = nullptr;
     NZ_TRY(nz_ctx_scratch(ctx, nz_pool_automata_mask_words(res), &p));
     unsigned *mask = reinterpret_cast<unsigned *>(p);
@@ -1160,6 +1173,7 @@ static int32_t pool_job(nz_ctx *ctx, float *pool, const float *height, int res, 
     } else {
         NZ_TRY(nz_launch_pool_automata_masks(ctx->stream, pool, res, mask, nullptr, 0));
     }
+    ctx->pool_last_dense = dense ? 1 : 0;
     if (!dense) return NZ_OK;
     for (int i = 0; i < iterations; i++) {
         if (i > 0) NZ_TRY(nz_launch_pool_automata_clean(ctx->stream, pool, res, mask, ctl));
@@ -1167,6 +1181,32 @@ static int32_t pool_job(nz_ctx *ctx, float *pool, const float *height, int res, 
             for (int zoff = 0; zoff < 2; zoff++)
                 NZ_TRY(nz_launch_pool_automata_pass(ctx->stream, pool, height, res, xoff, zoff, hdr, data, mask, ctl));
     }
+    return NZ_OK;
+}
+
+extern "C" int32_t nz_debug_pool_forms(int32_t runs, int32_t sparse) {
+    NZ_REQUIRE(sparse <= 2, "sparse %d is none of 0, 1, 2 (negative: the environment's)", sparse);
+    pool_runs.store(runs < 0 ? pool_env_runs() : (runs != 0 ? 1 : 0));
+    pool_sparse.store(sparse < 0 ? pool_env_sparse() : sparse);
+    return NZ_OK;
+}
+
+extern "C" int32_t nz_debug_pool_last_job(nz_ctx *ctx, int32_t *info) {
+    NZ_REQUIRE(ctx && info, "ctx/info is NULL");
+    NZ_REQUIRE(ctx->pool_last_runs >= 0, "the context has run no pool job");
+    NZ_TRY(nz_ctx_synchronize(ctx));
+    info[0] = ctx->pool_last_runs;
+    info[1] = ctx->pool_last_sparse;
+    info[2] = ctx->pool_last_dense;
+    info[3] = info[4] = 0;
+    info[5] = -1;
+    if (!ctx->pool_last_runs || !ctx->pool_last_sparse) return NZ_OK;  // nothing device-side exists
+    int ctl[4] = {0, 0, 0, 0};
+    NZ_HIP(hipMemcpy(ctl, ctx->pool_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+    info[3] = ctl[1];
+    info[4] = ctl[3];
+    const unsigned long long hint = *reinterpret_cast<volatile unsigned long long *>(ctx->pool_hint);
+    if (hint >> 32 == (ctx->pool_seq & 0xffffffffull)) info[5] = (int32_t)(unsigned)hint;
     return NZ_OK;
 }
 

@@ -662,9 +662,11 @@ def test_live_erosion_grid_jobs(nj, ctx, oracle, res):
 
 
 @pytest.mark.parametrize("res,cover", [(66, 1.0), (130, 0.6), (257, 1.0), (257, 0.03), (512, 0.9)])
-def test_pool_automata_runs_match_the_row_walk(nj, ctx, oracle, res, cover):
+def test_pool_automata_runs_match_the_row_walk(nj, oracle, res, cover):
     # the pass runs as parallel runs of acting steps (pool_runs_kernel): lakes that span mask words and whole rows,
-    # isolated puddles, water below the 1E-3 threshold between them, odd sizes -- all equal to the oracle's row walk
+    # isolated puddles, water below the 1E-3 threshold between them, odd sizes -- all equal to the oracle's row walk.
+    # On a context of its own: the first job of a context takes the dense launches, and its report stays out of the
+    # session context's hint (tests/test_gpu_pool_forms.py pins the forms one by one)
     rng = np.random.default_rng(res + int(cover * 100))
     height = (rng.random((res, res), dtype=f32) * f32(0.2)).astype(f32)
     wet = rng.random((res, res)) < cover
@@ -672,27 +674,29 @@ def test_pool_automata_runs_match_the_row_walk(nj, ctx, oracle, res, cover):
     pool[rng.random((res, res)) < 0.1] = f32(0.0005)      # standing water that does not act
     pool[:, res // 2] = f32(0.25)                          # one full line of water either way
     pool[res // 3, :] = f32(0.25)
-    d_pool, d_h = ctx.from_host(pool), ctx.from_host(height)
-    ctx.call("nz_pool_automata", d_pool.ptr, d_h.ptr, 2, res).Complete()
-    assert np.array_equal(d_pool.ToArray((res, res)), oracle.pool_automata(pool, height, 2))
+    with nj.Context(0) as ctx:
+        d_pool, d_h = ctx.from_host(pool), ctx.from_host(height)
+        ctx.call("nz_pool_automata", d_pool.ptr, d_h.ptr, 2, res).Complete()
+        assert np.array_equal(d_pool.ToArray((res, res)), oracle.pool_automata(pool, height, 2))
 
 
 @pytest.mark.parametrize("res,wet", [(512, 1.0), (640, 0.93), (512, 0.6)])
-def test_pool_automata_on_a_plane_under_water(nj, ctx, oracle, res, wet):
+def test_pool_automata_on_a_plane_under_water(nj, oracle, res, wet):
     # At least seven steps in eight acting: the job's launches walk whole rows, one lane each (the sparse launch decides
-    # that on the device, from this job's own plane: ctl[3]); fewer: parallel runs.  Twice on the same context,
+    # that on the device, from this job's own plane: ctl[3]); fewer: parallel runs.  Twice on the same context (its own),
     # so that the second job also meets the first one's report.  All equal to the oracle's row walk.
     rng = np.random.default_rng(res + int(wet * 10))
     height = (rng.random((res, res), dtype=f32) * f32(0.2)).astype(f32)
     pool = np.where(rng.random((res, res)) < wet, f32(0.002) + rng.random((res, res), dtype=f32) * f32(0.3), 0).astype(f32)
     want = oracle.pool_automata(pool, height, 3)
-    d_h = ctx.from_host(height)
-    for _ in range(2):
-        d_pool = ctx.from_host(pool)
-        ctx.call("nz_pool_automata", d_pool.ptr, d_h.ptr, 3, res).Complete()
-        assert np.array_equal(d_pool.ToArray((res, res)), want)
-        d_pool.Dispose()
-    d_h.Dispose()
+    with nj.Context(0) as ctx:
+        d_h = ctx.from_host(height)
+        for _ in range(2):
+            d_pool = ctx.from_host(pool)
+            ctx.call("nz_pool_automata", d_pool.ptr, d_h.ptr, 3, res).Complete()
+            assert np.array_equal(d_pool.ToArray((res, res)), want)
+            d_pool.Dispose()
+        d_h.Dispose()
 
 
 @pytest.mark.parametrize("n", [1, 3, 255, 1024, 4099, 300 * 300, 2048 * 2048 + 5])
