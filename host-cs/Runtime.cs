@@ -73,6 +73,13 @@ namespace xshazwar.noize.hip {
         public IntPtr rainMap;
     }
 
+    // the watershed stage's scalars (nz_watershed*)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzWatershedDesc {                                                                  // nz_watershed_desc
+        public float seaLevel, cellSize;
+        public int maxPasses;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

@@ -546,6 +546,68 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; plane?.Dispose(); plane = null; }
     }
 
+    // Watershed (new-framework feature; the model: nz_watershed in include/noize_hip.h): the steepest-descent tree of the
+    // payload's heights read upstream -- which outlet or pit every cell drains to, how far along the river it lies, and the
+    // tree itself.  The heights pass through untouched.  Once the handle completes, Basin holds the labels of the last payload
+    // (count * resolution^2 int32 in four-byte cells: BitConverter.SingleToInt32Bits; the index of the outlet or pit inside
+    // the cell's own tile), Length the flow-path length to it and Receivers one code per cell (0..7 in the order W E S N SW SE
+    // NW NE, 8 without a receiver; four codes per cell of the tile); Passes and Converged wait for the handle and read the
+    // status words.  seaLevel: cells at or below it are outlets like the border (-float.MaxValue: off).  cellSize: the length
+    // of a straight move.  maxPasses null means the default, 64 + resolution / 4; a budget that runs out is no error:
+    // Converged is false, the labels are the cells' own indices and the length is zero.  length = false: labels only.
+    // recordReceivers: keep the receiver plane.
+    public class WatershedStage : PipelineStage {
+        public float seaLevel = -float.MaxValue, cellSize = 1f;
+        public int? maxPasses = null;
+        public bool length = true;
+        public bool recordReceivers = false;
+        DeviceTile work;                         // nz_watershed_work_floats floats; its first two int32: {passes, converged}
+        DeviceTile labels, lengths, codes;
+        int resolution, count = 1;
+        public WatershedStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Basin => labels;
+        public DeviceTile Length => lengths;
+        public DeviceTile Receivers => codes;
+        public int? Passes => Status(0);
+        public bool? Converged => Status(1) is int c ? c == 1 : (bool?) null;
+        int? Status(int k) {
+            if (work == null) return null;
+            jobHandle.Complete();
+            return BitConverter.SingleToInt32Bits(work.Offset(0, 2).ToArray()[k]);
+        }
+        DeviceTile Size(DeviceTile t, bool want, int n) {   // a plane of the stage: resized with the payload, gone when not wanted
+            if (t != null && (!want || t.Length != n)) { t.Dispose(); t = null; }
+            return want && t == null ? ctx.Alloc(n) : t;
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            // sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+            int need = (int) (ulong) Native.nz_watershed_work_floats(resolution, count, length ? 1 : 0);
+            if (work == null || work.Length != need) { work?.Dispose(); work = ctx.Alloc(need); }
+            labels = Size(labels, true, Cells);
+            lengths = Size(lengths, length, Cells);
+            codes = Size(codes, recordReceivers, (Cells + 3) / 4);   // one byte per cell
+            NzWatershedDesc desc = new NzWatershedDesc { seaLevel = seaLevel, cellSize = cellSize, maxPasses = maxPasses ?? 64 + resolution / 4 };
+            IntPtr l = lengths != null ? lengths.Ptr : IntPtr.Zero, r = codes != null ? codes.Ptr : IntPtr.Zero;
+            ulong h;
+            if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_watershed_batch(ctx.Handle, b.data.Ptr, labels.Ptr, l, r, work.Ptr, ref desc, b.resolution, b.count, dependency.id, out h), "nz_watershed_batch");
+            } else {
+                Native.Check(Native.nz_watershed(ctx.Handle, d.data.Ptr, labels.Ptr, l, r, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_watershed");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() {
+            work?.Dispose(); work = null; labels?.Dispose(); labels = null; lengths?.Dispose(); lengths = null; codes?.Dispose(); codes = null;
+        }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

@@ -988,7 +988,7 @@ int32_t nz_debug_fill_sweeps(int32_t sweeps);
  * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: rain or seaLevel not finite (-FLT_MAX
  * switches the sea off); rain < 0; maxPasses < 1; a NULL desc, height, drainage or work; drainage overlapping height, work
  * or rainMap; work overlapping height or rainMap.
- * There is no _rw form (the heights do not change) and no receiver-code output. */
+ * There is no _rw form (the heights do not change) and no receiver-code output: nz_watershed, below, has one. */
 typedef struct nz_drainage_desc {
     float rain, seaLevel;
     int32_t maxPasses;
@@ -1042,6 +1042,69 @@ int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_stripe *st, 
 /* Test hook, the twin of nz_debug_fill_sweeps: the cap on a drainage pass's on-chip sweeps per tile (process-wide; <= 0
  * restores the default).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_drainage_sweeps(int32_t sweeps);
+
+/* ---- watershed: basin labels, flow length and receiver codes of a heightmap (new-framework feature) --------------------
+ * The steepest-descent tree read the other way: which outlet a cell drains to, how far along the river it lies, and the
+ * tree itself.  Catchment labels give lake and basin masks and regions per river system, the flow length a distance to the
+ * mouth, the receiver plane lets a host trace river polylines.  Feed it a filled tile (nz_fill_depressions) and every label
+ * lies on the border.
+ *
+ * THE MODEL (tests/watershed_ref.py restates it as a walk lowest cell first; the kernels are nz_watershed.hip):
+ *   Square tile res x res, row-major c = z * res + x, float32 heights, read only.  Outlets, the neighbour order
+ *   W E S N SW SE NW NE, "a neighbour outside the tile does not exist" and the receiver r(c) with its strict comparison and
+ *   tie rule are exactly step 1 of the fluvial model above: border cells and cells <= seaLevel have no receiver, and an
+ *   interior cell without a strictly lower neighbour, a pit, has none either.  For every cell:
+ *     r(c) == NONE:  basin[c] = c (int32) and length[c] = +0;
+ *     otherwise, with q the neighbour r(c) names:  basin[c] = basin[q] and length[c] = length[q] + step_k,
+ *   step_k = cellSize for k < 4 and cellSize * 0x1.6a09e6p+0f (one product, rounded once to float32) for k >= 4.  No
+ *   contraction, the same in every float mode (nz_ctx_set_float_mode does not apply).  In a batch c is the index inside the
+ *   cell's own tile.
+ * A receiver is strictly lower than its donor, so the graph is a forest, a cell's value is a fixed function of one other
+ * cell's final value and the fixed point is unique: a walk lowest cell first, Jacobi and tile sweeps end in the same bits.
+ * What follows:
+ *   - every label names a cell without a receiver, and basin[basin[c]] == basin[c];
+ *   - the number of cells that carry label o is what nz_drainage_area with rain 1 holds at o;
+ *   - length with cellSize 2 is twice length with cellSize 1, bit for bit.
+ * `receivers` (optional, NULL: not wanted) receives one byte per cell: the code 0..7, or 8 for outlets and pits alike.
+ * `length` is optional too (NULL): a labels-only call carries no float plane at all.
+ *
+ * The entry enqueues one receiver launch (heights -> one receiver byte per cell, into `receivers` or `work`), maxPasses
+ * pass launches and one finalise launch, stream-ordered; nothing is read back.  A pass is nz_drainage_area's scheme with
+ * the data flow reversed: every 64 x 16 tile is swept on chip against its frozen ring, each cell reading the one cell its
+ * code names; tiles whose neighbourhood was at rest in the pass before are skipped, and a launch returns at once when the
+ * pass before changed nothing.  After completion the first two int32 of `work` hold {passes that did work, converged 0/1}.
+ * The result is ALL OR NOTHING: when the last pass that ran changed nothing, `basin` and `length` hold the fixed point;
+ * otherwise -- the budget was too small -- they hold the start state, own index and +0, and converged == 0, which is not
+ * an error (`receivers` is complete either way).  A pass is at least one Jacobi step, so a budget of "moves of the longest
+ * flow path" + 2 always suffices; the hosts' default is far below that and measured ("watershed").
+ * Defaults of the hosts' WatershedStage: seaLevel -FLT_MAX (off), cellSize 1, maxPasses 64 + resolution / 4, with length,
+ * without receivers.
+ * The evidence (tools/bench_watershed.py): the 13-octave simplex fBm tile behind nz_fill_depressions
+ * comes to rest in 82 passes at 1024^2 and 192 at 4096^2, as nz_drainage_area does; the defaults allow 320 and 1088.  Not
+ * a bound: a path that winds through many tiles needs more, and a budget that runs out shows as converged == 0.
+ *
+ * `work` = nz_watershed_work_floats(resolution, count, withLength) floats, stage-owned, withLength != 0 for a call with a
+ * `length` plane: status words, tile bytes, the receiver bytes and the second plane of each pair (the first is the
+ * caller's).  0 for resolution <= 0 or count <= 0.  The _batch form runs `count` tiles stored back to back, each with its
+ * own border and its own labels; every batch position equals the single-tile call bit for bit, and the status words cover
+ * the whole batch.  resolution == 0 or count == 0 does nothing and returns NZ_OK.  The 16-byte path runs when every plane is
+ * 16-byte aligned (the receiver bytes 4-byte) and resolution % 4 == 0, the 4-byte path otherwise; both give the same bits.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: a NULL desc, height, basin or work;
+ * cellSize not finite or not > 0; a NaN seaLevel (-FLT_MAX switches the sea off); maxPasses < 1; count * resolution^2
+ * beyond int32; basin, length, receivers or work overlapping height or each other.
+ * A row-stripe form is not built yet. */
+typedef struct nz_watershed_desc {
+    float seaLevel, cellSize;
+    int32_t maxPasses;
+} nz_watershed_desc;
+size_t nz_watershed_work_floats(int32_t resolution, int32_t count, int32_t withLength);
+int32_t nz_watershed(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers, float *work,
+                     const nz_watershed_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out);
+int32_t nz_watershed_batch(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers, float *work,
+                           const nz_watershed_desc *desc, int32_t resolution, int32_t count, nz_handle dep, nz_handle *out);
+/* Test hook, the twin of nz_debug_drainage_sweeps: the cap on a watershed pass's on-chip sweeps per tile (process-wide;
+ * <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
+int32_t nz_debug_watershed_sweeps(int32_t sweeps);
 
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as

@@ -10,7 +10,7 @@ from .runtime import Context, DeviceTile, JobHandle
 from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, ConstantStage, CropStage, CurveStage, DepressionFillStage, DownsampleData, DrainageAreaStage, DownsampleStage, ErosionStage, FlowMapStage, FluvialErosionStage, FractalNoise, FractalShape, GaussSigma,
                        GeneratorData, GeneratorDataBatch, HydraulicBorder, HydraulicErosionStage, KernelFilterStage, KernelFilterType, MeshBuffers, MeshStageData,
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
-                       ReducePipeline, ReduceStage, ShapedNoiseStage, UpsampleStage, Upstream, WarpedNoiseStage,
+                       ReducePipeline, ReduceStage, ShapedNoiseStage, UpsampleStage, Upstream, WarpedNoiseStage, WatershedStage,
                        ReductionType, ResampleFilter, StageGaussianBlur, StageThermalErosion,
                        StageIO, StageSmoothBlur)
 

@@ -100,10 +100,16 @@ class DrainageDesc(C.Structure):
     _fields_ = [("rain", C.c_float), ("seaLevel", C.c_float), ("maxPasses", C.c_int32), ("rainMap", C.c_void_p)]
 
 
+class WatershedDesc(C.Structure):
+    """nz_watershed_desc (include/noize_hip.h): the scalars of the watershed stage."""
+    _fields_ = [("seaLevel", C.c_float), ("cellSize", C.c_float), ("maxPasses", C.c_int32)]
+
+
 hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
 fill_p = C.POINTER(FillDesc)
 drain_p = C.POINTER(DrainageDesc)
+shed_p = C.POINTER(WatershedDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -222,6 +228,10 @@ SIGNATURES = {
     "nz_drainage_stripe_round": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, drain_p, _i, dev_ptr, dev_ptr] + _tail),
     "nz_drainage_stripe_finalise": (_i, [ctx_p, dev_ptr, stripe_p, drain_p, dev_ptr] + _tail),
     "nz_debug_drainage_sweeps": (_i, [_i]),
+    "nz_watershed_work_floats": (_sz, [_i, _i, _i]),
+    "nz_watershed": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, dev_ptr, shed_p, _i] + _tail),
+    "nz_watershed_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, dev_ptr, shed_p, _i, _i] + _tail),
+    "nz_debug_watershed_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

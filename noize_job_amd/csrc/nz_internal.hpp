@@ -463,6 +463,18 @@ int32_t nz_launch_drainage_stripe_pass(hipStream_t s, const unsigned char *donor
 int32_t nz_launch_drainage_stripe_finalise(hipStream_t s, float *a, const float *rain_map, const int *converged, float rain,
                                            const nz_geom &g);
 
+// watershed (nz_watershed.hip) on `count` tiles of res^2 cells stored back to back.  receivers: one receiver byte per cell
+// from the heights (the code 0..7, or 8 without a receiver).  pass `pass` of the series: label planes b_in -> b_out and,
+// when l_out is not NULL, length planes l_in -> l_out (pass 0 reads none: it derives the start state, own index and +0),
+// tile bytes flags_in -> flags_out, at most `sweeps` in-LDS sweeps per tile; cell / diag: the step of a straight and of a
+// diagonal move; status as in the drainage launches.  finalise sets status[1] and, when the series did not come to rest,
+// writes the start state to `basin` and (not NULL) `length`
+int32_t nz_launch_watershed_receivers(hipStream_t s, const float *h, unsigned char *recv, float sea, int res, int count);
+int32_t nz_launch_watershed_pass(hipStream_t s, const unsigned char *recv, const int *b_in, int *b_out, const float *l_in,
+                                 float *l_out, int *status, const unsigned char *flags_in, unsigned char *flags_out,
+                                 float cell, float diag, int res, int count, int pass, int sweeps);
+int32_t nz_launch_watershed_finalise(hipStream_t s, int *basin, float *length, int *status, int res, size_t n);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {

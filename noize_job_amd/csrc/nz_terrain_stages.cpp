@@ -1,5 +1,5 @@
 // nz_terrain_stages.cpp -- the extern "C" entry points of the terrain stages the reference does not have (grid hydraulic
-// erosion, fluvial erosion, depression filling, drainage area, resampling; include/noize_hip.h): tile, batch,
+// erosion, fluvial erosion, depression filling, drainage area, watershed, resampling; include/noize_hip.h): tile, batch,
 // read/write-pair and row-stripe forms.  The stripe geometry and the aliasing checks they share are in nz_planes.hpp.
 #include <atomic>
 #include <cmath>
@@ -723,6 +723,89 @@ extern "C" int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_s
     nz_ctx_arm_last_launch(ctx);
     NZ_TRY(nz_launch_drainage_stripe_finalise(ctx->stream, a, desc->rainMap, converged, desc->rain, nz_geom_from_stripe(*st)));
     return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// watershed: basin labels, flow length, receiver codes (new-framework feature, include/noize_hip.h, nz_watershed.hip)
+// ---------------------------------------------------------------------------------------------
+// The passes follow the fill stage's protocol (nz_relax_pass.hpp), so `work` begins as the fill's does -- 16 status words,
+// two generations of per-tile bytes -- and goes on with one receiver byte per cell (rounded up to 16 bytes; unused when the
+// caller has a `receivers` plane), the second label plane of count * res^2 int32 and, with a length, the second length
+// plane; the first planes are the caller's `basin` and `length`.
+namespace {
+constexpr int WATERSHED_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "watershed"
+std::atomic<int> watershed_sweeps{WATERSHED_SWEEPS};  // nz_debug_watershed_sweeps may be called while a thread runs an entry
+constexpr float WATERSHED_SQRT2 = 0x1.6a09e6p+0f;     // the diagonal step is cellSize times this, rounded once
+struct watershed_layout {
+    fill_layout f;
+    size_t recv_floats;
+    size_t total(bool with_length) const { return FILL_STATUS + 2 * f.gen_floats + recv_floats + (with_length ? 2 : 1) * f.n; }
+};
+watershed_layout watershed_layout_of(int res, int count) {
+    const fill_layout f = fill_layout_of(res, count);
+    return watershed_layout{f, (f.n + 15) / 16 * 4};
+}
+}  // namespace
+
+extern "C" size_t nz_watershed_work_floats(int32_t resolution, int32_t count, int32_t withLength) {
+    return resolution > 0 && count > 0 ? watershed_layout_of(resolution, count).total(withLength != 0) : 0;
+}
+
+extern "C" int32_t nz_debug_watershed_sweeps(int32_t sweeps) {
+    return watershed_sweeps.exchange(sweeps > 0 ? sweeps : WATERSHED_SWEEPS);
+}
+
+static int32_t watershed_impl(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers, float *work,
+                              const nz_watershed_desc *d, int res, int count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(basin, "basin is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(std::isfinite(d->cellSize), "cellSize is not finite");
+    NZ_REQUIRE(!std::isnan(d->seaLevel), "seaLevel is NaN");
+    NZ_REQUIRE(d->cellSize > 0.0f, "cellSize %g <= 0", (double)d->cellSize);
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    const watershed_layout L = watershed_layout_of(res, count);
+    const size_t n = L.f.n;
+    NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
+    const float *labels = reinterpret_cast<const float *>(basin);  // a plane of n 4-byte cells
+    const nz_named_plane writes[] = {{"basin", labels, n}, {"length", length, n}, {"work", work, L.total(length != nullptr)}};
+    const nz_named_plane reads[] = {{"height", height, n}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    for (const auto &p : {reads[0], writes[0], writes[1], writes[2]})  // the receiver plane is bytes, not floats
+        NZ_REQUIRE(!nz_bytes_overlap(receivers, n, p.p, p.floats * sizeof(float)), "receivers overlaps %s", p.name);
+    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
+    unsigned char *recv = receivers ? receivers : reinterpret_cast<unsigned char *>(c.planes);
+    float *second = c.planes + L.recv_floats;
+    int *labels2[2] = {basin, reinterpret_cast<int *>(second)};  // pass p writes plane p & 1 and byte generation p & 1
+    float *lengths[2] = {length, length ? second + n : nullptr};
+    const float cell = d->cellSize, diag = d->cellSize * WATERSHED_SQRT2;
+    const int sweeps = watershed_sweeps.load();  // one cap for the whole series
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_watershed_receivers(ctx->stream, height, recv, d->seaLevel, res, count));
+    for (int p = 0; p < d->maxPasses; p++)
+        NZ_TRY(nz_launch_watershed_pass(ctx->stream, recv, p ? labels2[(p - 1) & 1] : nullptr, labels2[p & 1],
+                                        p ? lengths[(p - 1) & 1] : nullptr, lengths[p & 1], c.status, c.flags[(p - 1) & 1],
+                                        c.flags[p & 1], cell, diag, res, count, p, sweeps));
+    nz_ctx_arm_last_launch(ctx);
+    // a series at rest holds the fixed point in both planes of a pair, so the caller's have it whichever was written last
+    NZ_TRY(nz_launch_watershed_finalise(ctx->stream, basin, length, c.status, res, n));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_watershed(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers,
+                                float *work, const nz_watershed_desc *desc, int32_t resolution, nz_handle dep,
+                                nz_handle *out) {
+    return watershed_impl(ctx, height, basin, length, receivers, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_watershed_batch(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers,
+                                      float *work, const nz_watershed_desc *desc, int32_t resolution, int32_t count,
+                                      nz_handle dep, nz_handle *out) {
+    return watershed_impl(ctx, height, basin, length, receivers, work, desc, resolution, count, dep, out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -967,6 +967,72 @@ class DrainageAreaStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, plane;
 };
 
+// Watershed (new-framework feature; the model: nz_watershed in include/noize_hip.h): the steepest-descent tree of the
+// payload's heights read upstream -- which outlet or pit every cell drains to, how far along the river it lies, and the
+// tree itself.  The heights pass through untouched.  Once the handle completes, basin() holds the labels of the last
+// payload (cells() int32, the index of the outlet or pit inside the cell's own tile), flowLength() the flow-path length to
+// it (the member the other hosts call length; here `length` is the parameter) and receivers() one code per cell (0..7 in
+// the order W E S N SW SE NW NE, 8 without a receiver); passes() and converged() wait for the handle and read the status
+// words.  seaLevel: cells at or below it are outlets like the border (-FLT_MAX: off).  cellSize: the length of a straight
+// move.  maxPasses < 1 means the default, 64 + resolution / 4; a budget that runs out is no error: converged() is false,
+// the labels are the cells' own indices and the length is zero.  length = false: labels only.  recordReceivers: keep the
+// receiver plane.
+class WatershedStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    float seaLevel = -3.402823466e+38f, cellSize = 1.f;
+    int maxPasses = 0;  // < 1: 64 + resolution / 4
+    bool length = true;
+    bool recordReceivers = false;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        // sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        const size_t need = nz_watershed_work_floats(resolution, count, length ? 1 : 0);
+        if (!work || work->Length != need) work.reset(new DeviceTile(ctx, need));
+        if (!labels || labels->Length != cells()) labels.reset(new DeviceTile(ctx, cells()));
+        if (!length) lengths.reset();
+        else if (!lengths || lengths->Length != cells()) lengths.reset(new DeviceTile(ctx, cells()));
+        const size_t codeFloats = (cells() + 3) / 4;  // one byte per cell
+        if (!recordReceivers) codes.reset();
+        else if (!codes || codes->Length != codeFloats) codes.reset(new DeviceTile(ctx, codeFloats));
+        const nz_watershed_desc desc{seaLevel, cellSize, maxPasses >= 1 ? maxPasses : 64 + resolution / 4};
+        int32_t *b = reinterpret_cast<int32_t *>(labels->ptr);
+        float *l = lengths ? lengths->ptr : nullptr;
+        uint8_t *r = codes ? reinterpret_cast<uint8_t *>(codes->ptr) : nullptr;
+        nz_handle h = 0;
+        if (auto *bd = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_watershed_batch(ctx, bd->data->ptr, b, l, r, work->ptr, &desc, bd->resolution, bd->count, dependency.id, &h),
+                  "nz_watershed_batch");
+        } else {
+            check(nz_watershed(ctx, d->data->ptr, b, l, r, work->ptr, &desc, d->resolution, dependency.id, &h), "nz_watershed");
+        }
+        jobHandle = done(h);
+    }
+    const int32_t *basin() const { return labels ? reinterpret_cast<const int32_t *>(labels->ptr) : nullptr; }  // nullptr before a payload
+    const float *flowLength() const { return lengths ? lengths->ptr : nullptr; }
+    const uint8_t *receivers() const { return codes ? reinterpret_cast<const uint8_t *>(codes->ptr) : nullptr; }
+    size_t cells() const { return (size_t)count * resolution * resolution; }
+    int passes() const { return status(0); }                // -1 before the first run
+    bool converged() const { return status(1) == 1; }
+    void OnDestroy() override { work.reset(); labels.reset(); lengths.reset(); codes.reset(); }
+
+  private:
+    int status(int k) const {
+        if (!work) return -1;
+        jobHandle.Complete();
+        int32_t words[2];
+        check(nz_tile_download(ctx, work->ptr, reinterpret_cast<float *>(words), 2, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[k];
+    }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, labels, lengths, codes;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

@@ -1136,6 +1136,118 @@ class DrainageAreaStage(PipelineStage):
         self.DisposeArrays()
 
 
+class WatershedStage(PipelineStage):
+    """Watershed (new-framework feature; the model is the comment block of nz_watershed in include/noize_hip.h): the
+    steepest-descent tree of the payload's heights read upstream -- which outlet or pit every cell drains to, how far along
+    the river it lies, and the tree itself.  The heights pass through untouched.  Once the stage's handle completes, `basin`
+    holds the labels of the last payload (count * resolution^2 int32, the index of the outlet or pit inside the cell's own
+    tile), `length` the flow-path length to it and `receivers` one code per cell (0..7 in the order W E S N SW SE NW NE, 8
+    without a receiver); `passes` and `converged` are the status words of that run.  Behind DepressionFillStage every label
+    lies on the border.
+
+    seaLevel: cells at or below it are outlets like the border cells (the default, -FLT_MAX, switches it off).  cellSize:
+    the length of a straight move; a diagonal one is cellSize * sqrt(2).  maxPasses: the number of pass launches; None means
+    64 + resolution // 4.  A budget that runs out is no error: converged is False, the labels are the cells' own indices and
+    the length is zero.  length=False: labels only, no float plane is carried.  recordReceivers: keep the receiver plane."""
+
+    SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+
+    def __init__(self, ctx, seaLevel=SEA_OFF, cellSize=1.0, maxPasses=None, length=True, recordReceivers=False):
+        super().__init__(ctx)
+        self.seaLevel = seaLevel
+        self.cellSize = cellSize
+        self.maxPasses = maxPasses
+        self.withLength = length
+        self.recordReceivers = recordReceivers
+        self.resolution = 0
+        self.count = 0
+        self.work = None        # nz_watershed_work_floats floats; its first two int32: {passes, converged}
+        self._basin = None      # the label plane: count * resolution^2 cells of 4 bytes
+        self._length = None     # the length plane (length=True)
+        self._receivers = None  # the receiver bytes (recordReceivers)
+
+    def DisposeArrays(self):
+        for t in (self.work, self._basin, self._length, self._receivers):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.work = self._basin = self._length = self._receivers = None
+
+    @property
+    def basin(self):
+        """The labels of the last run as int32, or None before the first payload and after OnDestroy."""
+        if self._basin is None:
+            return None
+        return self.ctx.wrap(self._basin.ptr, self._basin.Length, dtype=np.int32)
+
+    @property
+    def length(self):
+        """The flow-length plane(s) of the last run, or None: with length=False, before the first payload and after
+        OnDestroy."""
+        return self._length
+
+    @property
+    def receivers(self):
+        """The receiver codes of the last run (uint8), or None: without recordReceivers, before the first payload and
+        after OnDestroy."""
+        return self._receivers
+
+    def _status(self):
+        if self.work is None:
+            return None
+        self.jobHandle.Complete()
+        return self.ctx.wrap(self.work.ptr, 2, dtype=np.int32).ToArray()
+
+    @property
+    def passes(self):
+        """Passes of the last run that did work (the launches after them returned at once); None before the first run."""
+        s = self._status()
+        return None if s is None else int(s[0])
+
+    @property
+    def converged(self):
+        """Whether the last run reached the fixed point within maxPasses; None before the first run."""
+        s = self._status()
+        return None if s is None else bool(s[1])
+
+    def _size(self, tile, want, n, dtype=np.float32):
+        """A plane of the stage: n cells when wanted, resized with the payload, disposed of when not."""
+        if tile is not None and (not want or tile.Length != n):
+            tile.Dispose()
+            tile = None
+        if want and tile is None:
+            tile = self.ctx.alloc(n, dtype=dtype)
+        return tile
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        n = self.count * self.resolution * self.resolution
+        # sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        need = N.lib.nz_watershed_work_floats(self.resolution, self.count, 1 if self.withLength else 0)
+        if self.work is None or self.work.Length != need:
+            if self.work is not None and self.work.IsCreated:
+                self.work.Dispose()
+            self.work = self.ctx.alloc(need)
+        self._basin = self._size(self._basin, True, n)
+        self._length = self._size(self._length, bool(self.withLength), n)
+        self._receivers = self._size(self._receivers, bool(self.recordReceivers), n, np.uint8)
+        budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
+        desc = N.WatershedDesc(self.seaLevel, self.cellSize, budget)
+        planes = (self._basin.ptr, self._length.ptr if self._length is not None else None,
+                  self._receivers.ptr if self._receivers is not None else None, self.work.ptr)
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_watershed_batch", d.data.ptr, *planes, C.byref(desc), d.resolution, d.count,
+                                           dep=dependency)
+        else:
+            self.jobHandle = self.ctx.call("nz_watershed", d.data.ptr, *planes, C.byref(desc), d.resolution, dep=dependency)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
     def __init__(self, ctx, meshType=MeshType.SquareGridHeightMap):
         super().__init__(ctx)
