@@ -22,11 +22,27 @@ struct flux4 {
 //   * a total height is water + height: not -0 since the water is not, even over a plane of -0;
 //   * a height difference d = total - neighbour is -0 only for total == -0 (x - y is -0 only as -0 - +0): never;
 //   * a flux is fmaxf(0, old + d), one of its operands (+0 for a NaN): -0 only if old and d both were; scaled by
-//     K = fmaxf(0, fminf(1, water / (sum * dt))) with water >= +0 or NaN and sum >= +0, K is +0 .. 1 and the product
+//     K = fminf(1, water / (sum * dt)) with water >= +0 and sum >= +0, K is +0 .. 1 (below) and the product
 //     of two non-negative numbers is not -0.
 // So `flowIN = 0; flowIN += fE` is fE, and the first iteration's `old + d` with old == +0 is d.
+//
+// The same induction carries the sign argument of two more removals:
+//   * K needs no fmaxf(0, .).  The water is +0 .. +inf (never -0, never NaN: fmaxf(0, .) of the update), sum is a sum
+//     of fmaxf(0, .) values, +0 .. +inf, so is sum * dt, and the quotient of two such numbers is +0 .. +inf or NaN
+//     (0 / 0, inf / inf): never negative, never -0.  fminf(1, .) turns the NaN into 1, so its result is in [+0, 1] and
+//     fmaxf(0, .) hands it back unchanged.
+//   * Two adjacent cells a, b subtract the same two totals in both directions, D = a - b here and b - a there.  IEEE
+//     subtraction is antisymmetric but for the sign of a zero (a == b: both are +0) and of a NaN, and
+//     fmaxf(0, old - D) has the bits of fmaxf(0, old + (b - a)) for every old that is not -0 (no flux is): where D is
+//     +-0 both sums are old, a NaN sum is replaced by fmaxf, everywhere else b - a is -D exactly.  So one of the two
+//     cells may take the other's difference and subtract it (flux_sum<false>(old, D, true)).  NOT in the first
+//     iteration, whose flux is fmaxf(0, d) of the difference itself: fmaxf(+0, -0) meets the zero's sign there
+//     (tests/test_flow_shared_differences.py), so FIRST keeps a subtraction of its own.
+// sub: d is the neighbour's difference (neighbour - this cell's total), to be subtracted
 template <bool FIRST>
-__device__ __forceinline__ float flux_sum(float old, float d) { return FIRST ? d : old + d; }
+__device__ __forceinline__ float flux_sum(float old, float d, bool sub = false) {
+    return FIRST ? d : (sub ? old - d : old + d);
+}
 
 // ComputeFlowStep.CalculateCell, FlowMapComponents.cs:20-65
 __device__ __forceinline__ flux4 compute_flow(float totalHt, float water_0, float tW, float tE, float tS, float tN,
@@ -48,24 +64,29 @@ __device__ __forceinline__ flux4 compute_flow(float totalHt, float water_0, floa
     return f;
 }
 
-// The same without the branch, bit for bit.  Every f is fmaxf(0, .), so f is in [0, +inf] (never NaN: fmaxf returns its
-// other operand) and sum_ is in [0, +inf]: `sum_ > 0` fails only when all four are +0.  Then water_0 / 0 is +-inf or NaN,
-// which the clamp turns into a K of 0 or 1 (fminf(1, NaN) = 1), and +0 * K = +0 -- the zeros the else branch stores.
+// The same without the branch, bit for bit, from ready-made height differences: d.w, d.e, d.s, d.n are this cell's own
+// (total - neighbour), or, where sub_w / sub_s say so, the west / south neighbour's east / north difference (see above;
+// never with FIRST).  Every f is fmaxf(0, .), so f is in [0, +inf] (never NaN: fmaxf returns its other operand) and sum_
+// is in [0, +inf]: `sum_ > 0` fails only when all four are +0.  Then water_0 / 0 is +inf or NaN, which the clamp turns
+// into a K of 1 (fminf(1, NaN) = 1), and +0 * K = +0 -- the zeros the else branch stores.
 // FIRST: the map's first iteration, old == +0 (flux_sum)
+template <bool FIRST = false>
+__device__ __forceinline__ flux4 compute_flow_d(float water_0, flux4 d, bool sub_w, bool sub_s, flux4 old) {
+    flux4 f;
+    f.w = fmaxf(0.0f, flux_sum<FIRST>(old.w, d.w, sub_w));
+    f.e = fmaxf(0.0f, flux_sum<FIRST>(old.e, d.e));
+    f.s = fmaxf(0.0f, flux_sum<FIRST>(old.s, d.s, sub_s));
+    f.n = fmaxf(0.0f, flux_sum<FIRST>(old.n, d.n));
+    float sum_ = (f.w + f.e) + (f.s + f.n);
+    float K = fminf(1.0f, water_0 / (sum_ * TIMESTEP));  // without the reference's fmaxf(0, .): see above
+    f.w *= K; f.e *= K; f.s *= K; f.n *= K;
+    return f;
+}
+
 template <bool FIRST = false>
 __device__ __forceinline__ flux4 compute_flow_nb(float totalHt, float water_0, float tW, float tE, float tS, float tN,
                                                  flux4 old) {
-    float dW = totalHt - tW, dE = totalHt - tE, dS = totalHt - tS, dN = totalHt - tN;
-    flux4 f;
-    f.w = fmaxf(0.0f, flux_sum<FIRST>(old.w, dW));
-    f.e = fmaxf(0.0f, flux_sum<FIRST>(old.e, dE));
-    f.s = fmaxf(0.0f, flux_sum<FIRST>(old.s, dS));
-    f.n = fmaxf(0.0f, flux_sum<FIRST>(old.n, dN));
-    float sum_ = (f.w + f.e) + (f.s + f.n);
-    float K = water_0 / (sum_ * TIMESTEP);
-    K = fmaxf(0.0f, fminf(1.0f, K));
-    f.w *= K; f.e *= K; f.s *= K; f.n *= K;
-    return f;
+    return compute_flow_d<FIRST>(water_0, flux4{totalHt - tW, totalHt - tE, totalHt - tS, totalHt - tN}, false, false, old);
 }
 
 // UpdateWaterStep.CalculateCell, FlowMapComponents.cs:81-104

@@ -22,7 +22,8 @@ __device__ __forceinline__ float wave_next0(float v) {
 // stores, and every iteration crosses three workgroup barriers.  Here ONE WAVE owns a 128-column strip (two columns per
 // lane) and walks down its rows with the iterations pipelined behind each other, iteration i two rows behind iteration
 // i - 1 (time skewing).  Per iteration a lane keeps only what the rows still in flight need: two rows of total height
-// and water of the previous iteration and two rows of its own four outflows, 12 registers per column and iteration;
+// and water of the previous iteration and two rows of its own four outflows, 12 registers per column and iteration
+// (13 in strict mode after the first iteration: the row difference handed to the next step, fs_step);
 // the z-neighbours of a cell are those registers, the x-neighbours the adjacent lanes' (wave-shift DPP).  No LDS traffic
 // except the wave's private ring of height rows (tot = water + height needs the height again four times, two rows
 // later each time), no barrier, no flag.  Redundant work is the x halo (2n columns per side of 128) and the pipeline
@@ -59,6 +60,7 @@ struct fs_state {
     float Tm[NST][NC], T0[NST][NC];   // total height (water + height) of rows r - 1, r after iteration i - 1
     float Wm[NST][NC], W0[NST][NC];   // water of rows r - 1, r after iteration i - 1
     float FA[NST][NC][4], FB[NST][NC][4];  // {W, E, S, N} outflow of rows r - 2, r - 1 of iteration i
+    float dN[NST][NC];                // strict mode, i > 0: row r - 1's total minus row r's (shared differences, fs_step)
 };
 
 struct fs_bounds {
@@ -76,6 +78,14 @@ struct fs_bounds {
 //   XEDGE: the strip touches the grid's first / last column: the lane that holds it takes its own value for the clamped
 //          x-neighbour (column 0 is the first of its lane's two columns; the last column the second, or the first when the row length is odd).
 // Cells outside the grid are computed like any other and never read by a cell inside it.
+// Shared differences (strict mode, stages after the first; nz_flow_common.hpp has the proof): two adjacent cells need the
+// same difference of totals with opposite signs, so each is formed once.  In x a lane forms D[e] = its column e minus the
+// column east of it (the next lane's first column as the DPP source of that subtraction); D[e] is the east difference of
+// column e and, subtracted, the west difference of column e + 1 -- for the lane's first column the previous lane's last D,
+// again a DPP source.  In z a stage keeps dN = row r minus row r + 1 for the next step, where it is row r + 1's south
+// difference, subtracted.  Where a border clamp makes a cell its own neighbour the cell keeps its direct subtraction
+// (self - self is NaN for a non-finite cell, not the other cell's difference): the west difference of an XEDGE strip's
+// first column, and every south difference of a COND step, whose dN is still kept for the steady step that follows it.
 template <int NST, int NC, int NACT, bool COND, bool XEDGE, bool VEC, bool FAST>
 __device__ __forceinline__ void fs_step(fs_state<NST, NC> &st, const int t, const fs_row<NC> hp, const fs_row<NC> hn,
                                         fs_row<NC> *ring, const fs_bounds &b, const int gx, const bool lane_x0,
@@ -96,6 +106,7 @@ __device__ __forceinline__ void fs_step(fs_state<NST, NC> &st, const int t, cons
         if (i == NACT) {  // not computing yet: its windows follow what stage NACT - 1 hands on
 #pragma unroll
             for (int e = 0; e < NC; e++) {
+                if (!FAST) st.dN[i][e] = st.T0[i][e] - Tp[e];  // the south difference of the first row it will compute
                 st.Tm[i][e] = st.T0[i][e]; st.T0[i][e] = Tp[e];
                 st.Wm[i][e] = st.W0[i][e]; st.W0[i][e] = Wp[e];
             }
@@ -113,7 +124,47 @@ __device__ __forceinline__ void fs_step(fs_state<NST, NC> &st, const int t, cons
         if (i == NACT - 1) ring[((t + 2) & (FS_RING - 1)) * 64] = hn;
         // ---- outflow of row r (ComputeFlowStep)
         const bool fa = !COND || (r >= b.loF[i] && r < b.hiF[i]);
-        if (fa) {
+        const bool share = !FAST && i > 0;
+        float dNn[NC];  // row r minus row r + 1: kept for the next step whether or not this one computes
+#pragma unroll
+        for (int e = 0; e < NC; e++) {
+            float tN = Tp[e];
+            if (COND && r >= g.zc1) tN = st.T0[i][e];
+            dNn[e] = share ? st.T0[i][e] - tN : 0.0f;
+        }
+        if (fa && share) {
+            float right = wave_next0(st.T0[i][0]);
+            if (XEDGE) right = lane_x1 ? st.T0[i][NC - 1] : right;
+            float D[NC];
+#pragma unroll
+            for (int e = 0; e < NC; e++) {
+                float tE = e == NC - 1 ? right : st.T0[i][e + 1 < NC ? e + 1 : e];
+                if (XEDGE && NC == 2 && e == 0 && lane_x1o) tE = st.T0[i][e];
+                D[e] = st.T0[i][e] - tE;
+            }
+            float dW0;
+            if (XEDGE) {
+                float left = wave_prev0(st.T0[i][NC - 1]);
+                left = lane_x0 ? st.T0[i][0] : left;
+                dW0 = st.T0[i][0] - left;
+            } else {
+                dW0 = wave_prev0(D[NC - 1]);
+            }
+#pragma unroll
+            for (int e = 0; e < NC; e++) {
+                const float self = st.T0[i][e];
+                flux4 d;
+                d.w = e == 0 ? dW0 : D[e > 0 ? e - 1 : 0];
+                d.e = D[e];
+                d.s = st.dN[i][e];
+                if (COND) d.s = self - (r <= g.zc0 ? self : st.Tm[i][e]);
+                d.n = dNn[e];
+                const flux4 old = flux4{st.FA[i > 0 ? i - 1 : 0][e][0], st.FA[i > 0 ? i - 1 : 0][e][1],
+                                        st.FA[i > 0 ? i - 1 : 0][e][2], st.FA[i > 0 ? i - 1 : 0][e][3]};
+                const flux4 f = compute_flow_d<false>(st.W0[i][e], d, !(XEDGE && e == 0), !COND, old);
+                FC[e][0] = f.w; FC[e][1] = f.e; FC[e][2] = f.s; FC[e][3] = f.n;
+            }
+        } else if (fa) {
             float left = wave_prev0(st.T0[i][NC - 1]), right = wave_next0(st.T0[i][0]);
             if (XEDGE) {
                 left = lane_x0 ? st.T0[i][0] : left;
@@ -220,6 +271,7 @@ __device__ __forceinline__ void fs_step(fs_state<NST, NC> &st, const int t, cons
         for (int e = 0; e < NC; e++) {
             st.Tm[i][e] = st.T0[i][e]; st.T0[i][e] = Tp[e];
             st.Wm[i][e] = st.W0[i][e]; st.W0[i][e] = Wp[e];
+            if (share) st.dN[i][e] = dNn[e];
             Tp[e] = Tn[e]; Wp[e] = Wn[e];
 #pragma unroll
             for (int k = 0; k < 4; k++) FCprev[e][k] = FC[e][k];
@@ -283,6 +335,7 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
             st.Tm[i][e] = 0.0f; st.T0[i][e] = 0.0f; st.Wm[i][e] = 0.0001f; st.W0[i][e] = 0.0001f;
 #pragma unroll
             for (int k = 0; k < 4; k++) { st.FA[i][e][k] = 0.0f; st.FB[i][e][k] = 0.0f; }
+            st.dN[i][e] = 0.0f;
         }
     // rows read: [t0 - 1, t1], all clamped into the grid's rows (a clamped row is only ever a cell's z-neighbour beyond
     // the grid, which the COND steps replace)
