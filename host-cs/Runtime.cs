@@ -80,6 +80,14 @@ namespace xshazwar.noize.hip {
         public int maxPasses;
     }
 
+    // the stream-order stage's scalars and the optional drainage plane (nz_stream_order*); IntPtr.Zero = every cell is a channel cell
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzStreamOrderDesc {                                                                // nz_stream_order_desc
+        public float seaLevel, threshold;
+        public int maxPasses;
+        public IntPtr drainage;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

@@ -608,6 +608,72 @@ namespace xshazwar.noize.hip {
         }
     }
 
+    // Stream order (new-framework feature; the model: nz_stream_order in include/noize_hip.h): the channel cells of the
+    // payload's heights, their Strahler order and the unbranched reaches between heads and confluences.  The heights pass
+    // through untouched.  Once the handle completes, Order holds one byte per cell of the last payload (0: no channel, 1: a
+    // head reach, +1 where two reaches of the same order meet; four orders per cell of the tile) and Links the cell index,
+    // inside the cell's own tile, of the head or confluence its reach starts at (count * resolution^2 int32 in four-byte
+    // cells: BitConverter.SingleToInt32Bits; -1: no channel); Passes and Converged wait for the handle and read the status
+    // words.  seaLevel: cells at or below it are outlets like the border (-float.MaxValue: off).  drainage: a device plane
+    // of the payload's size the caller supplies and keeps alive, the one DrainageAreaStage.@out received; a cell is a channel
+    // cell when its drainage >= threshold; null: every cell is one.  maxPasses null means the default,
+    // 64 + resolution / 4; a budget that runs out is no error: Converged is false, the order is 1 on channel cells and every
+    // channel cell is its own link.  recordLinks: carry the link plane.  Strahler streams, as opposed to links, are the
+    // caller's to derive from the two planes.
+    public class StreamOrderStage : PipelineStage {
+        public float seaLevel = -float.MaxValue, threshold = 0f;
+        public int? maxPasses = null;
+        public DeviceTile drainage = null;
+        public bool recordLinks = false;
+        DeviceTile work;                         // nz_stream_order_work_floats floats; its first two int32: {passes, converged}
+        DeviceTile orders, linkPlane;
+        int resolution, count = 1;
+        public StreamOrderStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Order => orders;
+        public DeviceTile Links => linkPlane;
+        public int? Passes => Status(0);
+        public bool? Converged => Status(1) is int c ? c == 1 : (bool?) null;
+        int? Status(int k) {
+            if (work == null) return null;
+            jobHandle.Complete();
+            return BitConverter.SingleToInt32Bits(work.Offset(0, 2).ToArray()[k]);
+        }
+        DeviceTile Size(DeviceTile t, bool want, int n) {   // a plane of the stage: resized with the payload, gone when not wanted
+            if (t != null && (!want || t.Length != n)) { t.Dispose(); t = null; }
+            return want && t == null ? ctx.Alloc(n) : t;
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            if (drainage != null && drainage.Length != Cells)   // before any launch
+                throw new Exception($"StreamOrderStage: a drainage plane of {drainage.Length} floats does not fit the payload's {Cells}");
+            // sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+            int need = (int) (ulong) Native.nz_stream_order_work_floats(resolution, count, recordLinks ? 1 : 0);
+            if (work == null || work.Length != need) { work?.Dispose(); work = ctx.Alloc(need); }
+            orders = Size(orders, true, (Cells + 3) / 4);   // one byte per cell
+            linkPlane = Size(linkPlane, recordLinks, Cells);
+            NzStreamOrderDesc desc = new NzStreamOrderDesc {
+                seaLevel = seaLevel, threshold = threshold, maxPasses = maxPasses ?? 64 + resolution / 4,
+                drainage = drainage != null ? drainage.Ptr : IntPtr.Zero };
+            IntPtr l = linkPlane != null ? linkPlane.Ptr : IntPtr.Zero;
+            ulong h;
+            if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_stream_order_batch(ctx.Handle, b.data.Ptr, orders.Ptr, l, work.Ptr, ref desc, b.resolution, b.count, dependency.id, out h), "nz_stream_order_batch");
+            } else {
+                Native.Check(Native.nz_stream_order(ctx.Handle, d.data.Ptr, orders.Ptr, l, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_stream_order");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() {
+            work?.Dispose(); work = null; orders?.Dispose(); orders = null; linkPlane?.Dispose(); linkPlane = null;
+        }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

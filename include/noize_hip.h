@@ -1106,6 +1106,77 @@ int32_t nz_watershed_batch(nz_ctx *ctx, const float *height, int32_t *basin, flo
  * <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_watershed_sweeps(int32_t sweeps);
 
+/* ---- stream order: Strahler order and river links of a heightmap (new-framework feature) ----------------------------
+ * The last product of a river-network extraction: which cells are channel, how big each channel is as a class (Strahler
+ * order: brook, stream, river) and which cells form one unbranched reach, a link, that can become one polyline, one width,
+ * one spline.  Feed it a filled tile (nz_fill_depressions) and the plane nz_drainage_area wrote, with a threshold.
+ *
+ * THE MODEL (tests/stream_order_ref.py restates it as a walk highest cell first; the kernels are nz_stream_order.hip):
+ *   Square tile res x res, row-major c = z * res + x, float32 heights, read only.  Outlets, the neighbour order
+ *   W E S N SW SE NW NE, "a neighbour outside the tile does not exist" and the receiver r(c) with its strict comparison and
+ *   tie rule are exactly step 1 of the fluvial model above: border cells and cells <= seaLevel have no receiver.  The same
+ *   in every float mode (nz_ctx_set_float_mode does not apply).
+ *   ch(c), the channel predicate: drainage == NULL ? true : drainage[c] >= threshold -- one float32 comparison, so a NaN is
+ *   not a channel; static, read once, and nothing else decides it.  A sea or border cell is a channel cell like any other
+ *   when its drainage says so, so a river keeps its order at its mouth.
+ *   D(c): the existing neighbours k of c with r(k) == c and ch(k).
+ *   order[c] (uint8):  !ch(c): 0;  D(c) empty: 1;  otherwise, with m = max order[D(c)] and n = #{d in D(c) : order[d] == m},
+ *     order[c] = m + (n >= 2 ? 1 : 0).
+ *   link[c] (int32, optional plane):  !ch(c): -1;  |D(c)| != 1: c, a channel head or a confluence: a link starts here;
+ *     otherwise link[d] of the one donor.  In a batch c is the index inside the cell's own tile.
+ * A receiver is strictly lower than its donor, so the graph is a forest, every value is a fixed function of the donors'
+ * final values and the fixed point is unique: a walk highest cell first, Jacobi and tile-local sweeps end in the same
+ * bytes.  Order w needs at least 2^(w-1) channel heads upstream; the entries refuse count * resolution^2 >= 2^31, so
+ * order <= 31 and a byte never saturates.  The start state, and the "nothing" of all or nothing: order = ch ? 1 : 0,
+ * link = ch ? c : -1.  What follows:
+ *   - order > 0 <=> ch <=> link >= 0, and order never falls along a receiver step between channel cells;
+ *   - link[link[c]] == link[c], and the distinct links are exactly the channel cells with |D| != 1;
+ *   - without `drainage`, order[c] <= 1 + floor(log2(A[c])) for A the rain-1 nz_drainage_area.
+ * `link` is optional (NULL): an order-only call carries no 4-byte plane at all.
+ *
+ * The entry enqueues one mask launch (heights and drainage -> one channel-donor byte per cell into `work`, the start state
+ * into `order`), maxPasses pass launches and one finalise launch, stream-ordered; nothing is read back.  A pass is
+ * nz_drainage_area's scheme on small integers, max and count in place of a float sum: every 64 x 16 tile is swept on chip
+ * against its frozen ring; tiles whose neighbourhood was at rest in the pass before are skipped, and a launch returns at
+ * once when the pass before changed nothing.  After completion the first two int32 of `work` hold {passes that did work,
+ * converged 0/1}.  The result is ALL OR NOTHING: when the last pass that ran changed nothing, `order` and `link` hold the
+ * fixed point; otherwise -- the budget was too small -- they hold the start state and converged == 0, which is not an
+ * error.  A pass is at least one Jacobi step, so a budget of "cells of the longest chain of channel donors" + 2 always
+ * suffices; the hosts' default is far below that and measured ("stream order").
+ * Defaults of the hosts' StreamOrderStage: seaLevel -FLT_MAX (off), threshold 0, maxPasses 64 + resolution / 4, without
+ * drainage, without links.
+ * The evidence (tools/bench_stream_order.py): the 13-octave simplex fBm tile behind
+ * nz_fill_depressions, with the plane of nz_drainage_area and threshold 100, comes to rest in 59 passes at 1024^2 and 94 at
+ * 4096^2 (51 and 88 without a drainage plane), where nz_drainage_area takes 82 and 192; the defaults allow 320 and 1088.
+ * Not a bound: a channel that winds through many tiles needs more, and a budget that runs out shows as converged == 0.
+ *
+ * `work` = nz_stream_order_work_floats(resolution, count, withLinks) floats, stage-owned, any withLinks != 0 counting as 1,
+ * for a call with a `link` plane: status words, tile bytes, one channel-donor byte per cell, the second `order` plane and,
+ * with links, the second `link` plane (the first of each pair is the caller's).  0 for resolution <= 0 or count <= 0.  The
+ * _batch form runs `count` tiles stored back to back, each with its own border and its own link indices; every batch
+ * position equals the single-tile call bit for bit, and the status words cover the whole batch.  resolution == 0 or
+ * count == 0 does nothing and returns NZ_OK.  The wide path runs when resolution % 4 == 0, the byte planes are 4-byte
+ * aligned and height, drainage and link 16-byte aligned, the narrow path otherwise; both give the same bytes.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: a NULL desc, height, order or work;
+ * threshold not finite; a NaN seaLevel (-FLT_MAX switches the sea off); maxPasses < 1; count * resolution^2 beyond int32;
+ * order, link or work overlapping height, drainage or each other.
+ * A row-stripe form is not built; Strahler streams, as opposed to links, are the host's to derive
+ * from `order` and `link`. */
+typedef struct nz_stream_order_desc {
+    float seaLevel, threshold;
+    int32_t maxPasses;
+    const float *drainage;   /* NULL: every cell is a channel cell, threshold is not compared */
+} nz_stream_order_desc;
+size_t nz_stream_order_work_floats(int32_t resolution, int32_t count, int32_t withLinks);
+int32_t nz_stream_order(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,
+                        const nz_stream_order_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out);
+int32_t nz_stream_order_batch(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,
+                              const nz_stream_order_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                              nz_handle *out);
+/* Test hook, the twin of nz_debug_watershed_sweeps: the cap on a stream-order pass's on-chip sweeps per tile
+ * (process-wide; <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
+int32_t nz_debug_stream_order_sweeps(int32_t sweeps);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

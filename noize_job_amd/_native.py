@@ -105,11 +105,18 @@ class WatershedDesc(C.Structure):
     _fields_ = [("seaLevel", C.c_float), ("cellSize", C.c_float), ("maxPasses", C.c_int32)]
 
 
+class StreamOrderDesc(C.Structure):
+    """nz_stream_order_desc (include/noize_hip.h): the scalars of the stream-order stage and the optional drainage plane (a
+    device address; None = every cell is a channel cell)."""
+    _fields_ = [("seaLevel", C.c_float), ("threshold", C.c_float), ("maxPasses", C.c_int32), ("drainage", C.c_void_p)]
+
+
 hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
 fill_p = C.POINTER(FillDesc)
 drain_p = C.POINTER(DrainageDesc)
 shed_p = C.POINTER(WatershedDesc)
+order_p = C.POINTER(StreamOrderDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -232,6 +239,10 @@ SIGNATURES = {
     "nz_watershed": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, dev_ptr, shed_p, _i] + _tail),
     "nz_watershed_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, dev_ptr, shed_p, _i, _i] + _tail),
     "nz_debug_watershed_sweeps": (_i, [_i]),
+    "nz_stream_order_work_floats": (_sz, [_i, _i, _i]),
+    "nz_stream_order": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, order_p, _i] + _tail),
+    "nz_stream_order_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, order_p, _i, _i] + _tail),
+    "nz_debug_stream_order_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

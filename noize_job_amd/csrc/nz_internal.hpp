@@ -475,6 +475,21 @@ int32_t nz_launch_watershed_pass(hipStream_t s, const unsigned char *recv, const
                                  float cell, float diag, int res, int count, int pass, int sweeps);
 int32_t nz_launch_watershed_finalise(hipStream_t s, int *basin, float *length, int *status, int res, size_t n);
 
+// stream order (nz_stream_order.hip) on `count` tiles of res^2 cells stored back to back.  mask: one channel-donor byte per
+// cell from the heights and `drainage` (bit k: neighbour k drains into the cell and is a channel cell; drainage NULL: every
+// cell is one), and the start state ch ? 1 : 0 to `order`.  pass `pass` of the series: order planes o_in -> o_out and, when
+// l_out is not NULL, link planes l_in -> l_out (pass 0 reads the start state from o_in and no link plane: it derives
+// ch ? own index : -1), tile bytes flags_in -> flags_out, at most `sweeps` in-LDS sweeps per tile; status as in the
+// drainage launches.  finalise sets status[1] and, when the series did not come to rest, writes the start state to
+// `order` and (not NULL) `link`
+int32_t nz_launch_stream_mask(hipStream_t s, const float *h, const float *drainage, unsigned char *donors,
+                              unsigned char *order, float sea, float threshold, int res, int count);
+int32_t nz_launch_stream_pass(hipStream_t s, const unsigned char *donors, const unsigned char *o_in, unsigned char *o_out,
+                              const int *l_in, int *l_out, int *status, const unsigned char *flags_in,
+                              unsigned char *flags_out, int res, int count, int pass, int sweeps);
+int32_t nz_launch_stream_finalise(hipStream_t s, unsigned char *order, int *link, const float *drainage, int *status,
+                                  float threshold, int res, size_t n);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {

@@ -809,6 +809,82 @@ extern "C" int32_t nz_watershed_batch(nz_ctx *ctx, const float *height, int32_t 
 }
 
 // ---------------------------------------------------------------------------------------------
+// stream order: Strahler order and river links (new-framework feature, include/noize_hip.h, nz_stream_order.hip)
+// ---------------------------------------------------------------------------------------------
+// `work` is laid out as the watershed's: 16 status words, two generations of per-tile bytes, then one channel-donor byte
+// per cell and the second order plane of one byte per cell (each rounded up to 16 bytes) and, with links, the second link
+// plane of count * res^2 int32; the first planes are the caller's `order` and `link`.
+namespace {
+constexpr int STREAM_ORDER_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "stream order"
+std::atomic<int> stream_order_sweeps{STREAM_ORDER_SWEEPS};  // nz_debug_stream_order_sweeps may be called while a thread runs an entry
+struct stream_order_layout {
+    fill_layout f;
+    size_t byte_floats;  // one byte plane in floats
+    size_t total(bool with_links) const { return FILL_STATUS + 2 * f.gen_floats + 2 * byte_floats + (with_links ? f.n : 0); }
+};
+stream_order_layout stream_order_layout_of(int res, int count) {
+    const fill_layout f = fill_layout_of(res, count);
+    return stream_order_layout{f, (f.n + 15) / 16 * 4};
+}
+}  // namespace
+
+extern "C" size_t nz_stream_order_work_floats(int32_t resolution, int32_t count, int32_t withLinks) {
+    return resolution > 0 && count > 0 ? stream_order_layout_of(resolution, count).total(withLinks != 0) : 0;
+}
+
+extern "C" int32_t nz_debug_stream_order_sweeps(int32_t sweeps) {
+    return stream_order_sweeps.exchange(sweeps > 0 ? sweeps : STREAM_ORDER_SWEEPS);
+}
+
+static int32_t stream_order_impl(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,
+                                 const nz_stream_order_desc *d, int res, int count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(order, "order is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(std::isfinite(d->threshold), "threshold is not finite");
+    NZ_REQUIRE(!std::isnan(d->seaLevel), "seaLevel is NaN");
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    const stream_order_layout L = stream_order_layout_of(res, count);
+    const size_t n = L.f.n;
+    NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
+    const float *links = reinterpret_cast<const float *>(link);  // a plane of n 4-byte cells
+    const nz_named_plane writes[] = {{"link", links, n}, {"work", work, L.total(link != nullptr)}};
+    const nz_named_plane reads[] = {{"height", height, n}, {"drainage", d->drainage, n}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    for (const auto &p : {reads[0], reads[1], writes[0], writes[1]})  // the order plane is bytes, not floats
+        NZ_REQUIRE(!nz_bytes_overlap(order, n, p.p, p.floats * sizeof(float)), "order overlaps %s", p.name);
+    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
+    unsigned char *donors = reinterpret_cast<unsigned char *>(c.planes);
+    unsigned char *orders[2] = {order, reinterpret_cast<unsigned char *>(c.planes + L.byte_floats)};
+    int *links2[2] = {link, link ? reinterpret_cast<int *>(c.planes + 2 * L.byte_floats) : nullptr};
+    const int sweeps = stream_order_sweeps.load();  // one cap for the whole series
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_stream_mask(ctx->stream, height, d->drainage, donors, order, d->seaLevel, d->threshold, res, count));
+    for (int p = 0; p < d->maxPasses; p++)  // pass p reads plane p & 1 and writes the other, and byte generation p & 1
+        NZ_TRY(nz_launch_stream_pass(ctx->stream, donors, orders[p & 1], orders[(p + 1) & 1], p ? links2[p & 1] : nullptr,
+                                     links2[(p + 1) & 1], c.status, c.flags[(p - 1) & 1], c.flags[p & 1], res, count, p, sweeps));
+    nz_ctx_arm_last_launch(ctx);
+    // a series at rest holds the fixed point in both planes of a pair, so the caller's have it whichever was written last
+    NZ_TRY(nz_launch_stream_finalise(ctx->stream, order, link, d->drainage, c.status, d->threshold, res, n));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_stream_order(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,
+                                   const nz_stream_order_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out) {
+    return stream_order_impl(ctx, height, order, link, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_stream_order_batch(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,
+                                         const nz_stream_order_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                                         nz_handle *out) {
+    return stream_order_impl(ctx, height, order, link, work, desc, resolution, count, dep, out);
+}
+
+// ---------------------------------------------------------------------------------------------
 // upsample / downsample (new-framework feature, include/noize_hip.h, nz_resample.hip)
 // ---------------------------------------------------------------------------------------------
 static int32_t check_resample(int32_t factor, int32_t filter) {

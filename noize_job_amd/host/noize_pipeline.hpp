@@ -1033,6 +1033,72 @@ class WatershedStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, labels, lengths, codes;
 };
 
+// Stream order (new-framework feature; the model: nz_stream_order in include/noize_hip.h): the channel cells of the
+// payload's heights, their Strahler order and the unbranched reaches between heads and confluences.  The heights pass
+// through untouched.  Once the handle completes, order() holds one byte per cell of the last payload (0: no channel,
+// 1: a head reach, +1 where two reaches of the same order meet) and links() the cell index, inside the cell's own tile, of
+// the head or confluence its reach starts at (cells() int32, -1: no channel); passes() and converged() wait for the handle
+// and read the status words.  seaLevel: cells at or below it are outlets like the border (-FLT_MAX: off).  drainage: a
+// device plane of the payload's size the caller supplies and keeps alive, the one DrainageAreaStage's `out` received; a
+// cell is a channel cell when its drainage >= threshold; nullptr: every cell is one.  maxPasses < 1 means the default,
+// 64 + resolution / 4; a budget that runs out is no error: converged() is false, order is 1 on channel cells and every
+// channel cell is its own link.  recordLinks: carry the link plane.  Strahler streams, as opposed to links, are the
+// caller's to derive from the two planes.
+class StreamOrderStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    float seaLevel = -3.402823466e+38f, threshold = 0.f;
+    int maxPasses = 0;  // < 1: 64 + resolution / 4
+    const DeviceTile *drainage = nullptr;
+    bool recordLinks = false;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        if (drainage && drainage->Length != cells())  // before any launch
+            throw std::runtime_error("StreamOrderStage: drainage does not fit the payload");
+        // sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        const size_t need = nz_stream_order_work_floats(resolution, count, recordLinks ? 1 : 0);
+        if (!work || work->Length != need) work.reset(new DeviceTile(ctx, need));
+        const size_t orderFloats = (cells() + 3) / 4;  // one byte per cell
+        if (!orders || orders->Length != orderFloats) orders.reset(new DeviceTile(ctx, orderFloats));
+        if (!recordLinks) linkPlane.reset();
+        else if (!linkPlane || linkPlane->Length != cells()) linkPlane.reset(new DeviceTile(ctx, cells()));
+        const nz_stream_order_desc desc{seaLevel, threshold, maxPasses >= 1 ? maxPasses : 64 + resolution / 4,
+                                        drainage ? drainage->ptr : nullptr};
+        uint8_t *o = reinterpret_cast<uint8_t *>(orders->ptr);
+        int32_t *l = linkPlane ? reinterpret_cast<int32_t *>(linkPlane->ptr) : nullptr;
+        nz_handle h = 0;
+        if (auto *bd = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_stream_order_batch(ctx, bd->data->ptr, o, l, work->ptr, &desc, bd->resolution, bd->count, dependency.id, &h),
+                  "nz_stream_order_batch");
+        } else {
+            check(nz_stream_order(ctx, d->data->ptr, o, l, work->ptr, &desc, d->resolution, dependency.id, &h), "nz_stream_order");
+        }
+        jobHandle = done(h);
+    }
+    const uint8_t *order() const { return orders ? reinterpret_cast<const uint8_t *>(orders->ptr) : nullptr; }  // nullptr before a payload
+    const int32_t *links() const { return linkPlane ? reinterpret_cast<const int32_t *>(linkPlane->ptr) : nullptr; }
+    size_t cells() const { return (size_t)count * resolution * resolution; }
+    int passes() const { return status(0); }                // -1 before the first run
+    bool converged() const { return status(1) == 1; }
+    void OnDestroy() override { work.reset(); orders.reset(); linkPlane.reset(); }
+
+  private:
+    int status(int k) const {
+        if (!work) return -1;
+        jobHandle.Complete();
+        int32_t words[2];
+        check(nz_tile_download(ctx, work->ptr, reinterpret_cast<float *>(words), 2, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[k];
+    }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, orders, linkPlane;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

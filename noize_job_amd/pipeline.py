@@ -1248,6 +1248,115 @@ class WatershedStage(PipelineStage):
         self.DisposeArrays()
 
 
+class StreamOrderStage(PipelineStage):
+    """Stream order (new-framework feature; the model is the comment block of nz_stream_order in include/noize_hip.h): the
+    channel cells of the payload's heights, their Strahler order and the unbranched reaches between heads and confluences.
+    The heights pass through untouched.  Once the stage's handle completes, `order` holds one byte per cell of the last
+    payload (0: no channel, 1: a head reach, +1 where two reaches of the same order meet) and `links` the cell index, inside
+    the cell's own tile, of the head or confluence its reach starts at (int32, -1: no channel); `passes` and `converged` are
+    the status words of that run.  Strahler streams, reaches joined across confluences that keep the order, are the
+    caller's to derive from the two planes.
+
+    seaLevel: cells at or below it are outlets like the border cells (the default, -FLT_MAX, switches it off).  drainage: a
+    device plane of the payload's size the caller supplies and keeps alive, the one DrainageAreaStage(out=...) wrote; a
+    cell is a channel cell when its drainage >= threshold.  Without it every cell is one and threshold is not compared.
+    maxPasses: the number of pass launches; None means 64 + resolution // 4.  A budget that runs out is no error: converged
+    is False, order is 1 on channel cells and every channel cell is its own link.  recordLinks: carry the link plane."""
+
+    SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+
+    def __init__(self, ctx, seaLevel=SEA_OFF, threshold=0.0, maxPasses=None, drainage=None, recordLinks=False):
+        super().__init__(ctx)
+        self.seaLevel = seaLevel
+        self.threshold = threshold
+        self.maxPasses = maxPasses
+        self.drainage = drainage
+        self.recordLinks = recordLinks
+        self.resolution = 0
+        self.count = 0
+        self.work = None    # nz_stream_order_work_floats floats; its first two int32: {passes, converged}
+        self._order = None  # the order plane: count * resolution^2 bytes
+        self._links = None  # the link plane (recordLinks): count * resolution^2 cells of 4 bytes
+
+    def DisposeArrays(self):
+        for t in (self.work, self._order, self._links):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.work = self._order = self._links = None
+
+    @property
+    def order(self):
+        """The Strahler orders of the last run (uint8), or None before the first payload and after OnDestroy."""
+        return self._order
+
+    @property
+    def links(self):
+        """The links of the last run as int32, or None: without recordLinks, before the first payload and after
+        OnDestroy."""
+        if self._links is None:
+            return None
+        return self.ctx.wrap(self._links.ptr, self._links.Length, dtype=np.int32)
+
+    def _status(self):
+        if self.work is None:
+            return None
+        self.jobHandle.Complete()
+        return self.ctx.wrap(self.work.ptr, 2, dtype=np.int32).ToArray()
+
+    @property
+    def passes(self):
+        """Passes of the last run that did work (the launches after them returned at once); None before the first run."""
+        s = self._status()
+        return None if s is None else int(s[0])
+
+    @property
+    def converged(self):
+        """Whether the last run reached the fixed point within maxPasses; None before the first run."""
+        s = self._status()
+        return None if s is None else bool(s[1])
+
+    def _size(self, tile, want, n, dtype=np.float32):
+        """A plane of the stage: n cells when wanted, resized with the payload, disposed of when not."""
+        if tile is not None and (not want or tile.Length != n):
+            tile.Dispose()
+            tile = None
+        if want and tile is None:
+            tile = self.ctx.alloc(n, dtype=dtype)
+        return tile
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        n = self.count * self.resolution * self.resolution
+        if self.drainage is not None:  # before any launch: a device tile of the payload's size, nothing else
+            have = getattr(self.drainage, "Length", None)
+            if not hasattr(self.drainage, "ptr") or have != n or getattr(self.drainage, "dtype", np.float32) != np.float32:
+                raise ValueError("StreamOrderStage.drainage must be a device tile of %d floats, the payload's size (it holds %s)"
+                                 % (n, have))
+        # sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        need = N.lib.nz_stream_order_work_floats(self.resolution, self.count, 1 if self.recordLinks else 0)
+        if self.work is None or self.work.Length != need:
+            if self.work is not None and self.work.IsCreated:
+                self.work.Dispose()
+            self.work = self.ctx.alloc(need)
+        self._order = self._size(self._order, True, n, np.uint8)
+        self._links = self._size(self._links, bool(self.recordLinks), n)
+        budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
+        desc = N.StreamOrderDesc(self.seaLevel, self.threshold, budget, self.drainage.ptr if self.drainage is not None else None)
+        planes = (self._order.ptr, self._links.ptr if self._links is not None else None, self.work.ptr)
+        if isinstance(d, GeneratorDataBatch):
+            self.jobHandle = self.ctx.call("nz_stream_order_batch", d.data.ptr, *planes, C.byref(desc), d.resolution, d.count,
+                                           dep=dependency)
+        else:
+            self.jobHandle = self.ctx.call("nz_stream_order", d.data.ptr, *planes, C.byref(desc), d.resolution, dep=dependency)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
     def __init__(self, ctx, meshType=MeshType.SquareGridHeightMap):
         super().__init__(ctx)
