@@ -11,9 +11,9 @@
 // topological walk -- ends in the same floats.  No monotonicity is needed (a rain map may be negative), only that a test
 // "nothing changed" looks at every single update: see `relax` below.
 //
-// The mask launch, once per call, on the geometry of nz_tile64.hpp (16-byte accesses where planes and pitch allow):
-// heights at radius 2 into LDS, receiver codes at radius 1, and per own cell one DONOR BYTE -- bit k set when neighbour k
-// exists and its receiver is the direction opposite to k.  After it no launch looks at a height.
+// The mask launch, once per call, on the geometry of nz_tile64.hpp (16-byte accesses where planes and pitch allow), is
+// nz_donor_front.hpp's: heights at radius 2 into LDS, receiver codes at radius 1, and per own cell one DONOR BYTE -- bit k
+// set when neighbour k exists and its receiver is the direction opposite to k.  After it no launch looks at a height.
 //
 // One launch per PASS of A, by the pass protocol of nz_relax_pass.hpp -- gate, tile skip, sweeps against a frozen ring,
 // the closing byte and word, and the argument for them; the caller's `drainage` is plane 0.  What is this stage's own:
@@ -40,126 +40,26 @@
 #include "nz_receiver.hpp"
 #include "nz_relax_pass.hpp"
 #include "nz_tile64.hpp"
+#include "nz_donor_front.hpp"
 
 namespace {
 
-// WIN: the owned rows of one stripe-shaped buffer, rows in buffer coordinates; the pitch travels as the kernels' `res`
-struct drain_win {
-    int xhi;                // last column of the grid
-    int zlo, zhi;           // first and last row of the global grid
-    int r0, r1;             // owned rows [r0, r1)
+// WIN: the owned rows of one stripe-shaped buffer (nz_front::win_rows) and what the passes of a round need beside them
+struct drain_win : nz_front::win_rows {
     int ghost_from_rain;    // the frozen rows are the start state rain_c (a round with `first`), else the caller's plane's
     int *status;            // the round's status words (the mask launch reads status[GO])
     int *changed_out;       // the caller's word
 };
 
-using nz_recv::NONE;
-using nz_recv::receiver;
-using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, halo2_cell
+using namespace nz_tile64;  // the tile, its LDS layout, ring_cell
 using namespace nz_relax;   // the status words and the pass protocol
 
-// ---- the mask launch: heights -> donor bytes ----
-// VEC: 16-byte height reads; WORD: the four donor bytes of a thread as one 32-bit store (res % 4 == 0)
-// WIN: res is the pitch; heights are read on the rows within 2 of the owned ones, donor bytes stored for the owned rows,
-// at the cell's index in the plane
+// ---- the mask launch: heights -> donor bytes (nz_donor_front.hpp, no channel predicate) ----
 template <bool VEC, bool WORD, bool WIN>
 __global__ __launch_bounds__(FT) void drainage_mask_kernel(const float *__restrict__ h, unsigned char *__restrict__ donors,
                                                            float sea, int res, drain_win win) {
-    __shared__ __attribute__((aligned(16))) float H[(FZ + 4) * LP];          // radius 2: LDS row = plane row - z0 + 2
-    __shared__ __attribute__((aligned(16))) unsigned RW[(FZ + 2) * LP / 4];  // radius 1, one byte per cell
-    unsigned char *RC = reinterpret_cast<unsigned char *>(RW);
-
-    const int tid = threadIdx.x;
-    if constexpr (WIN) {
-        if (!win.status[ST_GO]) return;
-    }
-    const int x0 = blockIdx.x * FX, z0 = (WIN ? win.r0 : 0) + blockIdx.y * FZ;
-    const size_t base = WIN ? 0 : (size_t)blockIdx.z * res * res;
-    const int hi = WIN ? win.xhi : res - 1;                            // last column
-    const int zlo = WIN ? win.zlo : 0, zhi = WIN ? win.zhi : res - 1;  // the grid's rows
-    const int rlo = WIN ? (zlo > win.r0 - 2 ? zlo : win.r0 - 2) : 0, rhi = WIN ? (zhi < win.r1 + 1 ? zhi : win.r1 + 1) : hi;  // rows read
-    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= rlo && pz <= rhi; };
-    auto on_border = [&](int px, int pz) { return px == 0 || px == hi || pz == zlo || pz == zhi; };
-
-    const int tz = tid >> 4, tx = (tid & 15) * 4;
-    const int px = x0 + tx, pz = z0 + tz;
-    const size_t c0 = base + (size_t)pz * res + px;
-    const bool row_in = pz <= rhi;  // WIN: the two rows below the owned ones lie in own slots when the tile reaches them
-    const bool quad = row_in && px + 3 <= hi;
-
-    // ---- fill: a cell outside the grid reads as +0 and is never looked at ----
-    float hc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (VEC && quad) {
-        const float4 v = *reinterpret_cast<const float4 *>(h + c0);
-        hc[0] = v.x, hc[1] = v.y, hc[2] = v.z, hc[3] = v.w;
-    } else if (!VEC && row_in) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (px + j > hi) break;
-            hc[j] = h[c0 + j];
-        }
-    }
-    *reinterpret_cast<float4 *>(&H[(tz + 2) * LP + LC + tx]) = make_float4(hc[0], hc[1], hc[2], hc[3]);
-    for (int i = tid; i < NHALO2; i += FT) {  // the heights at radius 1 and 2
-        int lz, lx;
-        halo2_cell(i, lz, lx);
-        const int qx = x0 + lx - LC, qz = z0 + lz - 2;
-        H[lz * LP + lx] = inside(qx, qz) ? h[base + (size_t)qz * res + qx] : 0.0f;
-    }
-    __syncthreads();
-
-    // ---- receivers at radius 1: NONE for an outlet and for a cell outside the grid ----
-    {
-        float w[3][6];  // rows pz-1 .. pz+1, columns px-1 .. px+4
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const float *row = &H[(tz + 1 + r) * LP + LC + tx];
-            const float4 v = *reinterpret_cast<const float4 *>(row);
-            w[r][0] = row[-1], w[r][1] = v.x, w[r][2] = v.y, w[r][3] = v.z, w[r][4] = v.w, w[r][5] = row[4];
-        }
-        unsigned codes = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float s, d;
-            unsigned r = receiver(w[1][j + 1], w[1][j], w[1][j + 2], w[0][j + 1], w[2][j + 1], w[0][j], w[0][j + 2], w[2][j],
-                                  w[2][j + 2], s, d);
-            if (!inside(px + j, pz) || on_border(px + j, pz) || w[1][j + 1] <= sea) r = NONE;
-            codes |= r << (8 * j);
-        }
-        RW[((tz + 1) * LP + LC + tx) >> 2] = codes;
-    }
-    if (tid < NRING) {
-        int lz, lx;
-        ring_cell(tid, lz, lx);
-        const int qx = x0 + lx - LC, qz = z0 + lz - 1;
-        unsigned r = NONE;
-        if (inside(qx, qz) && !on_border(qx, qz)) {
-            const float *row = &H[(lz + 1) * LP + lx];
-            float s, d;
-            if (!(row[0] <= sea))
-                r = receiver(row[0], row[-1], row[1], row[-LP], row[LP], row[-LP - 1], row[-LP + 1], row[LP - 1], row[LP + 1], s,
-                             d);
-        }
-        RC[lz * LP + lx] = (unsigned char)r;
-    }
-    __syncthreads();
-
-    // ---- the donor bytes of the own cells ----
-    if (!(WIN ? pz < win.r1 : row_in) || px > hi) return;
-    unsigned cw[3][6];  // the receiver codes of the window
-    window_bytes(RW, tz, tx, cw);
-    unsigned word = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) word |= nz_recv::donor_mask(cw, j) << (8 * j);
-    if (WORD && quad) {
-        *reinterpret_cast<unsigned *>(donors + c0) = word;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (px + j > hi) break;
-            donors[c0 + j] = (unsigned char)(word >> (8 * j));
-        }
-    }
+    if (WIN && !win.status[ST_GO]) return;
+    nz_front::donor_front<VEC, WORD, WIN, false>(h, nullptr, donors, nullptr, sea, 0.0f, res, win);
 }
 
 // ---- a pass ----
@@ -372,24 +272,13 @@ int32_t nz_launch_drainage_stripe_mask(hipStream_t s, const float *h, unsigned c
     const dim3 grid(tiles_x(g.cols), tiles_z(g.or1 - g.or0), 1);
     const bool word = g.cols % 4 == 0 && g.pitch % 4 == 0 && (reinterpret_cast<uintptr_t>(donors) & 3) == 0;
     const bool vec = word && (reinterpret_cast<uintptr_t>(h) & 15) == 0;  // every row starts 16-byte aligned
-    const drain_win win{g.cols - 1, zlo, zhi, g.or0, g.or1, 0, status, nullptr};
+    const drain_win win{{g.cols - 1, zlo, zhi, g.or0, g.or1}, 0, status, nullptr};
     if (vec) NZ_LAUNCH((drainage_mask_kernel<true, true, true>), grid, dim3(FT), 0, s, h, donors, sea, g.pitch, win);
     else if (word) NZ_LAUNCH((drainage_mask_kernel<false, true, true>), grid, dim3(FT), 0, s, h, donors, sea, g.pitch, win);
     else NZ_LAUNCH((drainage_mask_kernel<false, false, true>), grid, dim3(FT), 0, s, h, donors, sea, g.pitch, win);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
-
-namespace {
-// the form of a pass by <FIRST, VEC, MAP, WIN>
-template <bool FIRST, bool VEC, bool WIN>
-void launch_pass(bool map, dim3 grid, hipStream_t s, const unsigned char *donors, const float *rain_map, const float *a_in,
-                 float *a_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain, int res,
-                 int pass, int sweeps, const drain_win &win) {
-    if (map) NZ_LAUNCH((drainage_pass_kernel<FIRST, VEC, true, WIN>), grid, dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, win);
-    else NZ_LAUNCH((drainage_pass_kernel<FIRST, VEC, false, WIN>), grid, dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, win);
-}
-}  // namespace
 
 int32_t nz_launch_drainage_pass(hipStream_t s, const unsigned char *donors, const float *rain_map, const float *a_in,
                                 float *a_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain,
@@ -399,14 +288,10 @@ int32_t nz_launch_drainage_pass(hipStream_t s, const unsigned char *donors, cons
     const uintptr_t bits = reinterpret_cast<uintptr_t>(rain_map) | reinterpret_cast<uintptr_t>(a_in) |
                            reinterpret_cast<uintptr_t>(a_out) | reinterpret_cast<uintptr_t>(donors);
     const bool vec = (bits & 15) == 0 && res % 4 == 0;  // a row, and with it a tile of the batch, starts 16-byte aligned
-    const bool map = rain_map != nullptr;
-    if (pass == 0) {
-        if (vec) launch_pass<true, true, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
-        else launch_pass<true, false, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
-    } else {
-        if (vec) launch_pass<false, true, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
-        else launch_pass<false, false, false>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
-    }
+    nz_with_bools([&](auto first, auto v, auto map) {
+        NZ_LAUNCH((drainage_pass_kernel<decltype(first)::value, decltype(v)::value, decltype(map)::value, false>), grid,
+                  dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, res, pass, sweeps, NO_WIN);
+    }, pass == 0, vec, rain_map != nullptr);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }
@@ -420,15 +305,11 @@ int32_t nz_launch_drainage_stripe_pass(hipStream_t s, const unsigned char *donor
     const uintptr_t bits = reinterpret_cast<uintptr_t>(rain_map) | reinterpret_cast<uintptr_t>(a_in) |
                            reinterpret_cast<uintptr_t>(a_out) | reinterpret_cast<uintptr_t>(donors);
     const bool vec = (bits & 15) == 0 && g.cols % 4 == 0 && g.pitch % 4 == 0;  // every row starts 16-byte aligned
-    const bool map = rain_map != nullptr;
-    const drain_win win{g.cols - 1, zlo, zhi, g.or0, g.or1, first, status, changed};
-    if (first && pass == 0) {
-        if (vec) launch_pass<true, true, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
-        else launch_pass<true, false, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
-    } else {
-        if (vec) launch_pass<false, true, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
-        else launch_pass<false, false, true>(map, grid, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
-    }
+    const drain_win win{{g.cols - 1, zlo, zhi, g.or0, g.or1}, first, status, changed};
+    nz_with_bools([&](auto start, auto v, auto map) {
+        NZ_LAUNCH((drainage_pass_kernel<decltype(start)::value, decltype(v)::value, decltype(map)::value, true>), grid,
+                  dim3(FT), 0, s, donors, rain_map, a_in, a_out, status, flags_in, flags_out, rain, g.pitch, pass, sweeps, win);
+    }, first && pass == 0, vec, rain_map != nullptr);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

@@ -251,6 +251,17 @@ inline void nz_with_unit_fast(const nz_kernel_taps &k, F &&f) {
         if (fast) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type());
     }
 }
+// the 2^n instantiations of a kernel with n bool template arguments: calls f with each run-time bool as a std::true_type or
+// std::false_type argument, in the order given (the kernel's argument is then `decltype(x)::value`)
+template <class F, class... Bools>
+inline void nz_with_bools(F &&f, Bools... picked) {
+    f(picked...);
+}
+template <class F, class... Rest>
+inline void nz_with_bools(F &&f, bool b, Rest... rest) {
+    if (b) nz_with_bools(f, rest..., std::true_type());
+    else nz_with_bools(f, rest..., std::false_type());
+}
 void nz_ctx_handle_rides(nz_ctx *ctx, bool wanted);
 void nz_ctx_arm_last_launch(nz_ctx *ctx);
 

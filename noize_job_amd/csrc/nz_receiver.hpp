@@ -1,6 +1,7 @@
 // nz_receiver.hpp -- the receiver rule of the drainage network, stated once: step 1 of the fluvial model
-// (include/noize_hip.h).  nz_fluvial.hip erodes along it, nz_drainage.hip accumulates down it; both include this file, so
-// the two cannot drift apart.
+// (include/noize_hip.h).  nz_fluvial.hip erodes along it, nz_drainage.hip accumulates down it, nz_watershed.hip labels and
+// measures along it, nz_stream_order.hip orders the channels among it -- the last three through nz_donor_front.hpp; all
+// include this file, so they cannot drift apart.
 #pragma once
 
 namespace nz_recv {
@@ -29,7 +30,7 @@ __device__ __forceinline__ unsigned receiver(float c, float w, float e, float s,
 }
 
 // The donors of own cell j against the receiver codes cw of the thread's 3 x 6 window: bit k set when neighbour k drains
-// here, that is when its receiver is the direction opposite to k -- E W N S NE NW SE SW.  nz_drainage.hip stores the mask;
+// here, that is when its receiver is the direction opposite to k -- E W N S NE NW SE SW.  nz_donor_front.hpp stores the mask;
 // nz_fluvial.hip's gather keeps the same eight comparisons written out, which leaves its code object as it was.
 __device__ __forceinline__ unsigned donor_mask(const unsigned (&cw)[3][6], int j) {
     unsigned m = 0;

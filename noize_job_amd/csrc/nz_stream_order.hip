@@ -17,7 +17,8 @@
 // function that is monotone in every donor, so a series that starts at 1 never passes the fixed point and a byte holds
 // every value on the way (the entry refuses 2^31 cells: order <= 31).
 //
-// The mask launch, once per call, on the geometry of nz_tile64.hpp (16-byte accesses where planes and pitch allow):
+// The mask launch, once per call, on the geometry of nz_tile64.hpp (16-byte accesses where planes and pitch allow), is
+// nz_donor_front.hpp's with the channel predicate on:
 // heights at radius 2 into LDS, receiver codes at radius 1 with ch folded in -- a cell that is no channel gets the code
 // NONE, it donates to nothing -- and per own cell one CHANNEL-DONOR BYTE: bit k set when neighbour k exists, drains into the
 // cell and is a channel cell.  `drainage` is read at radius 1 only.  The start state of `order`, ch ? 1 : 0, goes into
@@ -43,121 +44,20 @@
 #include "nz_receiver.hpp"
 #include "nz_relax_pass.hpp"
 #include "nz_tile64.hpp"
+#include "nz_donor_front.hpp"
 
 namespace {
 
-using nz_recv::NONE;
-using nz_recv::receiver;
-using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, halo2_cell, window_bytes
+using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, window_bytes, neighbour_lds
 using namespace nz_relax;   // the status words and the pass protocol
 
-// ---- the mask launch: heights and drainage -> channel-donor bytes and the start state of `order` ----
-// VEC: 16-byte height and drainage reads; WORD: the four bytes of a thread as one 32-bit store (res % 4 == 0)
+// ---- the mask launch: heights and drainage -> channel-donor bytes and the start state of `order` (nz_donor_front.hpp,
+// with the channel predicate) ----
 template <bool VEC, bool WORD>
 __global__ __launch_bounds__(FT) void stream_mask_kernel(const float *__restrict__ h, const float *__restrict__ drainage,
                                                          unsigned char *__restrict__ donors, unsigned char *__restrict__ order,
                                                          float sea, float threshold, int res) {
-    __shared__ __attribute__((aligned(16))) float H[(FZ + 4) * LP];          // radius 2: LDS row = plane row - z0 + 2
-    __shared__ __attribute__((aligned(16))) unsigned RW[(FZ + 2) * LP / 4];  // radius 1, one byte per cell
-    unsigned char *RC = reinterpret_cast<unsigned char *>(RW);
-
-    const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * FX, z0 = blockIdx.y * FZ;
-    const size_t base = (size_t)blockIdx.z * res * res;
-    const int hi = res - 1;  // last column and row
-    const bool all = drainage == nullptr;  // every cell is a channel cell
-    auto inside = [&](int px, int pz) { return px >= 0 && px <= hi && pz >= 0 && pz <= hi; };
-    auto on_border = [&](int px, int pz) { return px == 0 || px == hi || pz == 0 || pz == hi; };
-
-    const int tz = tid >> 4, tx = (tid & 15) * 4;
-    const int px = x0 + tx, pz = z0 + tz;
-    const size_t c0 = base + (size_t)pz * res + px;
-    const bool row_in = pz <= hi;
-    const bool quad = row_in && px + 3 <= hi;
-
-    // ---- fill: a cell outside the grid reads as +0 and is never looked at; it is no channel ----
-    float hc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    unsigned chw = 0;  // ch of the own cells, one byte each: the start state of their order
-    if (VEC && quad) {
-        const float4 v = *reinterpret_cast<const float4 *>(h + c0);
-        hc[0] = v.x, hc[1] = v.y, hc[2] = v.z, hc[3] = v.w;
-        chw = 0x01010101u;
-        if (!all) {
-            const float4 a = *reinterpret_cast<const float4 *>(drainage + c0);
-            chw = (unsigned)(a.x >= threshold) | (unsigned)(a.y >= threshold) << 8 | (unsigned)(a.z >= threshold) << 16 |
-                  (unsigned)(a.w >= threshold) << 24;
-        }
-    } else if (!VEC && row_in) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (px + j > hi) break;
-            hc[j] = h[c0 + j];
-            chw |= (unsigned)(all || drainage[c0 + j] >= threshold) << (8 * j);
-        }
-    }
-    *reinterpret_cast<float4 *>(&H[(tz + 2) * LP + LC + tx]) = make_float4(hc[0], hc[1], hc[2], hc[3]);
-    for (int i = tid; i < NHALO2; i += FT) {  // the heights at radius 1 and 2
-        int lz, lx;
-        halo2_cell(i, lz, lx);
-        const int qx = x0 + lx - LC, qz = z0 + lz - 2;
-        H[lz * LP + lx] = inside(qx, qz) ? h[base + (size_t)qz * res + qx] : 0.0f;
-    }
-    __syncthreads();
-
-    // ---- receivers at radius 1: NONE for an outlet, for a cell outside the grid and for a cell that is no channel ----
-    {
-        float w[3][6];  // rows pz-1 .. pz+1, columns px-1 .. px+4
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const float *row = &H[(tz + 1 + r) * LP + LC + tx];
-            const float4 v = *reinterpret_cast<const float4 *>(row);
-            w[r][0] = row[-1], w[r][1] = v.x, w[r][2] = v.y, w[r][3] = v.z, w[r][4] = v.w, w[r][5] = row[4];
-        }
-        unsigned codes = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float s, d;
-            unsigned r = receiver(w[1][j + 1], w[1][j], w[1][j + 2], w[0][j + 1], w[2][j + 1], w[0][j], w[0][j + 2], w[2][j],
-                                  w[2][j + 2], s, d);
-            if (!((chw >> (8 * j)) & 1u) || on_border(px + j, pz) || w[1][j + 1] <= sea) r = NONE;  // (chw: inside, too)
-            codes |= r << (8 * j);
-        }
-        RW[((tz + 1) * LP + LC + tx) >> 2] = codes;
-    }
-    if (tid < NRING) {
-        int lz, lx;
-        ring_cell(tid, lz, lx);
-        const int qx = x0 + lx - LC, qz = z0 + lz - 1;
-        unsigned r = NONE;
-        if (inside(qx, qz) && !on_border(qx, qz)) {
-            const float *row = &H[(lz + 1) * LP + lx];
-            float s, d;
-            if (!(row[0] <= sea) && (all || drainage[base + (size_t)qz * res + qx] >= threshold))
-                r = receiver(row[0], row[-1], row[1], row[-LP], row[LP], row[-LP - 1], row[-LP + 1], row[LP - 1], row[LP + 1], s,
-                             d);
-        }
-        RC[lz * LP + lx] = (unsigned char)r;
-    }
-    __syncthreads();
-
-    // ---- the channel-donor bytes and the start state of the own cells ----
-    if (!row_in || px > hi) return;
-    unsigned cw[3][6];  // the receiver codes of the window
-    window_bytes(RW, tz, tx, cw);
-    unsigned word = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) word |= nz_recv::donor_mask(cw, j) << (8 * j);
-    if (WORD && quad) {
-        *reinterpret_cast<unsigned *>(donors + c0) = word;
-        *reinterpret_cast<unsigned *>(order + c0) = chw;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (px + j > hi) break;
-            donors[c0 + j] = (unsigned char)(word >> (8 * j));
-            order[c0 + j] = (unsigned char)(chw >> (8 * j));
-        }
-    }
+    nz_front::donor_front<VEC, WORD, false, true>(h, drainage, donors, order, sea, threshold, res, nz_front::win_rows{});
 }
 
 // ---- a pass ----
@@ -255,10 +155,7 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_num_sgpr(102))) void stre
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const unsigned d = (don >> (8 * j)) & 255u;
-            const int k = __popc(d) == 1 ? __ffs(d) - 1 : 8;
-            const int dx = k >= 8 || k == 2 || k == 3 ? 0 : (k & 1) ? 1 : -1;
-            const int dz = k >= 8 || k < 2 ? 0 : (k == 3 || k >= 6) ? 1 : -1;
-            at[j] = (tz + 1 + dz) * LP + LC + tx + j + dx;
+            at[j] = neighbour_lds(tz, tx, j, __popc(d) == 1 ? __ffs(d) - 1 : 8);
         }
     }
     __syncthreads();
@@ -360,17 +257,6 @@ int32_t nz_launch_stream_mask(hipStream_t s, const float *h, const float *draina
     return NZ_OK;
 }
 
-namespace {
-// the form of a pass by <FIRST, VEC, LINK>
-template <bool FIRST, bool VEC>
-void launch_pass(bool link, dim3 grid, hipStream_t s, const unsigned char *donors, const unsigned char *o_in,
-                 unsigned char *o_out, const int *l_in, int *l_out, int *status, const unsigned char *flags_in,
-                 unsigned char *flags_out, int res, int pass, int sweeps) {
-    if (link) NZ_LAUNCH((stream_pass_kernel<FIRST, VEC, true>), grid, dim3(FT), 0, s, donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
-    else NZ_LAUNCH((stream_pass_kernel<FIRST, VEC, false>), grid, dim3(FT), 0, s, donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
-}
-}  // namespace
-
 int32_t nz_launch_stream_pass(hipStream_t s, const unsigned char *donors, const unsigned char *o_in, unsigned char *o_out,
                               const int *l_in, int *l_out, int *status, const unsigned char *flags_in,
                               unsigned char *flags_out, int res, int count, int pass, int sweeps) {
@@ -381,14 +267,10 @@ int32_t nz_launch_stream_pass(hipStream_t s, const unsigned char *donors, const 
     const uintptr_t ints = reinterpret_cast<uintptr_t>(l_in) | reinterpret_cast<uintptr_t>(l_out);
     // a row, and with it a tile of the batch, starts 4-byte aligned in the byte planes and 16-byte aligned in the links
     const bool vec = (bytes & 3) == 0 && (ints & 15) == 0 && res % 4 == 0;
-    const bool link = l_out != nullptr;
-    if (pass == 0) {
-        if (vec) launch_pass<true, true>(link, grid, s, donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
-        else launch_pass<true, false>(link, grid, s, donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
-    } else {
-        if (vec) launch_pass<false, true>(link, grid, s, donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
-        else launch_pass<false, false>(link, grid, s, donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
-    }
+    nz_with_bools([&](auto first, auto v, auto link) {
+        NZ_LAUNCH((stream_pass_kernel<decltype(first)::value, decltype(v)::value, decltype(link)::value>), grid, dim3(FT), 0, s,
+                  donors, o_in, o_out, l_in, l_out, status, flags_in, flags_out, res, pass, sweeps);
+    }, pass == 0, vec, l_out != nullptr);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

@@ -414,30 +414,89 @@ extern "C" int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float 
 // ---------------------------------------------------------------------------------------------
 // depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
 // ---------------------------------------------------------------------------------------------
-// `work` in floats: 16 status words (nz_relax_pass.hpp; the rest spare), two generations of per-tile bytes (nz_tile64.hpp),
-// each rounded up to 16 bytes, and the W planes the passes alternate between: both of them in the tile forms (count * res^2
-// floats each), one in the stripe form, whose other W plane is the caller's `w`.  One pass is one launch whatever its depth,
-// so the launch-series planner (nz_split_iterations) has nothing to split here.
+// The four stages that iterate to rest -- this one, drainage area, watershed, stream order -- share what follows.
+//
+// `work` in floats begins the same way for all of them: 16 status words (nz_relax_pass.hpp; the rest spare) and two
+// generations of per-tile bytes (nz_tile64.hpp); then come the stage's own byte planes (one byte per cell) and 4-byte
+// planes.  Bytes are rounded up to 16 per part.  relax_work lays the plane out by being asked for the parts in order;
+// run on a null base it yields the total alone, so a *_work_floats entry and the entry that carves are one sequence of
+// requests (the *_work_of functions) and cannot disagree.  One pass is one launch whatever its depth, so the launch-series
+// planner (nz_split_iterations) has nothing to split here.
 namespace {
-constexpr size_t FILL_STATUS = 16;
-constexpr int FILL_SWEEPS = 16;  // measured: DESIGN.md section 4
-std::atomic<int> fill_sweeps{FILL_SWEEPS};  // nz_debug_fill_sweeps may be called while another thread runs an entry
-struct fill_layout {
-    size_t gen_floats, n;  // one generation of tile bytes in floats, floats of one W plane
-    size_t total(int w_planes) const { return FILL_STATUS + 2 * gen_floats + w_planes * n; }
+struct relax_shape { size_t tiles, n; };  // the tiles of the call and the cells of one of its planes
+relax_shape tile_shape(int res, int count) {
+    return {(size_t)nz_tile64::tiles_x(res) * nz_tile64::tiles_z(res) * count, (size_t)res * res * count};
+}
+relax_shape stripe_shape(const nz_stripe &st) {  // the tiles cover the owned rows, a plane has the stripe's shape
+    return {(size_t)nz_tile64::tiles_x(st.cols) * nz_tile64::tiles_z(st.own1 - st.own0), nz_stripe_plane_floats(&st)};
+}
+bool stripe_has_work(const nz_stripe *st) { return nz_stripe_plane_floats(st) && st->own0 >= 0 && st->own1 >= st->own0; }
+
+struct relax_work {
+    float *base;
+    size_t total = 0;  // floats handed out so far; in the end, the size of `work`
+    int *status;
+    unsigned char *flags[2];
+    relax_work(float *work, const relax_shape &sh)
+        : base(work), status(ints(16)), flags{bytes(sh.tiles), bytes(sh.tiles)} {}
+    float *floats(size_t n) {
+        float *p = base ? base + total : nullptr;
+        total += n;
+        return p;
+    }
+    unsigned char *bytes(size_t n) { return reinterpret_cast<unsigned char *>(floats((n + 15) / 16 * 4)); }
+    int *ints(size_t n) { return reinterpret_cast<int *>(floats(n)); }
 };
-fill_layout fill_layout_of(int res, int count) {
-    const size_t tiles = (size_t)nz_tile64::tiles_x(res) * nz_tile64::tiles_z(res) * count;
-    return fill_layout{(tiles + 15) / 16 * 4, (size_t)res * res * count};
+
+// The sweep cap of a stage: 16 for each of the four (measured per stage, 4 to 64: DESIGN.md section 4).  The debug entry
+// may be called while another thread runs an entry; it returns the cap before, and a value < 1 puts the default back.
+constexpr int RELAX_SWEEPS = 16;
+struct sweep_cap {
+    std::atomic<int> cap{RELAX_SWEEPS};
+    int load() const { return cap.load(); }  // an entry reads it once: one cap for the whole series
+    int exchange(int sweeps) { return cap.exchange(sweeps > 0 ? sweeps : RELAX_SWEEPS); }
+};
+sweep_cap fill_sweeps, drainage_sweeps, watershed_sweeps, stream_order_sweeps;
+
+// One series on whole tiles: pass(p, flags_in, flags_out) launches pass p, which reads byte generation (p - 1) & 1 and
+// writes generation p & 1 -- which plane it reads and writes is the stage's business; finalise() launches last.
+template <class Pass, class Finalise>
+int32_t run_tile_series(nz_ctx *ctx, nz_handle *out, int maxPasses, const relax_work &hd, Pass pass, Finalise finalise) {
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    for (int p = 0; p < maxPasses; p++) NZ_TRY(pass(p, hd.flags[(p - 1) & 1], hd.flags[p & 1]));
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(finalise());
+    return nz_ctx_finish(ctx, out);
 }
-fill_layout fill_stripe_layout(const nz_stripe &st) {
-    const size_t tiles = (size_t)nz_tile64::tiles_x(st.cols) * nz_tile64::tiles_z(st.own1 - st.own0);
-    return fill_layout{(tiles + 15) / 16 * 4, nz_stripe_plane_floats(&st)};
+
+// One round on the owned rows of a stripe: the round's begin launch, mask() (a stage without one launches nothing),
+// `passes` times pass(p, plane_in, plane_out, flags_in, flags_out) -- pass p reads plane p & 1 and writes the other, plane
+// 0 the caller's -- and, when the last pass wrote the work plane, the round's end launch, which copies it back.
+template <class Mask, class Pass>
+int32_t run_stripe_round(nz_ctx *ctx, nz_handle *out, int passes, const relax_work &hd, float *callers, float *second,
+                         const int32_t *proceed, int32_t *changed, int32_t first, const nz_geom &g, Mask mask, Pass pass) {
+    float *planes[2] = {callers, second};
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    NZ_TRY(nz_launch_fill_round_begin(ctx->stream, hd.status, proceed, changed, first != 0));
+    NZ_TRY(mask());
+    for (int p = 0; p < passes; p++) {
+        if (p == passes - 1 && !(passes & 1)) nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(pass(p, planes[p & 1], planes[(p + 1) & 1], hd.flags[(p + 1) & 1], hd.flags[p & 1]));
+    }
+    if (passes & 1) {  // the last pass wrote the work plane
+        nz_ctx_arm_last_launch(ctx);
+        NZ_TRY(nz_launch_fill_round_end(ctx->stream, callers, second, hd.status, passes, g));
+    }
+    return nz_ctx_finish(ctx, out);
 }
-struct fill_work { int *status; unsigned char *flags[2]; float *planes; };  // planes: the first (or only) W plane of `work`
-fill_work fill_carve(float *work, const fill_layout &L) {
-    unsigned char *bytes = reinterpret_cast<unsigned char *>(work + FILL_STATUS);
-    return fill_work{reinterpret_cast<int *>(work), {bytes, bytes + 4 * L.gen_floats}, work + FILL_STATUS + 2 * L.gen_floats};
+
+// the fill's `work`: the head and the W planes the passes alternate between -- both of them in the tile forms, one in the
+// stripe form, whose other W plane is the caller's `w`
+struct fill_work { relax_work hd; float *w[2]; };
+fill_work fill_work_of(float *work, const relax_shape &sh, int w_planes) {
+    fill_work k{relax_work(work, sh), {}};
+    for (int i = 0; i < w_planes; i++) k.w[i] = k.hd.floats(sh.n);
+    return k;
 }
 }  // namespace
 
@@ -451,34 +510,32 @@ static int32_t check_fill_desc(const nz_fill_desc *d) {
 }
 
 extern "C" size_t nz_fill_depressions_work_floats(int32_t resolution, int32_t count) {
-    return resolution > 0 && count > 0 ? fill_layout_of(resolution, count).total(2) : 0;
+    return resolution > 0 && count > 0 ? fill_work_of(nullptr, tile_shape(resolution, count), 2).hd.total : 0;
 }
 
-extern "C" int32_t nz_debug_fill_sweeps(int32_t sweeps) {
-    return fill_sweeps.exchange(sweeps > 0 ? sweeps : FILL_SWEEPS);
-}
+extern "C" int32_t nz_debug_fill_sweeps(int32_t sweeps) { return fill_sweeps.exchange(sweeps); }
 
 // h: the plane that holds the input and receives the result; other: the write plane of an _rw pair or NULL
 static int32_t fill_impl(nz_ctx *ctx, float *h, const float *other, float *work, const nz_fill_desc *d, int res, int count,
                          nz_handle *out) {
     NZ_REQUIRE(h && work, "src/work is NULL");
     NZ_TRY(check_fill_desc(d));
-    const fill_layout L = fill_layout_of(res, count);
-    NZ_REQUIRE(!nz_planes_overlap(d->depth, L.n, h, L.n), "depth overlaps src");
-    NZ_REQUIRE(!nz_planes_overlap(d->depth, L.n, other, L.n), "depth overlaps the write plane");
-    NZ_REQUIRE(!nz_planes_overlap(d->depth, L.n, work, L.total(2)), "depth overlaps work");
-    const fill_work c = fill_carve(work, L);
-    float *planes[2] = {c.planes, c.planes + L.n};
+    const relax_shape sh = tile_shape(res, count);
+    const fill_work k = fill_work_of(work, sh, 2);
+    const size_t n = sh.n;
+    NZ_REQUIRE(!nz_planes_overlap(d->depth, n, h, n), "depth overlaps src");
+    NZ_REQUIRE(!nz_planes_overlap(d->depth, n, other, n), "depth overlaps the write plane");
+    NZ_REQUIRE(!nz_planes_overlap(d->depth, n, work, k.hd.total), "depth overlaps work");
     const float eps = d->epsilon + 0.0f;  // -0 -> +0
-    const int sweeps = fill_sweeps.load();  // one cap for the whole series
-    nz_ctx_handle_rides(ctx, out != nullptr);
-    for (int p = 0; p < d->maxPasses; p++)  // pass p writes plane p & 1 and byte generation p & 1
-        NZ_TRY(nz_launch_fill_pass(ctx->stream, h, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1], c.status,
-                                   c.flags[(p - 1) & 1], c.flags[p & 1], eps, d->seaLevel, res, count, p, sweeps));
-    nz_ctx_arm_last_launch(ctx);
-    // a converged series holds the fixed point in both planes, so either serves
-    NZ_TRY(nz_launch_fill_finalise(ctx->stream, h, planes[0], d->depth, c.status, L.n));
-    return nz_ctx_finish(ctx, out);
+    const int sweeps = fill_sweeps.load();
+    return run_tile_series(
+        ctx, out, d->maxPasses, k.hd,
+        [&](int p, const unsigned char *flags_in, unsigned char *flags_out) {  // pass p writes plane p & 1
+            return nz_launch_fill_pass(ctx->stream, h, p ? k.w[(p - 1) & 1] : nullptr, k.w[p & 1], k.hd.status, flags_in,
+                                       flags_out, eps, d->seaLevel, res, count, p, sweeps);
+        },
+        // a converged series holds the fixed point in both planes, so either serves
+        [&] { return nz_launch_fill_finalise(ctx->stream, h, k.w[0], d->depth, k.hd.status, n); });
 }
 
 extern "C" int32_t nz_fill_depressions(nz_ctx *ctx, float *src, float *work, const nz_fill_desc *desc, int32_t resolution,
@@ -506,8 +563,7 @@ extern "C" int32_t nz_fill_depressions_rw(nz_ctx *ctx, nz_rw_tile *tile, float *
 extern "C" int32_t nz_fill_stripe_halo_rows(void) { return 1; }
 
 extern "C" size_t nz_fill_stripe_work_floats(const nz_stripe *st) {
-    if (!nz_stripe_plane_floats(st) || st->own0 < 0 || st->own1 < st->own0) return 0;
-    return fill_stripe_layout(*st).total(1);
+    return stripe_has_work(st) ? fill_work_of(nullptr, stripe_shape(*st), 1).hd.total : 0;
 }
 
 extern "C" int32_t nz_fill_stripe(nz_ctx *ctx, const float *height, float *w, float *work, const nz_stripe *st,
@@ -519,8 +575,8 @@ extern "C" int32_t nz_fill_stripe(nz_ctx *ctx, const float *height, float *w, fl
     NZ_REQUIRE(height && w && work, "height/w/work is NULL");
     NZ_REQUIRE(changed, "changed is NULL");
     const nz_geom g = nz_geom_from_stripe(*st);
-    const fill_layout L = fill_stripe_layout(*st);
-    const size_t span = nz_stripe_span(*st), total = L.total(1);
+    const fill_work k = fill_work_of(work, stripe_shape(*st), 1);
+    const size_t span = nz_stripe_span(*st), total = k.hd.total;
     NZ_REQUIRE(!nz_planes_overlap(w, span, height, span), "w overlaps height");
     NZ_REQUIRE(!nz_planes_overlap(work, total, height, span), "work overlaps height");
     NZ_REQUIRE(!nz_planes_overlap(work, total, w, span), "work overlaps w");
@@ -529,24 +585,15 @@ extern "C" int32_t nz_fill_stripe(nz_ctx *ctx, const float *height, float *w, fl
         NZ_REQUIRE(!nz_bytes_overlap(changed, 4, p.p, p.floats * 4), "changed overlaps a plane");
         NZ_REQUIRE(!nz_bytes_overlap(proceed, 4, p.p, p.floats * 4), "proceed overlaps a plane");
     }
-    const fill_work c = fill_carve(work, L);
-    float *planes[2] = {w, c.planes};  // pass p reads plane p & 1 and writes the other
     const float eps = desc->epsilon + 0.0f;  // -0 -> +0
-    const int sweeps = fill_sweeps.load(), passes = desc->maxPasses;
+    const int sweeps = fill_sweeps.load();
     const int zlo = nz_stripe_grid_lo(*st), zhi = nz_stripe_grid_hi(*st) - 1;
-    nz_ctx_handle_rides(ctx, out != nullptr);
-    NZ_TRY(nz_launch_fill_round_begin(ctx->stream, c.status, proceed, changed, first != 0));
-    for (int p = 0; p < passes; p++) {
-        if (p == passes - 1 && !(passes & 1)) nz_ctx_arm_last_launch(ctx);
-        NZ_TRY(nz_launch_fill_stripe_pass(ctx->stream, height, planes[p & 1], planes[(p + 1) & 1], w, c.status,
-                                          c.flags[(p + 1) & 1], c.flags[p & 1], changed, eps, desc->seaLevel, g, zlo, zhi,
-                                          first != 0, p, sweeps));
-    }
-    if (passes & 1) {  // the last pass wrote the work plane
-        nz_ctx_arm_last_launch(ctx);
-        NZ_TRY(nz_launch_fill_round_end(ctx->stream, w, planes[1], c.status, passes, g));
-    }
-    return nz_ctx_finish(ctx, out);
+    return run_stripe_round(
+        ctx, out, desc->maxPasses, k.hd, w, k.w[0], proceed, changed, first, g, [] { return (int32_t)NZ_OK; },
+        [&](int p, const float *w_in, float *w_out, const unsigned char *flags_in, unsigned char *flags_out) {
+            return nz_launch_fill_stripe_pass(ctx->stream, height, w_in, w_out, w, k.hd.status, flags_in, flags_out, changed,
+                                              eps, desc->seaLevel, g, zlo, zhi, first != 0, p, sweeps);
+        });
 }
 
 extern "C" int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const float *w, float *depth, const nz_stripe *st,
@@ -568,30 +615,24 @@ extern "C" int32_t nz_fill_stripe_finalise(nz_ctx *ctx, float *height, const flo
 // ---------------------------------------------------------------------------------------------
 // drainage area (new-framework feature, include/noize_hip.h, nz_drainage.hip)
 // ---------------------------------------------------------------------------------------------
-// The passes follow the fill stage's protocol (nz_relax_pass.hpp), so `work` begins as the fill's does -- 16 status words,
-// two generations of per-tile bytes -- and goes on with one donor byte per cell (rounded up to 16 bytes) and one A plane of
-// count * res^2 floats; the other A plane is the caller's `drainage`.
+// `work`, in the tile and in the stripe form: the head, one donor byte per cell and one A plane; the other A plane is the
+// caller's.  (The stripe form counts the tile bytes over the owned rows and keeps a donor byte at the cell's index in the
+// stripe's plane, of which only the owned rows are used.)
 namespace {
-constexpr int DRAINAGE_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "drainage area"
-std::atomic<int> drainage_sweeps{DRAINAGE_SWEEPS};  // nz_debug_drainage_sweeps may be called while a thread runs an entry
-struct drainage_layout {
-    fill_layout f;
-    size_t donor_floats;
-    size_t total() const { return FILL_STATUS + 2 * f.gen_floats + donor_floats + f.n; }
-};
-drainage_layout drainage_layout_of(int res, int count) {
-    const fill_layout f = fill_layout_of(res, count);
-    return drainage_layout{f, (f.n + 15) / 16 * 4};
+struct drainage_work { relax_work hd; unsigned char *donors; float *a; };
+drainage_work drainage_work_of(float *work, const relax_shape &sh) {
+    drainage_work k{relax_work(work, sh), nullptr, nullptr};
+    k.donors = k.hd.bytes(sh.n);
+    k.a = k.hd.floats(sh.n);
+    return k;
 }
 }  // namespace
 
 extern "C" size_t nz_drainage_area_work_floats(int32_t resolution, int32_t count) {
-    return resolution > 0 && count > 0 ? drainage_layout_of(resolution, count).total() : 0;
+    return resolution > 0 && count > 0 ? drainage_work_of(nullptr, tile_shape(resolution, count)).hd.total : 0;
 }
 
-extern "C" int32_t nz_debug_drainage_sweeps(int32_t sweeps) {
-    return drainage_sweeps.exchange(sweeps > 0 ? sweeps : DRAINAGE_SWEEPS);
-}
+extern "C" int32_t nz_debug_drainage_sweeps(int32_t sweeps) { return drainage_sweeps.exchange(sweeps); }
 
 static int32_t check_drainage_desc(const nz_drainage_desc *d) {
     NZ_REQUIRE(d, "desc is NULL");
@@ -612,24 +653,23 @@ static int32_t drainage_impl(nz_ctx *ctx, const float *height, float *drainage, 
     NZ_REQUIRE(drainage, "drainage is NULL");
     NZ_REQUIRE(work, "work is NULL");
     NZ_TRY(check_drainage_desc(d));
-    const drainage_layout L = drainage_layout_of(res, count);
-    const size_t n = L.f.n;
-    const nz_named_plane writes[] = {{"drainage", drainage, n}, {"work", work, L.total()}};
+    const relax_shape sh = tile_shape(res, count);
+    const drainage_work k = drainage_work_of(work, sh);
+    const size_t n = sh.n;
+    const nz_named_plane writes[] = {{"drainage", drainage, n}, {"work", work, k.hd.total}};
     const nz_named_plane reads[] = {{"height", height, n}, {"rainMap", d->rainMap, n}};
     NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
-    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
-    unsigned char *donors = reinterpret_cast<unsigned char *>(c.planes);
-    float *planes[2] = {drainage, c.planes + L.donor_floats};  // pass p writes plane p & 1 and byte generation p & 1
-    const int sweeps = drainage_sweeps.load();  // one cap for the whole series
-    nz_ctx_handle_rides(ctx, out != nullptr);
-    NZ_TRY(nz_launch_drainage_mask(ctx->stream, height, donors, d->seaLevel, res, count));
-    for (int p = 0; p < d->maxPasses; p++)
-        NZ_TRY(nz_launch_drainage_pass(ctx->stream, donors, d->rainMap, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1],
-                                       c.status, c.flags[(p - 1) & 1], c.flags[p & 1], d->rain, res, count, p, sweeps));
-    nz_ctx_arm_last_launch(ctx);
-    // a series at rest holds the fixed point in both planes, so `drainage` has it whichever plane was written last
-    NZ_TRY(nz_launch_drainage_finalise(ctx->stream, drainage, d->rainMap, c.status, d->rain, n));
-    return nz_ctx_finish(ctx, out);
+    float *planes[2] = {drainage, k.a};
+    const int sweeps = drainage_sweeps.load();
+    NZ_TRY(nz_launch_drainage_mask(ctx->stream, height, k.donors, d->seaLevel, res, count));
+    return run_tile_series(
+        ctx, out, d->maxPasses, k.hd,
+        [&](int p, const unsigned char *flags_in, unsigned char *flags_out) {  // pass p writes plane p & 1
+            return nz_launch_drainage_pass(ctx->stream, k.donors, d->rainMap, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1],
+                                           k.hd.status, flags_in, flags_out, d->rain, res, count, p, sweeps);
+        },
+        // a series at rest holds the fixed point in both planes, so `drainage` has it whichever plane was written last
+        [&] { return nz_launch_drainage_finalise(ctx->stream, drainage, d->rainMap, k.hd.status, d->rain, n); });
 }
 
 extern "C" int32_t nz_drainage_area(nz_ctx *ctx, const float *height, float *drainage, float *work,
@@ -644,19 +684,12 @@ extern "C" int32_t nz_drainage_area_batch(nz_ctx *ctx, const float *height, floa
 }
 
 // ---- the stripe form (include/noize_hip.h): one round of passes on the owned rows against one frozen row of A on each side ----
-// `work` as in the tile form, the tile bytes counted over the owned rows: status words, two generations of tile bytes, one
-// donor byte per cell of the stripe's plane (at the cell's index; only the owned rows are used) and one A plane of the
-// stripe's shape, last.  The round's begin and end launches are the fill stripe's: they know status words and planes only.
-static drainage_layout drainage_stripe_layout(const nz_stripe &st) {
-    const fill_layout f = fill_stripe_layout(st);
-    return drainage_layout{f, (f.n + 15) / 16 * 4};
-}
-
+// `work` is laid out as in the tile form.  The round's begin and end launches are the fill stripe's: they know status words
+// and planes only.
 extern "C" int32_t nz_drainage_stripe_halo_rows(void) { return 2; }
 
 extern "C" size_t nz_drainage_stripe_work_floats(const nz_stripe *st) {
-    if (!nz_stripe_plane_floats(st) || st->own0 < 0 || st->own1 < st->own0) return 0;
-    return drainage_stripe_layout(*st).total();
+    return stripe_has_work(st) ? drainage_work_of(nullptr, stripe_shape(*st)).hd.total : 0;
 }
 
 // the two words of a stripe call are ints, not planes of floats: apart from every plane of the call and from each other
@@ -681,32 +714,25 @@ extern "C" int32_t nz_drainage_stripe_round(nz_ctx *ctx, const float *height, fl
     NZ_REQUIRE(work, "work is NULL");
     NZ_REQUIRE(changed, "changed is NULL");
     const nz_geom g = nz_geom_from_stripe(*st);
-    const drainage_layout L = drainage_stripe_layout(*st);
+    const drainage_work k = drainage_work_of(work, stripe_shape(*st));
     const size_t span = nz_stripe_span(*st);
-    const nz_named_plane writes[] = {{"a", a, span}, {"work", work, L.total()}};
+    const nz_named_plane writes[] = {{"a", a, span}, {"work", work, k.hd.total}};
     const nz_named_plane reads[] = {{"height", height, span}, {"rainMap", desc->rainMap, span}};
     NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
     const nz_named_plane all[] = {writes[0], writes[1], reads[0], reads[1]};
     NZ_TRY(check_stripe_words(changed, "changed", proceed, "proceed", all, std::size(all)));
-    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
-    unsigned char *donors = reinterpret_cast<unsigned char *>(c.planes);
-    float *planes[2] = {a, c.planes + L.donor_floats};  // pass p reads plane p & 1 and writes the other
-    const int sweeps = drainage_sweeps.load(), passes = desc->maxPasses;
+    const int sweeps = drainage_sweeps.load();
     const int zlo = nz_stripe_grid_lo(*st), zhi = nz_stripe_grid_hi(*st) - 1;
-    nz_ctx_handle_rides(ctx, out != nullptr);
-    NZ_TRY(nz_launch_fill_round_begin(ctx->stream, c.status, proceed, changed, first != 0));
-    if (first) NZ_TRY(nz_launch_drainage_stripe_mask(ctx->stream, height, donors, c.status, desc->seaLevel, g, zlo, zhi));
-    for (int p = 0; p < passes; p++) {
-        if (p == passes - 1 && !(passes & 1)) nz_ctx_arm_last_launch(ctx);
-        NZ_TRY(nz_launch_drainage_stripe_pass(ctx->stream, donors, desc->rainMap, planes[p & 1], planes[(p + 1) & 1],
-                                              c.status, c.flags[(p + 1) & 1], c.flags[p & 1], changed, desc->rain, g, zlo, zhi,
-                                              first != 0, p, sweeps));
-    }
-    if (passes & 1) {  // the last pass wrote the work plane
-        nz_ctx_arm_last_launch(ctx);
-        NZ_TRY(nz_launch_fill_round_end(ctx->stream, a, planes[1], c.status, passes, g));
-    }
-    return nz_ctx_finish(ctx, out);
+    return run_stripe_round(
+        ctx, out, desc->maxPasses, k.hd, a, k.a, proceed, changed, first, g,
+        [&]() -> int32_t {  // the donor bytes of a round that continues stand in `work`
+            if (!first) return NZ_OK;
+            return nz_launch_drainage_stripe_mask(ctx->stream, height, k.donors, k.hd.status, desc->seaLevel, g, zlo, zhi);
+        },
+        [&](int p, const float *a_in, float *a_out, const unsigned char *flags_in, unsigned char *flags_out) {
+            return nz_launch_drainage_stripe_pass(ctx->stream, k.donors, desc->rainMap, a_in, a_out, k.hd.status, flags_in,
+                                                  flags_out, changed, desc->rain, g, zlo, zhi, first != 0, p, sweeps);
+        });
 }
 
 extern "C" int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_stripe *st, const nz_drainage_desc *desc,
@@ -728,32 +754,26 @@ extern "C" int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_s
 // ---------------------------------------------------------------------------------------------
 // watershed: basin labels, flow length, receiver codes (new-framework feature, include/noize_hip.h, nz_watershed.hip)
 // ---------------------------------------------------------------------------------------------
-// The passes follow the fill stage's protocol (nz_relax_pass.hpp), so `work` begins as the fill's does -- 16 status words,
-// two generations of per-tile bytes -- and goes on with one receiver byte per cell (rounded up to 16 bytes; unused when the
-// caller has a `receivers` plane), the second label plane of count * res^2 int32 and, with a length, the second length
-// plane; the first planes are the caller's `basin` and `length`.
+// `work`: the head, one receiver byte per cell (unused when the caller has a `receivers` plane), the second label plane of
+// count * res^2 int32 and, with a length, the second length plane; the first planes are the caller's `basin` and `length`.
 namespace {
-constexpr int WATERSHED_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "watershed"
-std::atomic<int> watershed_sweeps{WATERSHED_SWEEPS};  // nz_debug_watershed_sweeps may be called while a thread runs an entry
-constexpr float WATERSHED_SQRT2 = 0x1.6a09e6p+0f;     // the diagonal step is cellSize times this, rounded once
-struct watershed_layout {
-    fill_layout f;
-    size_t recv_floats;
-    size_t total(bool with_length) const { return FILL_STATUS + 2 * f.gen_floats + recv_floats + (with_length ? 2 : 1) * f.n; }
-};
-watershed_layout watershed_layout_of(int res, int count) {
-    const fill_layout f = fill_layout_of(res, count);
-    return watershed_layout{f, (f.n + 15) / 16 * 4};
+constexpr float WATERSHED_SQRT2 = 0x1.6a09e6p+0f;  // the diagonal step is cellSize times this, rounded once
+struct watershed_work { relax_work hd; unsigned char *recv; int *basin; float *length; };
+watershed_work watershed_work_of(float *work, const relax_shape &sh, bool with_length) {
+    watershed_work k{relax_work(work, sh), nullptr, nullptr, nullptr};
+    k.recv = k.hd.bytes(sh.n);
+    k.basin = k.hd.ints(sh.n);
+    if (with_length) k.length = k.hd.floats(sh.n);
+    return k;
 }
 }  // namespace
 
 extern "C" size_t nz_watershed_work_floats(int32_t resolution, int32_t count, int32_t withLength) {
-    return resolution > 0 && count > 0 ? watershed_layout_of(resolution, count).total(withLength != 0) : 0;
+    if (resolution <= 0 || count <= 0) return 0;
+    return watershed_work_of(nullptr, tile_shape(resolution, count), withLength != 0).hd.total;
 }
 
-extern "C" int32_t nz_debug_watershed_sweeps(int32_t sweeps) {
-    return watershed_sweeps.exchange(sweeps > 0 ? sweeps : WATERSHED_SWEEPS);
-}
+extern "C" int32_t nz_debug_watershed_sweeps(int32_t sweeps) { return watershed_sweeps.exchange(sweeps); }
 
 static int32_t watershed_impl(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers, float *work,
                               const nz_watershed_desc *d, int res, int count, nz_handle dep, nz_handle *out) {
@@ -768,32 +788,31 @@ static int32_t watershed_impl(nz_ctx *ctx, const float *height, int32_t *basin, 
     NZ_REQUIRE(!std::isnan(d->seaLevel), "seaLevel is NaN");
     NZ_REQUIRE(d->cellSize > 0.0f, "cellSize %g <= 0", (double)d->cellSize);
     NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
-    const watershed_layout L = watershed_layout_of(res, count);
-    const size_t n = L.f.n;
+    const relax_shape sh = tile_shape(res, count);
+    const watershed_work k = watershed_work_of(work, sh, length != nullptr);
+    const size_t n = sh.n;
     NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
     const float *labels = reinterpret_cast<const float *>(basin);  // a plane of n 4-byte cells
-    const nz_named_plane writes[] = {{"basin", labels, n}, {"length", length, n}, {"work", work, L.total(length != nullptr)}};
+    const nz_named_plane writes[] = {{"basin", labels, n}, {"length", length, n}, {"work", work, k.hd.total}};
     const nz_named_plane reads[] = {{"height", height, n}};
     NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
     for (const auto &p : {reads[0], writes[0], writes[1], writes[2]})  // the receiver plane is bytes, not floats
         NZ_REQUIRE(!nz_bytes_overlap(receivers, n, p.p, p.floats * sizeof(float)), "receivers overlaps %s", p.name);
-    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
-    unsigned char *recv = receivers ? receivers : reinterpret_cast<unsigned char *>(c.planes);
-    float *second = c.planes + L.recv_floats;
-    int *labels2[2] = {basin, reinterpret_cast<int *>(second)};  // pass p writes plane p & 1 and byte generation p & 1
-    float *lengths[2] = {length, length ? second + n : nullptr};
+    unsigned char *recv = receivers ? receivers : k.recv;
+    int *labels2[2] = {basin, k.basin};
+    float *lengths[2] = {length, k.length};
     const float cell = d->cellSize, diag = d->cellSize * WATERSHED_SQRT2;
-    const int sweeps = watershed_sweeps.load();  // one cap for the whole series
-    nz_ctx_handle_rides(ctx, out != nullptr);
+    const int sweeps = watershed_sweeps.load();
     NZ_TRY(nz_launch_watershed_receivers(ctx->stream, height, recv, d->seaLevel, res, count));
-    for (int p = 0; p < d->maxPasses; p++)
-        NZ_TRY(nz_launch_watershed_pass(ctx->stream, recv, p ? labels2[(p - 1) & 1] : nullptr, labels2[p & 1],
-                                        p ? lengths[(p - 1) & 1] : nullptr, lengths[p & 1], c.status, c.flags[(p - 1) & 1],
-                                        c.flags[p & 1], cell, diag, res, count, p, sweeps));
-    nz_ctx_arm_last_launch(ctx);
-    // a series at rest holds the fixed point in both planes of a pair, so the caller's have it whichever was written last
-    NZ_TRY(nz_launch_watershed_finalise(ctx->stream, basin, length, c.status, res, n));
-    return nz_ctx_finish(ctx, out);
+    return run_tile_series(
+        ctx, out, d->maxPasses, k.hd,
+        [&](int p, const unsigned char *flags_in, unsigned char *flags_out) {  // pass p writes plane p & 1 of each pair
+            return nz_launch_watershed_pass(ctx->stream, recv, p ? labels2[(p - 1) & 1] : nullptr, labels2[p & 1],
+                                            p ? lengths[(p - 1) & 1] : nullptr, lengths[p & 1], k.hd.status, flags_in,
+                                            flags_out, cell, diag, res, count, p, sweeps);
+        },
+        // a series at rest holds the fixed point in both planes of a pair, so the caller's have it whichever was written last
+        [&] { return nz_launch_watershed_finalise(ctx->stream, basin, length, k.hd.status, res, n); });
 }
 
 extern "C" int32_t nz_watershed(nz_ctx *ctx, const float *height, int32_t *basin, float *length, uint8_t *receivers,
@@ -811,30 +830,25 @@ extern "C" int32_t nz_watershed_batch(nz_ctx *ctx, const float *height, int32_t 
 // ---------------------------------------------------------------------------------------------
 // stream order: Strahler order and river links (new-framework feature, include/noize_hip.h, nz_stream_order.hip)
 // ---------------------------------------------------------------------------------------------
-// `work` is laid out as the watershed's: 16 status words, two generations of per-tile bytes, then one channel-donor byte
-// per cell and the second order plane of one byte per cell (each rounded up to 16 bytes) and, with links, the second link
-// plane of count * res^2 int32; the first planes are the caller's `order` and `link`.
+// `work`: the head, one channel-donor byte per cell, the second order plane of one byte per cell and, with links, the second
+// link plane of count * res^2 int32; the first planes are the caller's `order` and `link`.
 namespace {
-constexpr int STREAM_ORDER_SWEEPS = 16;  // measured, 4 to 64: DESIGN.md section 4, "stream order"
-std::atomic<int> stream_order_sweeps{STREAM_ORDER_SWEEPS};  // nz_debug_stream_order_sweeps may be called while a thread runs an entry
-struct stream_order_layout {
-    fill_layout f;
-    size_t byte_floats;  // one byte plane in floats
-    size_t total(bool with_links) const { return FILL_STATUS + 2 * f.gen_floats + 2 * byte_floats + (with_links ? f.n : 0); }
-};
-stream_order_layout stream_order_layout_of(int res, int count) {
-    const fill_layout f = fill_layout_of(res, count);
-    return stream_order_layout{f, (f.n + 15) / 16 * 4};
+struct stream_order_work { relax_work hd; unsigned char *donors, *order; int *link; };
+stream_order_work stream_order_work_of(float *work, const relax_shape &sh, bool with_links) {
+    stream_order_work k{relax_work(work, sh), nullptr, nullptr, nullptr};
+    k.donors = k.hd.bytes(sh.n);
+    k.order = k.hd.bytes(sh.n);
+    if (with_links) k.link = k.hd.ints(sh.n);
+    return k;
 }
 }  // namespace
 
 extern "C" size_t nz_stream_order_work_floats(int32_t resolution, int32_t count, int32_t withLinks) {
-    return resolution > 0 && count > 0 ? stream_order_layout_of(resolution, count).total(withLinks != 0) : 0;
+    if (resolution <= 0 || count <= 0) return 0;
+    return stream_order_work_of(nullptr, tile_shape(resolution, count), withLinks != 0).hd.total;
 }
 
-extern "C" int32_t nz_debug_stream_order_sweeps(int32_t sweeps) {
-    return stream_order_sweeps.exchange(sweeps > 0 ? sweeps : STREAM_ORDER_SWEEPS);
-}
+extern "C" int32_t nz_debug_stream_order_sweeps(int32_t sweeps) { return stream_order_sweeps.exchange(sweeps); }
 
 static int32_t stream_order_impl(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,
                                  const nz_stream_order_desc *d, int res, int count, nz_handle dep, nz_handle *out) {
@@ -848,29 +862,29 @@ static int32_t stream_order_impl(nz_ctx *ctx, const float *height, uint8_t *orde
     NZ_REQUIRE(std::isfinite(d->threshold), "threshold is not finite");
     NZ_REQUIRE(!std::isnan(d->seaLevel), "seaLevel is NaN");
     NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
-    const stream_order_layout L = stream_order_layout_of(res, count);
-    const size_t n = L.f.n;
+    const relax_shape sh = tile_shape(res, count);
+    const stream_order_work k = stream_order_work_of(work, sh, link != nullptr);
+    const size_t n = sh.n;
     NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
     const float *links = reinterpret_cast<const float *>(link);  // a plane of n 4-byte cells
-    const nz_named_plane writes[] = {{"link", links, n}, {"work", work, L.total(link != nullptr)}};
+    const nz_named_plane writes[] = {{"link", links, n}, {"work", work, k.hd.total}};
     const nz_named_plane reads[] = {{"height", height, n}, {"drainage", d->drainage, n}};
     NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
     for (const auto &p : {reads[0], reads[1], writes[0], writes[1]})  // the order plane is bytes, not floats
         NZ_REQUIRE(!nz_bytes_overlap(order, n, p.p, p.floats * sizeof(float)), "order overlaps %s", p.name);
-    const fill_work c = fill_carve(work, L.f);  // c.planes: what follows the tile bytes
-    unsigned char *donors = reinterpret_cast<unsigned char *>(c.planes);
-    unsigned char *orders[2] = {order, reinterpret_cast<unsigned char *>(c.planes + L.byte_floats)};
-    int *links2[2] = {link, link ? reinterpret_cast<int *>(c.planes + 2 * L.byte_floats) : nullptr};
-    const int sweeps = stream_order_sweeps.load();  // one cap for the whole series
-    nz_ctx_handle_rides(ctx, out != nullptr);
-    NZ_TRY(nz_launch_stream_mask(ctx->stream, height, d->drainage, donors, order, d->seaLevel, d->threshold, res, count));
-    for (int p = 0; p < d->maxPasses; p++)  // pass p reads plane p & 1 and writes the other, and byte generation p & 1
-        NZ_TRY(nz_launch_stream_pass(ctx->stream, donors, orders[p & 1], orders[(p + 1) & 1], p ? links2[p & 1] : nullptr,
-                                     links2[(p + 1) & 1], c.status, c.flags[(p - 1) & 1], c.flags[p & 1], res, count, p, sweeps));
-    nz_ctx_arm_last_launch(ctx);
-    // a series at rest holds the fixed point in both planes of a pair, so the caller's have it whichever was written last
-    NZ_TRY(nz_launch_stream_finalise(ctx->stream, order, link, d->drainage, c.status, d->threshold, res, n));
-    return nz_ctx_finish(ctx, out);
+    unsigned char *orders[2] = {order, k.order};
+    int *links2[2] = {link, k.link};
+    const int sweeps = stream_order_sweeps.load();
+    NZ_TRY(nz_launch_stream_mask(ctx->stream, height, d->drainage, k.donors, order, d->seaLevel, d->threshold, res, count));
+    return run_tile_series(
+        ctx, out, d->maxPasses, k.hd,
+        // pass p READS plane p & 1 of each pair and writes the other: the mask launch left the start state in plane 0
+        [&](int p, const unsigned char *flags_in, unsigned char *flags_out) {
+            return nz_launch_stream_pass(ctx->stream, k.donors, orders[p & 1], orders[(p + 1) & 1], p ? links2[p & 1] : nullptr,
+                                         links2[(p + 1) & 1], k.hd.status, flags_in, flags_out, res, count, p, sweeps);
+        },
+        // a series at rest holds the fixed point in both planes of a pair, so the caller's have it whichever was written last
+        [&] { return nz_launch_stream_finalise(ctx->stream, order, link, d->drainage, k.hd.status, d->threshold, res, n); });
 }
 
 extern "C" int32_t nz_stream_order(nz_ctx *ctx, const float *height, uint8_t *order, int32_t *link, float *work,

@@ -1,4 +1,5 @@
-// nz_tile64.hpp -- the workgroup geometry of nz_fluvial.hip, nz_fill.hip and nz_drainage.hip, stated once: FT = 256 threads
+// nz_tile64.hpp -- the workgroup geometry of nz_fluvial.hip, nz_fill.hip, nz_drainage.hip, nz_watershed.hip and
+// nz_stream_order.hip (and of nz_donor_front.hpp, the mask launches of the last three), stated once: FT = 256 threads
 // own an FX x FZ = 64 x 16 tile of one plane, a thread four consecutive cells of a row (16-byte accesses where planes and
 // pitch allow), batch tiles on blockIdx.z.  A plane staged in LDS has LP = 72 cells per row with the tile at column LC = 4:
 // a thread's four cells are one aligned float4, and a radius-R plane keeps plane row z0 + i in LDS row R + i.
@@ -53,6 +54,14 @@ __device__ __forceinline__ void window_bytes(const unsigned *words, int tz, int 
         w[r][0] = bytes[l - 1], w[r][1] = q & 255u, w[r][2] = (q >> 8) & 255u, w[r][3] = (q >> 16) & 255u, w[r][4] = q >> 24;
         w[r][5] = bytes[l + 4];
     }
+}
+
+// the LDS cell of a radius-1 plane that neighbour code k -- W E S N SW SE NW NE -- of a thread's own cell j names; k >= 8
+// (no neighbour): the cell itself
+__device__ __forceinline__ int neighbour_lds(int tz, int tx, int j, int k) {
+    const int dx = k >= 8 || k == 2 || k == 3 ? 0 : (k & 1) ? 1 : -1;
+    const int dz = k >= 8 || k < 2 ? 0 : (k == 3 || k >= 6) ? 1 : -1;
+    return (tz + 1 + dz) * LP + LC + tx + j + dx;
 }
 
 }  // namespace nz_tile64

@@ -12,8 +12,9 @@
 // its code names instead of gathering up to eight donors, and it carries an int32 and a float plane together.
 //
 // The receiver launch, once per call, on the geometry of nz_tile64.hpp (16-byte accesses where planes and pitch allow):
-// heights at radius 1 into LDS and per own cell one RECEIVER BYTE, the code 0..7 or NONE -- to the caller's `receivers`
-// plane when it wants one, else to `work`.  After it no launch looks at a height.
+// heights at radius 1 into LDS and per own cell one RECEIVER BYTE, the code 0..7 or NONE (receiver_codes4 of
+// nz_donor_front.hpp) -- to the caller's `receivers` plane when it wants one, else to `work`.  After it no launch looks at
+// a height.
 //
 // One launch per PASS, by the pass protocol of nz_relax_pass.hpp -- gate, tile skip, sweeps against a frozen ring, the
 // closing byte and word, and the argument for them; the caller's `basin` and `length` are plane 0 of each pair.  What is
@@ -32,12 +33,12 @@
 #include "nz_receiver.hpp"
 #include "nz_relax_pass.hpp"
 #include "nz_tile64.hpp"
+#include "nz_donor_front.hpp"
 
 namespace {
 
 using nz_recv::NONE;
-using nz_recv::receiver;
-using namespace nz_tile64;  // the tile, its LDS layout, ring_cell
+using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, neighbour_lds
 using namespace nz_relax;   // the status words and the pass protocol
 
 constexpr unsigned NONE4 = NONE * 0x01010101u;  // the code word of four cells without a receiver
@@ -85,22 +86,7 @@ __global__ __launch_bounds__(FT) void watershed_receiver_kernel(const float *__r
 
     // ---- the receiver codes of the own cells: NONE for an outlet and for a pit ----
     if (!row_in || px > hi) return;
-    float w[3][6];  // rows pz-1 .. pz+1, columns px-1 .. px+4
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const float *row = &H[(tz + r) * LP + LC + tx];
-        const float4 v = *reinterpret_cast<const float4 *>(row);
-        w[r][0] = row[-1], w[r][1] = v.x, w[r][2] = v.y, w[r][3] = v.z, w[r][4] = v.w, w[r][5] = row[4];
-    }
-    unsigned word = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        float s, d;
-        unsigned r = receiver(w[1][j + 1], w[1][j], w[1][j + 2], w[0][j + 1], w[2][j + 1], w[0][j], w[0][j + 2], w[2][j],
-                              w[2][j + 2], s, d);
-        if (on_border(px + j, pz) || w[1][j + 1] <= sea) r = NONE;
-        word |= r << (8 * j);
-    }
+    const unsigned word = nz_front::receiver_codes4(H, tz, tx, sea, [&](int j) { return on_border(px + j, pz); });
     if (WORD && quad) {
         *reinterpret_cast<unsigned *>(recv + c0) = word;
     } else {
@@ -211,9 +197,7 @@ __global__ __launch_bounds__(FT) void watershed_pass_kernel(const unsigned char 
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         const unsigned k = (cod >> (8 * j)) & 255u;
-        const int dx = k >= NONE || k == 2u || k == 3u ? 0 : (k & 1u) ? 1 : -1;
-        const int dz = k >= NONE || k < 2u ? 0 : (k == 3u || k >= 6u) ? 1 : -1;
-        at[j] = (tz + 1 + dz) * LP + LC + tx + j + dx;
+        at[j] = neighbour_lds(tz, tx, j, (int)k);
         st[j] = k < 4u ? cell : diag;
     }
     __syncthreads();
@@ -302,17 +286,6 @@ int32_t nz_launch_watershed_receivers(hipStream_t s, const float *h, unsigned ch
     return NZ_OK;
 }
 
-namespace {
-// the form of a pass by <FIRST, VEC, LEN>
-template <bool FIRST, bool VEC>
-void launch_pass(bool len, dim3 grid, hipStream_t s, const unsigned char *recv, const int *b_in, int *b_out, const float *l_in,
-                 float *l_out, int *status, const unsigned char *flags_in, unsigned char *flags_out, float cell, float diag,
-                 int res, int pass, int sweeps) {
-    if (len) NZ_LAUNCH((watershed_pass_kernel<FIRST, VEC, true>), grid, dim3(FT), 0, s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
-    else NZ_LAUNCH((watershed_pass_kernel<FIRST, VEC, false>), grid, dim3(FT), 0, s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
-}
-}  // namespace
-
 int32_t nz_launch_watershed_pass(hipStream_t s, const unsigned char *recv, const int *b_in, int *b_out, const float *l_in,
                                  float *l_out, int *status, const unsigned char *flags_in, unsigned char *flags_out,
                                  float cell, float diag, int res, int count, int pass, int sweeps) {
@@ -322,14 +295,10 @@ int32_t nz_launch_watershed_pass(hipStream_t s, const unsigned char *recv, const
                            reinterpret_cast<uintptr_t>(l_in) | reinterpret_cast<uintptr_t>(l_out);
     // a row, and with it a tile of the batch, starts 16-byte aligned in the planes and 4-byte aligned in the receiver bytes
     const bool vec = (bits & 15) == 0 && (reinterpret_cast<uintptr_t>(recv) & 3) == 0 && res % 4 == 0;
-    const bool len = l_out != nullptr;
-    if (pass == 0) {
-        if (vec) launch_pass<true, true>(len, grid, s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
-        else launch_pass<true, false>(len, grid, s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
-    } else {
-        if (vec) launch_pass<false, true>(len, grid, s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
-        else launch_pass<false, false>(len, grid, s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
-    }
+    nz_with_bools([&](auto first, auto v, auto len) {
+        NZ_LAUNCH((watershed_pass_kernel<decltype(first)::value, decltype(v)::value, decltype(len)::value>), grid, dim3(FT), 0,
+                  s, recv, b_in, b_out, l_in, l_out, status, flags_in, flags_out, cell, diag, res, pass, sweeps);
+    }, pass == 0, vec, l_out != nullptr);
     NZ_HIP(hipGetLastError());
     return NZ_OK;
 }

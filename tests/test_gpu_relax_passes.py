@@ -1,9 +1,11 @@
-"""The pass counts of the iterate-to-rest series (nz_fill_depressions*, nz_fill_stripe, nz_drainage_area), pinned exactly.
+"""The pass counts of the iterate-to-rest series (nz_fill_depressions*, nz_fill_stripe, nz_drainage_area, nz_watershed,
+nz_stream_order), pinned exactly.
 Result bits cannot show a broken tile skip or series gate (csrc/nz_relax_pass.hpp): a series that skips too little, or
 notices rest one pass late, ends in the same floats more slowly.  The count is deterministic -- no launch has a race, the
 ring of a tile is frozen during its sweeps and barriers separate the phases -- so it is an integer to compare, not a time
-to bound.  tests/golden/relax_passes.json holds what the series took before the protocol moved into its own header;
-`measure` is what recorded it, on the commit the file names."""
+to bound.  tests/golden/relax_passes.json holds what the series took before the protocol moved into its own header, and what the
+watershed and stream-order series took before their mask kernels, launchers and host drivers were shared; `measure` is
+what recorded either table, on the commit its key names."""
 import json
 import os
 
@@ -13,6 +15,8 @@ import torch
 
 import test_gpu_drainage as TD
 import test_gpu_fill as TF
+import test_gpu_stream_order as TS
+import test_gpu_watershed as TW
 from conftest import GOLDEN
 from fill_stripe_cases import EPS as STRIPE_EPS
 from fill_stripe_cases import grid, lockstep, stripe_ops, work_floats
@@ -68,6 +72,29 @@ def measure(nj, ctx, hip):
             got["drainage filled fbm130 rain map cap %d" % cap] = passes
     finally:
         lib.nz_debug_drainage_sweeps(0)
+    h, _, _, hops = TW.serpentine()
+    _, _, _, passes, conv = TW.run_gpu(nj, ctx, h, budget=int(hops.max()) + 2)
+    assert conv == 1
+    got["watershed serpentine160"] = passes
+    for which, (h, dr, _, _, chain) in enumerate(TS.long_tiles()):
+        _, _, passes, conv = TS.run_gpu(nj, ctx, h, TS.OFF, dr, 0.5, budget=chain + 2)
+        assert conv == 1
+        got["stream order long chain %d" % which] = passes
+    area, _, conv = TD.run_gpu(nj, ctx, filled, budget=AMPLE)
+    assert conv == 1
+    try:
+        for cap in CAPS:
+            lib.nz_debug_watershed_sweeps(cap)
+            _, _, _, passes, conv = TW.run_gpu(nj, ctx, filled, budget=AMPLE, length=True)
+            assert conv == 1
+            got["watershed filled fbm130 length cap %d" % cap] = passes
+            lib.nz_debug_stream_order_sweeps(cap)
+            _, _, passes, conv = TS.run_gpu(nj, ctx, filled, TS.OFF, area, 8.0, budget=AMPLE, links=True)
+            assert conv == 1
+            got["stream order filled fbm130 drainage threshold 8 links cap %d" % cap] = passes
+    finally:
+        lib.nz_debug_watershed_sweeps(0)
+        lib.nz_debug_stream_order_sweeps(0)
     sh, ops = hip
     rec = Recording(ops)
     _, _, rounds, converged, _, _ = lockstep(sh, rec, 2, grid("bowl"), PARAMS, work_floats(nj), "cuda")
@@ -78,7 +105,8 @@ def measure(nj, ctx, hip):
 
 def test_pass_counts_are_the_recorded_ones(nj, ctx):
     with open(os.path.join(GOLDEN, "relax_passes.json")) as f:
-        want = json.load(f)["passes"]
+        table = json.load(f)
+    want = dict(table["passes"], **table["passes on 0da72c4"])
     with stripe_ops(nj) as hip:
         got = measure(nj, ctx, hip)
     print(json.dumps(got))
