@@ -88,6 +88,15 @@ namespace xshazwar.noize.hip {
         public IntPtr drainage;
     }
 
+    // the implicit fluvial step's scalars, optional read-only planes and optional device words (nz_fluvial_implicit*);
+    // IntPtr.Zero = option off
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzFluvialImplicitDesc {                                                            // nz_fluvial_implicit_desc
+        public float erodibility, uplift, dt, seaLevel;
+        public int maxPasses;
+        public IntPtr hardness, upliftMap, proceed, tally;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

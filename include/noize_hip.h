@@ -1177,6 +1177,93 @@ int32_t nz_stream_order_batch(nz_ctx *ctx, const float *height, uint8_t *order, 
  * (process-wide; <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_stream_order_sweeps(int32_t sweeps);
 
+/* ---- implicit fluvial erosion: a large time step of the stream-power model in one solve (new-framework feature) ---------
+ * nz_fluvial_erosion above is the explicit scheme: one small step per launch, a drainage plane that is a transient, and a
+ * half-drop limiter in place of a stability bound.  The model is linear in the slope, so the implicit Euler step has a
+ * closed form along the receiver tree (the FastScape scheme, Braun & Willett 2013): stable for every dt, and one call
+ * carries "10 000 years".  Its drainage input is the exact plane nz_drainage_area delivers in one call.
+ *
+ * THE MODEL (tests/fluvial_implicit_ref.py restates it as a walk lowest cell first; the kernels are
+ * nz_fluvial_implicit.hip):
+ *   Square tile res x res, row-major c = z * res + x, float32 throughout, no contraction, the same in every float mode
+ *   (nz_ctx_set_float_mode does not apply).  Outlets, the neighbour order W E S N SW SE NW NE, "a neighbour outside the
+ *   tile does not exist" and the receiver r(c) with its strict comparison and tie rule are exactly step 1 of the fluvial
+ *   model above.  Inputs, all read only: heights h, a drainage plane A (required; e.g. nz_drainage_area on the same
+ *   heights) and the optional planes hardness and upliftMap as in nz_fluvial_desc.  Per cell:
+ *     du = dt * uplift (one product; with a map du * upliftMap[c]);  kc = erodibility * (1 - hardness[c]) (without a map
+ *     erodibility);
+ *     outlet (global border or h <= seaLevel):  h'[c] = h[c];
+ *     pit (interior, no receiver):              h'[c] = h[c] + du;
+ *     otherwise, with q the cell r(c) = k names:
+ *       b = h[c] + du,   f = ((kc * sqrt(A[c])) * invL_k) * dt,   invL_k = 1 for k < 4 and 0x1.6a09e6p-1f for k >= 4,
+ *       h'[c] = (b + f * h'[q]) / (1 + f)
+ *     each operation rounded once, in that order: product, sum, sum, one correctly rounded float32 division; sqrt is
+ *     correctly rounded as in nz_fluvial_erosion.
+ * A receiver is strictly lower than its donor, so the graph is a forest whose roots, the outlets and pits, are fixed from
+ * the start; a cell's new height is a fixed function of the new height of one other cell, so the fixed point is unique: a
+ * walk lowest cell first, Jacobi and tile sweeps end in the same bits, from any start state (the kernels start from b).
+ * The "nothing" of all or nothing is h' = h.  What follows:
+ *   - erodibility == 0 gives h + du off the outlets;
+ *   - outlets keep their bits;
+ *   - in exact arithmetic and without an upliftMap, h'[q] <= h'[c] <= h[c] + du: no cell rises above its uplifted height
+ *     or sinks below its receiver.  In float32 rounding can decide otherwise on tiles of tiny or equal heights.
+ * Say it plainly: an f that overflows (erodibility * sqrt(A) * dt beyond FLT_MAX) gives inf / inf = NaN in that cell and
+ * in every cell upstream of it; A must be finite and >= 0 (sqrt of a negative is NaN, and NaN travels upstream the same
+ * way); and pits stay pits -- a pit only rises by du and everything that drains to it is pulled towards it -- so put
+ * nz_fill_depressions (DepressionFillStage) in front.
+ *
+ * The entry enqueues one begin launch (a single thread), one setup launch (heights at radius 1, A and the maps -> one
+ * receiver byte and the coefficients b and f per cell, into `work`), maxPasses pass launches and one finalise launch,
+ * stream-ordered; nothing is read back.  After the setup launch no pass looks at a height, A or a map.  A pass is
+ * nz_watershed's scheme with a float recurrence in place of the label copy: every 64 x 16 tile is swept on chip against
+ * its frozen ring, each cell reading the one cell its code names; tiles whose neighbourhood was at rest in the pass before
+ * are skipped, and a launch returns at once when the pass before changed nothing.  After completion the first two int32 of
+ * `work` hold {passes that did work, converged 0/1}.  The result is ALL OR NOTHING: when the last pass that ran changed
+ * nothing, `out` holds the fixed point; otherwise -- the budget was too small -- out = h bit for bit and converged == 0,
+ * which is not an error.  A pass is at least one Jacobi step, so a budget of "moves of the longest flow path" + 2 always
+ * suffices.  Defaults of the hosts' ImplicitFluvialStage: iterations 1, erodibility 0.05, uplift 0.002, dt 1, rain 1,
+ * seaLevel -FLT_MAX (off), maxPasses 64 + resolution / 4 for the drainage and for the solve, no maps.
+ * The evidence (tools/bench_fluvial_implicit.py): the 13-octave simplex fBm tile behind
+ * nz_fill_depressions comes to rest in 23 passes at dt 1 and 82 at dt 100 at 1024^2, in 62 and 192 at 4096^2; the passes
+ * grow with dt up to those of nz_drainage_area and nz_watershed on the same tile (82 and 192: at a large f a cell follows
+ * its receiver to the last bit, as a label does), and the defaults allow 320 and 1088.  Not a bound: a path that winds
+ * through many tiles needs more, and a budget that runs out shows as converged == 0.
+ *
+ * `proceed` (device, optional) lets a host chain nz_drainage_area -> this entry without reading anything back: pass the
+ * address of the drainage call's converged word (the second int32 of its `work`).  The begin launch reads the word when it
+ * runs; with a zero word every launch of the call returns at once, out = h, the status is {0, 0} and `tally` is untouched.
+ * `tally` (device, two int32, optional): the finalise launch adds 1 to tally[0] when the step was applied and the passes
+ * that did work to tally[1]; calls on one context are ordered by its stream, so a host sums a series of steps there.
+ *
+ * `work` = nz_fluvial_implicit_work_floats(resolution, count) floats, stage-owned: status words, tile bytes, the receiver
+ * bytes, the planes b and f and the second h' plane (the first is `out`).  0 for resolution <= 0 or count <= 0.  The _batch
+ * form runs `count` tiles stored back to back, each with its own border; every batch position equals the single-tile call
+ * bit for bit, and the status words cover the whole batch.  resolution == 0 or count == 0 does nothing and returns NZ_OK.
+ * The 16-byte path runs when every plane is 16-byte aligned and resolution % 4 == 0, the 4-byte path otherwise; both give
+ * the same bits.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: a NULL desc, height, drainage, out or
+ * work; erodibility, uplift, dt or seaLevel not finite (-FLT_MAX switches the sea off); erodibility, uplift or dt < 0;
+ * maxPasses < 1; count * resolution^2 beyond int32; out or work overlapping height, drainage, a map or each other (`out`
+ * must not be `height`: the solve is not in place); tally overlapping a plane or proceed; proceed inside out or work.
+ * There is no row-stripe form and no _rw pair form. */
+typedef struct nz_fluvial_implicit_desc {
+    float erodibility, uplift, dt, seaLevel;
+    int32_t maxPasses;
+    const float *hardness;    /* NULL: erodibility everywhere */
+    const float *upliftMap;   /* NULL: uplift everywhere */
+    const int32_t *proceed;   /* device word, NULL: always run; a word of 0: the step is not applied */
+    int32_t *tally;           /* device, 2 words, NULL: off; tally[0] += 1 when the step was applied, tally[1] += passes that did work */
+} nz_fluvial_implicit_desc;
+size_t nz_fluvial_implicit_work_floats(int32_t resolution, int32_t count);
+int32_t nz_fluvial_implicit(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                            const nz_fluvial_implicit_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out_handle);
+int32_t nz_fluvial_implicit_batch(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                  const nz_fluvial_implicit_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                                  nz_handle *out_handle);
+/* Test hook, the twin of nz_debug_watershed_sweeps: the cap on an implicit-fluvial pass's on-chip sweeps per tile
+ * (process-wide; <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
+int32_t nz_debug_fluvial_implicit_sweeps(int32_t sweeps);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

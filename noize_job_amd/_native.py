@@ -111,12 +111,20 @@ class StreamOrderDesc(C.Structure):
     _fields_ = [("seaLevel", C.c_float), ("threshold", C.c_float), ("maxPasses", C.c_int32), ("drainage", C.c_void_p)]
 
 
+class FluvialImplicitDesc(C.Structure):
+    """nz_fluvial_implicit_desc (include/noize_hip.h): the scalars of the implicit fluvial step, the two optional read-only
+    planes and the two optional device words (device addresses; None = the option is off)."""
+    _fields_ = ([(n, C.c_float) for n in ("erodibility", "uplift", "dt", "seaLevel")] + [("maxPasses", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("hardness", "upliftMap", "proceed", "tally")])
+
+
 hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
 fill_p = C.POINTER(FillDesc)
 drain_p = C.POINTER(DrainageDesc)
 shed_p = C.POINTER(WatershedDesc)
 order_p = C.POINTER(StreamOrderDesc)
+fimp_p = C.POINTER(FluvialImplicitDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -243,6 +251,10 @@ SIGNATURES = {
     "nz_stream_order": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, order_p, _i] + _tail),
     "nz_stream_order_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, order_p, _i, _i] + _tail),
     "nz_debug_stream_order_sweeps": (_i, [_i]),
+    "nz_fluvial_implicit_work_floats": (_sz, [_i, _i]),
+    "nz_fluvial_implicit": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i] + _tail),
+    "nz_fluvial_implicit_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i, _i] + _tail),
+    "nz_debug_fluvial_implicit_sweeps": (_i, [_i]),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

@@ -501,6 +501,22 @@ int32_t nz_launch_stream_pass(hipStream_t s, const unsigned char *donors, const 
 int32_t nz_launch_stream_finalise(hipStream_t s, unsigned char *order, int *link, const float *drainage, int *status,
                                   float threshold, int res, size_t n);
 
+// implicit fluvial erosion (nz_fluvial_implicit.hip) on `count` tiles of res^2 cells stored back to back.  begin: status[5]
+// (ST_GO) from the caller's `proceed` word (NULL: go) and the status words of a fresh series; with ST_GO == 0 every later
+// launch returns at once.  setup: heights, drainage `area` and the maps (NULL: none) -> one receiver byte per cell and the
+// coefficient planes bco, fco.  pass `pass` of the series: h' planes h_in -> h_out (pass 0 reads none: it starts from bco),
+// tile bytes flags_in -> flags_out, at most `sweeps` in-LDS sweeps per tile; status as in the drainage launches.  finalise
+// sets status[1], adds {1, passes} to `tally` (NULL: off) when the series came to rest, and otherwise writes h to `out`
+int32_t nz_launch_fluvial_implicit_begin(hipStream_t s, int *status, const int *proceed);
+int32_t nz_launch_fluvial_implicit_setup(hipStream_t s, const float *h, const float *area, const float *hardness,
+                                         const float *uplift_map, unsigned char *recv, float *bco, float *fco,
+                                         const int *status, float erodibility, float uplift, float dt, float sea, int res,
+                                         int count);
+int32_t nz_launch_fluvial_implicit_pass(hipStream_t s, const unsigned char *recv, const float *bco, const float *fco,
+                                        const float *h_in, float *h_out, int *status, const unsigned char *flags_in,
+                                        unsigned char *flags_out, int res, int count, int pass, int sweeps);
+int32_t nz_launch_fluvial_implicit_finalise(hipStream_t s, const float *h, float *out, int *status, int *tally, size_t n);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {
