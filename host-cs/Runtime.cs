@@ -97,6 +97,13 @@ namespace xshazwar.noize.hip {
         public IntPtr hardness, upliftMap, proceed, tally;
     }
 
+    // the hillslope diffusion step's scalars (nz_hillslope_diffusion*)
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzHillslopeDesc {                                                                  // nz_hillslope_desc
+        public float diffusivity, dt;
+        public int iterations;
+    }
+
     // ErosionParameters, Geologic/ParticleErosion/LiveErosionDataTypes.cs:78-100 (field order kept)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzErosionParams {

@@ -1264,6 +1264,58 @@ int32_t nz_fluvial_implicit_batch(nz_ctx *ctx, const float *height, const float 
  * (process-wide; <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_fluvial_implicit_sweeps(int32_t sweeps);
 
+/* ---- hillslope diffusion: dh/dt = kappa * laplace(h) in one implicit step of any size (new-framework feature) ------------
+ * The second term of every landscape-evolution model beside stream power (FastScape pairs the two): linear diffusion rounds
+ * the knife-edge ridges and one-cell gullies the fluvial solve leaves.  An explicit step is unstable above kappa * dt = 1/4;
+ * this entry is a direct solve, stable and free of oscillation for every dt, with no pass budget and no verdict.
+ *
+ * THE MODEL (tests/hillslope_ref.py restates it in numpy; the kernels are nz_hillslope.hip):
+ *   Square tile res x res, row-major c = z * res + x, float32 throughout, every operation rounded once, no contraction, the
+ *   same in every float mode (nz_ctx_set_float_mode does not apply).  The scheme is backward Euler split by direction,
+ *   (I - r Lx)(I - r Lz) h' = h, with the border cells held (Dirichlet): they keep their bits -- they are the outlets of the
+ *   fluvial stages.  The amplification 1 / ((1 + r lx)(1 + r lz)) is positive for every r, so nothing oscillates at a large
+ *   dt; this is why the scheme is not Peaceman-Rachford, which tends to -1 there.
+ *   Coefficients, shared by every line:  r = diffusivity * dt (one product),  B = 1 + 2 * r.
+ *   Tables for i = 1 .. res-2:  den_1 = B,  den_i = B - r * cp_{i-1},  inv_i = 1 / den_i (a correctly rounded division),
+ *                               cp_i = r * inv_i.
+ *   One line solve over the values v_0 .. v_{n-1}:
+ *     p_0 = v_0;          p_i = (v_i + r * p_{i-1}) * inv_i   for i = 1 .. n-2;
+ *     x_{n-1} = v_{n-1};  x_i = p_i + cp_i * x_{i+1}          for i = n-2 .. 1;     x_0 = v_0.
+ *   One step is two half-steps: half-step X solves every row z = 1 .. res-2 along x (rows 0 and res-1 are copied), half-step
+ *   Z solves every column x = 1 .. res-2 of that result along z.  `iterations` steps are applied one after another with the
+ *   same tables.  What follows:
+ *   - res < 3 gives out = h;
+ *   - r == 0 gives out = h bit for bit, by definition: it does not go through the recurrence, which would flip the sign of a
+ *     -0.0;
+ *   - border cells keep their bits;
+ *   - in exact arithmetic the result stays within the input's minimum and maximum;
+ *   - a NaN or inf in a line spreads along that line and then across it.
+ * Defaults of the hosts' HillslopeDiffusionStage: diffusivity 0.01, dt 1, iterations 1 -- a choice, not pinned by any
+ * picture.  The evolution loop is [DepressionFillStage, ImplicitFluvialStage(dt=T), HillslopeDiffusionStage(dt=T)], repeated.
+ *
+ * The entry enqueues one table launch (inv and cp into `work`, on the device: no host buffer whose lifetime the entry would
+ * have to manage) and per step three launches -- the rows' forward sweep, the rows' backward sweep, the columns' two sweeps
+ * -- stream-ordered; nothing is read back and there are no status words.  p lives in `out`, so `work` holds only the tables:
+ * nz_hillslope_diffusion_work_floats(resolution, count) floats (0 for resolution <= 0 or count <= 0; the tables are shared
+ * by the tiles of a batch).  out == height, the same pointer, means in place and is allowed; otherwise the two planes must be
+ * disjoint.  The _batch form runs `count` tiles stored back to back, each with its own border; every batch position equals
+ * the single-tile call bit for bit.  resolution == 0 or count == 0 does nothing and returns NZ_OK.  The 16-byte path runs
+ * when every plane is 16-byte aligned and resolution % 4 == 0, the 4-byte path otherwise; both give the same bits.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: a NULL desc, height, out or work;
+ * diffusivity or dt not finite or < 0; r or 1 + 2 r not finite; iterations < 1; count * resolution^2 beyond int32; out partly
+ * overlapping height; work overlapping either plane.
+ * No sea-level cells are held, there is no per-cell diffusivity map (either would break the shared tables) and there is no
+ * row-stripe form. */
+typedef struct nz_hillslope_desc {
+    float diffusivity, dt;
+    int32_t iterations;
+} nz_hillslope_desc;
+size_t nz_hillslope_diffusion_work_floats(int32_t resolution, int32_t count);
+int32_t nz_hillslope_diffusion(nz_ctx *ctx, const float *height, float *out, float *work, const nz_hillslope_desc *desc,
+                               int32_t resolution, nz_handle dep, nz_handle *out_handle);
+int32_t nz_hillslope_diffusion_batch(nz_ctx *ctx, const float *height, float *out, float *work, const nz_hillslope_desc *desc,
+                                     int32_t resolution, int32_t count, nz_handle dep, nz_handle *out_handle);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

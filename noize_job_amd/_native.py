@@ -118,6 +118,11 @@ class FluvialImplicitDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("hardness", "upliftMap", "proceed", "tally")])
 
 
+class HillslopeDesc(C.Structure):
+    """nz_hillslope_desc (include/noize_hip.h): the diffusivity, the time step and the number of steps."""
+    _fields_ = [("diffusivity", C.c_float), ("dt", C.c_float), ("iterations", C.c_int32)]
+
+
 hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
 fill_p = C.POINTER(FillDesc)
@@ -125,6 +130,7 @@ drain_p = C.POINTER(DrainageDesc)
 shed_p = C.POINTER(WatershedDesc)
 order_p = C.POINTER(StreamOrderDesc)
 fimp_p = C.POINTER(FluvialImplicitDesc)
+hill_p = C.POINTER(HillslopeDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
 
@@ -255,6 +261,9 @@ SIGNATURES = {
     "nz_fluvial_implicit": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i] + _tail),
     "nz_fluvial_implicit_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i, _i] + _tail),
     "nz_debug_fluvial_implicit_sweeps": (_i, [_i]),
+    "nz_hillslope_diffusion_work_floats": (_sz, [_i, _i]),
+    "nz_hillslope_diffusion": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, hill_p, _i] + _tail),
+    "nz_hillslope_diffusion_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, hill_p, _i, _i] + _tail),
     "nz_upsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr] + _tail),
     "nz_upsample_batch": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i, _i, dev_ptr, _i] + _tail),
     "nz_downsample": (_i, [ctx_p, dev_ptr, _i, dev_ptr, _i] + _tail),

@@ -517,6 +517,13 @@ int32_t nz_launch_fluvial_implicit_pass(hipStream_t s, const unsigned char *recv
                                         unsigned char *flags_out, int res, int count, int pass, int sweeps);
 int32_t nz_launch_fluvial_implicit_finalise(hipStream_t s, const float *h, float *out, int *status, int *tally, size_t n);
 
+// hillslope diffusion (nz_hillslope.hip).  tables: inv[i] and cp[i], i = 1 .. res-2, of r (res floats each; res >= 3).
+// step: one step on `count` tiles of res^2 cells stored back to back, `in` -> `out` (the same pointer: in place; otherwise
+// disjoint), as three launches: the rows' forward sweep, their backward sweep, the columns' two sweeps
+int32_t nz_launch_hillslope_tables(hipStream_t s, float *inv, float *cp, float r, int res);
+int32_t nz_launch_hillslope_step(hipStream_t s, const float *in, float *out, const float *inv, const float *cp, float r,
+                                 int res, int count);
+
 // resampling (nz_resample.hip).  One geometry for the tile, batch and stripe forms: `c` names the coarse plane, `f` the fine
 // one; buffer row b of a plane is global row b + grow0 of its grid; fine grid = factor x coarse grid
 struct nz_up_geom {

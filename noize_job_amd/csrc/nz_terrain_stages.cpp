@@ -1,6 +1,6 @@
 // nz_terrain_stages.cpp -- the extern "C" entry points of the terrain stages the reference does not have (grid hydraulic
-// erosion, fluvial erosion, depression filling, drainage area, watershed, stream order, implicit fluvial erosion, resampling;
-// include/noize_hip.h): tile, batch,
+// erosion, fluvial erosion, depression filling, drainage area, watershed, stream order, implicit fluvial erosion, hillslope diffusion,
+// resampling; include/noize_hip.h): tile, batch,
 // read/write-pair and row-stripe forms.  The stripe geometry and the aliasing checks they share are in nz_planes.hpp.
 #include <atomic>
 #include <cmath>
@@ -981,6 +981,69 @@ extern "C" int32_t nz_fluvial_implicit_batch(nz_ctx *ctx, const float *height, c
                                              const nz_fluvial_implicit_desc *desc, int32_t resolution, int32_t count,
                                              nz_handle dep, nz_handle *out_handle) {
     return fluvial_implicit_impl(ctx, height, drainage, out, work, desc, resolution, count, dep, out_handle);
+}
+
+// ---------------------------------------------------------------------------------------------
+// hillslope diffusion: one implicit step of any size as two tridiagonal line solves (new-framework feature,
+// include/noize_hip.h, nz_hillslope.hip)
+// ---------------------------------------------------------------------------------------------
+// `work`: the tables inv and cp, one entry per line position each, the second starting 16-byte aligned behind the first.
+// The lines of every tile of a batch share them.
+namespace {
+size_t hillslope_table_floats(int res) { return ((size_t)res + 3) & ~(size_t)3; }
+}  // namespace
+
+extern "C" size_t nz_hillslope_diffusion_work_floats(int32_t resolution, int32_t count) {
+    if (resolution <= 0 || count <= 0) return 0;
+    return 2 * hillslope_table_floats(resolution);
+}
+
+static int32_t hillslope_impl(nz_ctx *ctx, const float *height, float *outp, float *work, const nz_hillslope_desc *d, int res,
+                              int count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(outp, "out is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(std::isfinite(d->diffusivity), "diffusivity is not finite");
+    NZ_REQUIRE(std::isfinite(d->dt), "dt is not finite");
+    NZ_REQUIRE(d->diffusivity >= 0.0f, "diffusivity %g < 0", (double)d->diffusivity);
+    NZ_REQUIRE(d->dt >= 0.0f, "dt %g < 0", (double)d->dt);
+    const float r = d->diffusivity * d->dt;  // the model's one product
+    NZ_REQUIRE(std::isfinite(r), "diffusivity %g x dt %g: r is not finite", (double)d->diffusivity, (double)d->dt);
+    NZ_REQUIRE(std::isfinite(1.0f + 2.0f * r), "diffusivity %g x dt %g: 1 + 2 r is not finite", (double)d->diffusivity,
+               (double)d->dt);
+    NZ_REQUIRE(d->iterations >= 1, "iterations %d < 1", d->iterations);
+    const size_t n = (size_t)count * res * res;
+    NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
+    const size_t table = hillslope_table_floats(res);
+    const bool in_place = outp == height;  // the same pointer: allowed; anything else must lie apart
+    const nz_named_plane writes[] = {{"work", work, 2 * table}, {"out", outp, n}};
+    const nz_named_plane reads[] = {{"height", in_place ? nullptr : height, n}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    if (res < 3 || r == 0.0f) {  // out = h bit for bit, by definition
+        if (!in_place) NZ_TRY(nz_launch_copy(ctx->stream, outp, height, n));
+        return nz_ctx_finish(ctx, out);
+    }
+    float *inv = work, *cp = work + table;
+    NZ_TRY(nz_launch_hillslope_tables(ctx->stream, inv, cp, r, res));
+    for (int i = 0; i < d->iterations; i++)  // the first step reads the heights, every later one runs in place on `out`
+        NZ_TRY(nz_launch_hillslope_step(ctx->stream, i ? outp : height, outp, inv, cp, r, res, count));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_hillslope_diffusion(nz_ctx *ctx, const float *height, float *out, float *work,
+                                          const nz_hillslope_desc *desc, int32_t resolution, nz_handle dep,
+                                          nz_handle *out_handle) {
+    return hillslope_impl(ctx, height, out, work, desc, resolution, 1, dep, out_handle);
+}
+
+extern "C" int32_t nz_hillslope_diffusion_batch(nz_ctx *ctx, const float *height, float *out, float *work,
+                                                const nz_hillslope_desc *desc, int32_t resolution, int32_t count,
+                                                nz_handle dep, nz_handle *out_handle) {
+    return hillslope_impl(ctx, height, out, work, desc, resolution, count, dep, out_handle);
 }
 
 // ---------------------------------------------------------------------------------------------

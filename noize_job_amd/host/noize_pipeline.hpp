@@ -1190,6 +1190,43 @@ class ImplicitFluvialStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, drainageWork, area, plane, tally;
 };
 
+// Linear hillslope diffusion, dh/dt = diffusivity * laplace(h), as implicit steps of any size (new-framework feature; the
+// model: nz_hillslope_diffusion in include/noize_hip.h): backward Euler split by direction, two tridiagonal line solves per
+// step, stable and free of oscillation for every dt, the border cells held.  It rounds the knife-edge ridges and one-cell
+// gullies ImplicitFluvialStage leaves; the evolution loop is [DepressionFillStage, ImplicitFluvialStage(dt = T),
+// HillslopeDiffusionStage(dt = T)], repeated.  A direct solve: no pass budget, no verdict, nothing read back.  The stage
+// works in place on the payload's `data` (GeneratorData and GeneratorDataBatch) and owns and resizes its `work`, the two
+// coefficient tables.  The defaults are a choice, not pinned by any picture.
+class HillslopeDiffusionStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    float diffusivity = .01f, dt = 1.f;
+    int iterations = 1;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        const size_t need = nz_hillslope_diffusion_work_floats(resolution, count);
+        if (!work || work->Length != need) work.reset(new DeviceTile(ctx, need));
+        const nz_hillslope_desc desc{diffusivity, dt, iterations};
+        nz_handle h = 0;
+        if (dynamic_cast<GeneratorDataBatch *>(d))
+            check(nz_hillslope_diffusion_batch(ctx, d->data->ptr, d->data->ptr, work->ptr, &desc, resolution, count,
+                                               dependency.id, &h), "nz_hillslope_diffusion_batch");
+        else
+            check(nz_hillslope_diffusion(ctx, d->data->ptr, d->data->ptr, work->ptr, &desc, resolution, dependency.id, &h),
+                  "nz_hillslope_diffusion");
+        jobHandle = done(h);
+    }
+    void OnDestroy() override { work.reset(); }
+
+  private:
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work;  // nz_hillslope_diffusion_work_floats floats
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;
