@@ -73,6 +73,14 @@ namespace xshazwar.noize.hip {
         public IntPtr rainMap;
     }
 
+    // the multiple-flow drainage stage's scalars and the optional rain map (nz_drainage_mfd*); IntPtr.Zero = rain everywhere
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzDrainageMfdDesc {                                                                // nz_drainage_mfd_desc
+        public float rain, seaLevel;
+        public int maxPasses, exponent;
+        public IntPtr rainMap;
+    }
+
     // the watershed stage's scalars (nz_watershed*)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzWatershedDesc {                                                                  // nz_watershed_desc

@@ -546,6 +546,66 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; plane?.Dispose(); plane = null; }
     }
 
+    // How ImplicitFluvialStage routes the drainage area: Steepest gives all of a cell's water to its steepest neighbour
+    // (DrainageAreaStage's rule), Multiple a slope-weighted share to every lower neighbour (MfdDrainageStage's).
+    public enum FlowRouting { Steepest = 0, Multiple = 1 }
+
+    // Multiple-flow drainage (new-framework feature; the model: nz_drainage_mfd in include/noize_hip.h): the flow accumulation
+    // of the payload's heights with every lower neighbour taking the share (slope / steepest slope) ^ exponent of a cell's
+    // water, normalised -- no parallel one-cell lines on hillsides, and water spreads on fans.  In every other respect the
+    // stage is DrainageAreaStage: the heights pass through, Drainage, Passes and Converged describe the last payload,
+    // seaLevel, rainMap and @out mean the same, a budget that runs out is no error and leaves the start state.  exponent:
+    // 1..16; 1 spreads most, larger values approach DrainageAreaStage.  maxPasses null means the default,
+    // 128 + resolution / 2, twice DrainageAreaStage's: the flow graph's paths are longer than the tree's.  The entry has no
+    // row-stripe form.
+    public class MfdDrainageStage : PipelineStage {
+        public float rain = 1f, seaLevel = -float.MaxValue;
+        public int exponent = 1;
+        public int? maxPasses = null;
+        public DeviceTile rainMap = null;
+        public DeviceTile @out = null;
+        DeviceTile work;                         // nz_drainage_mfd_work_floats floats; its first two int32: {passes, converged}
+        DeviceTile plane;
+        int resolution, count = 1;
+        public MfdDrainageStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Drainage => work == null ? null : @out ?? plane;
+        public int? Passes => Status(0);
+        public bool? Converged => Status(1) is int c ? c == 1 : (bool?) null;
+        int? Status(int k) {
+            if (work == null) return null;
+            jobHandle.Complete();
+            return BitConverter.SingleToInt32Bits(work.Offset(0, 2).ToArray()[k]);
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            foreach (DeviceTile m in new[] { rainMap, @out })   // before any launch
+                if (m != null && m.Length != Cells) throw new Exception($"MfdDrainageStage: a plane of {m.Length} floats does not fit the payload's {Cells}");
+            // sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+            int need = (int) (ulong) Native.nz_drainage_mfd_work_floats(resolution, count);
+            if (work == null || work.Length != need) { work?.Dispose(); work = ctx.Alloc(need); }
+            if (@out != null || (plane != null && plane.Length != Cells)) { plane?.Dispose(); plane = null; }
+            if (@out == null && plane == null) plane = ctx.Alloc(Cells);
+            NzDrainageMfdDesc desc = new NzDrainageMfdDesc {
+                rain = rain, seaLevel = seaLevel, maxPasses = maxPasses ?? 128 + resolution / 2, exponent = exponent,
+                rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero };
+            IntPtr dst = (@out ?? plane).Ptr;
+            ulong h;
+            if (d is GeneratorDataBatch b) {
+                Native.Check(Native.nz_drainage_mfd_batch(ctx.Handle, b.data.Ptr, dst, work.Ptr, ref desc, b.resolution, b.count, dependency.id, out h), "nz_drainage_mfd_batch");
+            } else {
+                Native.Check(Native.nz_drainage_mfd(ctx.Handle, d.data.Ptr, dst, work.Ptr, ref desc, d.resolution, dependency.id, out h), "nz_drainage_mfd");
+            }
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() { work?.Dispose(); work = null; plane?.Dispose(); plane = null; }
+    }
+
     // Watershed (new-framework feature; the model: nz_watershed in include/noize_hip.h): the steepest-descent tree of the
     // payload's heights read upstream -- which outlet or pit every cell drains to, how far along the river it lies, and the
     // tree itself.  The heights pass through untouched.  Once the handle completes, Basin holds the labels of the last payload
@@ -685,14 +745,19 @@ namespace xshazwar.noize.hip {
     // planes of the payload's size the caller keeps alive.  maxPasses null means the default, 64 + resolution / 4, for the
     // drainage series and for the solve each; a budget that runs out is no error: that iteration leaves the heights as they
     // were.  Drainage is the area the last iteration saw; Steps, Passes and Converged wait for the handle and read the
-    // stage's tally: the iterations applied, the solve passes that did work, and Steps == iterations.
+    // stage's tally: the iterations applied, the solve passes that did work, and Steps == iterations.  routing:
+    // FlowRouting.Multiple makes the drainage call of every iteration nz_drainage_mfd with flowExponent (1..16), chained
+    // through the same proceed word, its default budget 128 + resolution / 2; the solve still lowers each cell along its
+    // steepest receiver, only the area changes.
     public class ImplicitFluvialStage : PipelineStage {
         public int iterations = 1;
         public float erodibility = 0.05f, uplift = 0.002f, dt = 1f, rain = 1f, seaLevel = -float.MaxValue;
         public int? maxPasses = null;
         public DeviceTile rainMap = null, hardness = null, upliftMap = null;
+        public FlowRouting routing = FlowRouting.Steepest;
+        public int flowExponent = 1;
         DeviceTile work;                         // nz_fluvial_implicit_work_floats floats
-        DeviceTile drainageWork;                 // nz_drainage_area_work_floats floats; its second int32: the solve's `proceed`
+        DeviceTile drainageWork;                 // the drainage entry's work floats; its second int32: the solve's `proceed`
         DeviceTile area, plane, tally;           // the drainage, the heights' second plane, {steps applied, passes that did work}
         int resolution, count = 1;
         static readonly IntPtr Zeros = ZeroWords();   // what the tally is set to before a run; lives as long as the process
@@ -727,13 +792,18 @@ namespace xshazwar.noize.hip {
                 if (m != null && m.Length != Cells) throw new Exception($"ImplicitFluvialStage: a plane of {m.Length} floats does not fit the payload's {Cells}");
             // sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
             work = Size(work, true, (int) (ulong) Native.nz_fluvial_implicit_work_floats(resolution, count));
-            drainageWork = Size(drainageWork, true, (int) (ulong) Native.nz_drainage_area_work_floats(resolution, count));
+            bool multiple = routing == FlowRouting.Multiple;
+            drainageWork = Size(drainageWork, true, (int) (ulong) (multiple ? Native.nz_drainage_mfd_work_floats(resolution, count)
+                                                                            : Native.nz_drainage_area_work_floats(resolution, count)));
             area = Size(area, true, Cells);
             plane = Size(plane, d.write == null, Cells);
             tally = Size(tally, true, 2);
             int budget = maxPasses ?? 64 + resolution / 4;
             NzDrainageDesc drain = new NzDrainageDesc {
                 rain = rain, seaLevel = seaLevel, maxPasses = budget, rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero };
+            NzDrainageMfdDesc spread = new NzDrainageMfdDesc {
+                rain = rain, seaLevel = seaLevel, maxPasses = maxPasses ?? 128 + resolution / 2, exponent = flowExponent,
+                rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero };
             NzFluvialImplicitDesc solve = new NzFluvialImplicitDesc {
                 erodibility = erodibility, uplift = uplift, dt = dt, seaLevel = seaLevel, maxPasses = budget,
                 hardness = hardness != null ? hardness.Ptr : IntPtr.Zero, upliftMap = upliftMap != null ? upliftMap.Ptr : IntPtr.Zero,
@@ -744,11 +814,18 @@ namespace xshazwar.noize.hip {
             DeviceTile cur = d.data, other = d.write ?? plane;
             bool batch = d is GeneratorDataBatch;
             for (int i = 0; i < iterations; i++) {
-                if (batch) {
+                if (multiple && batch) {
+                    Native.Check(Native.nz_drainage_mfd_batch(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref spread, resolution, count, 0, IntPtr.Zero), "nz_drainage_mfd_batch");
+                } else if (multiple) {
+                    Native.Check(Native.nz_drainage_mfd(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref spread, resolution, 0, IntPtr.Zero), "nz_drainage_mfd");
+                } else if (batch) {
                     Native.Check(Native.nz_drainage_area_batch(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref drain, resolution, count, 0, IntPtr.Zero), "nz_drainage_area_batch");
-                    Native.Check(Native.nz_fluvial_implicit_batch(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, count, 0, out h), "nz_fluvial_implicit_batch");
                 } else {
                     Native.Check(Native.nz_drainage_area(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref drain, resolution, 0, IntPtr.Zero), "nz_drainage_area");
+                }
+                if (batch) {
+                    Native.Check(Native.nz_fluvial_implicit_batch(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, count, 0, out h), "nz_fluvial_implicit_batch");
+                } else {
                     Native.Check(Native.nz_fluvial_implicit(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, 0, out h), "nz_fluvial_implicit");
                 }
                 DeviceTile s = cur; cur = other; other = s;

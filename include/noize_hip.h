@@ -1043,6 +1043,76 @@ int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_stripe *st, 
  * restores the default).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_drainage_sweeps(int32_t sweeps);
 
+/* ---- multiple-flow drainage: slope-weighted flow accumulation (new-framework feature) ------------------------------------
+ * nz_drainage_area gives all of a cell's water to its steepest neighbour, which draws parallel one-cell lines along the
+ * eight grid directions on hillsides and cannot spread water on a fan.  This entry routes the area with multiple flow
+ * directions (Freeman 1991; Quinn et al. 1991; Holmgren 1994): every lower neighbour takes a share that grows with its
+ * slope.  The plane is a drop-in for nz_drainage_area's wherever a drainage plane is read (nz_fluvial_implicit,
+ * nz_stream_order, nz_fluvial_desc.drainageIn).
+ *
+ * THE MODEL (tests/drainage_mfd_ref.py restates it in numpy; the kernels are nz_drainage_mfd.hip):
+ *   Square tile res x res, row-major z * res + x, float32 throughout, every operation rounded once, no contraction, the
+ *   same in every float mode (nz_ctx_set_float_mode does not apply).  The outlets (global border, or h <= seaLevel), the
+ *   neighbour order W E S N SW SE NW NE, "a neighbour outside the tile does not exist" and DIAG = 0x1.6a09e6p-1f are
+ *   exactly step 1 of the fluvial model above.  rain_c = rain * rainMap[c] (one multiply), or rain without a map.
+ *   Per cell c that is not an outlet, with `best` the S of its receiver rule (the largest s_k, +0 when none):
+ *     for k ascending over the existing neighbours: d = h[c] - h[k]; s_k = d for k < 4, else d * DIAG;
+ *     neighbour k takes flow iff s_k > 0;
+ *     q_k = s_k / best (one correctly rounded division; the steepest neighbour has q == 1 exactly, nothing overflows, and
+ *       subnormal slopes work);
+ *     g_k = q_k, then exponent - 1 times g_k = g_k * q_k, left to right;
+ *     T = +0; for k ascending with g_k > 0: T = T + g_k;
+ *     w_k = g_k / T for g_k > 0 (one correctly rounded division), else the edge carries nothing -- a g_k that underflowed
+ *       to 0 is "nothing".
+ *   Outlets and cells without a lower neighbour send nothing.
+ *   The plane A: for every cell A[c] = rain_c; then, for k ascending over the existing neighbours whose weight towards c is
+ *   w > 0: A[c] = A[c] + (w * A[k]) -- product first, then sum.  The gate is w > 0, never the value of A.
+ * What follows from it:
+ *   - flow goes strictly downhill, so the graph has no cycle; a cell's value is a fixed function of higher cells' values, so
+ *     Jacobi, tile sweeps and a walk highest cell first end in the same bits;
+ *   - a cell with exactly one lower neighbour sends w == 1: it behaves as in nz_drainage_area;
+ *   - a cell's outgoing weights sum to 1 within 2^-20;
+ *   - with rain >= 0 and no map, A >= rain;
+ *   - NaN heights send and receive nothing.
+ * HEIGHT DIFFERENCES MUST BE FINITE.  An infinite s gives NaN weights, and the gate drops them: such a cell sends nothing
+ * at all, and no NaN reaches the plane, but that is not the flow of any terrain.
+ * exponent 1 is Quinn's rule without contour lengths, larger exponents concentrate the flow on the steepest neighbours
+ * (Holmgren), and the limit is nz_drainage_area.  `height` is read only.
+ *
+ * Everything that is not about weights is nz_drainage_area's: the entry enqueues one setup launch (heights -> per cell the
+ * eight INCOMING weights, eight float planes in `work`; it holds all the divisions, and after it no launch reads a
+ * height), maxPasses pass launches and one finalise launch, stream-ordered; nothing is read back.  After completion the
+ * first two int32 of `work` hold {passes that did work, converged 0/1}; the converged word is usable as
+ * nz_fluvial_implicit_desc.proceed.  The result is ALL OR NOTHING: a budget that runs out leaves rain_c in every cell and
+ * converged == 0, and that is no error.  A pass is at least one Jacobi step, so "cells of the longest path of the flow
+ * graph" + 1 always suffices; paths are longer than the steepest-descent tree's, and the hosts' default is twice
+ * DrainageAreaStage's: rain 1, seaLevel -FLT_MAX (off), exponent 1, maxPasses 128 + resolution / 2 (DESIGN.md section 4,
+ * "multiple-flow drainage").
+ * `work` = nz_drainage_mfd_work_floats(resolution, count) floats, stage-owned: status words, tile bytes, eight weight planes
+ * and one A plane (the other is `drainage`).  The _batch form runs `count` tiles stored back to back, each with its own
+ * border; every batch position equals the single-tile call bit for bit, and the status words cover the whole batch.
+ * resolution == 0 or count == 0 does nothing and returns NZ_OK.  The 16-byte path runs when every plane is 16-byte aligned
+ * and resolution % 4 == 0, the 4-byte path otherwise; both give the same bits.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: rain or seaLevel not finite (-FLT_MAX
+ * switches the sea off); rain < 0; maxPasses < 1; exponent outside 1..16; a NULL desc, height, drainage or work; drainage
+ * overlapping height, work or rainMap; work overlapping height or rainMap.
+ * There is no row-stripe form and no _rw form (the heights do not change). */
+typedef struct nz_drainage_mfd_desc {
+    float rain, seaLevel;
+    int32_t maxPasses;
+    int32_t exponent;       /* 1..16 */
+    const float *rainMap;   /* NULL: rain everywhere */
+} nz_drainage_mfd_desc;
+size_t nz_drainage_mfd_work_floats(int32_t resolution, int32_t count);
+int32_t nz_drainage_mfd(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_mfd_desc *desc,
+                        int32_t resolution, nz_handle dep, nz_handle *out);
+int32_t nz_drainage_mfd_batch(nz_ctx *ctx, const float *height, float *drainage, float *work,
+                              const nz_drainage_mfd_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                              nz_handle *out);
+/* Test hook, the twin of nz_debug_drainage_sweeps: the cap on a multiple-flow pass's on-chip sweeps per tile (process-wide;
+ * <= 0 restores the default).  Results must not change.  Returns the cap that was in force. */
+int32_t nz_debug_drainage_mfd_sweeps(int32_t sweeps);
+
 /* ---- watershed: basin labels, flow length and receiver codes of a heightmap (new-framework feature) --------------------
  * The steepest-descent tree read the other way: which outlet a cell drains to, how far along the river it lies, and the
  * tree itself.  Catchment labels give lake and basin masks and regions per river system, the flow length a distance to the

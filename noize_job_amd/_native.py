@@ -100,6 +100,13 @@ class DrainageDesc(C.Structure):
     _fields_ = [("rain", C.c_float), ("seaLevel", C.c_float), ("maxPasses", C.c_int32), ("rainMap", C.c_void_p)]
 
 
+class DrainageMfdDesc(C.Structure):
+    """nz_drainage_mfd_desc (include/noize_hip.h): the scalars of the multiple-flow drainage stage and the optional rain map
+    (a device address; None = rain everywhere)."""
+    _fields_ = [("rain", C.c_float), ("seaLevel", C.c_float), ("maxPasses", C.c_int32), ("exponent", C.c_int32),
+                ("rainMap", C.c_void_p)]
+
+
 class WatershedDesc(C.Structure):
     """nz_watershed_desc (include/noize_hip.h): the scalars of the watershed stage."""
     _fields_ = [("seaLevel", C.c_float), ("cellSize", C.c_float), ("maxPasses", C.c_int32)]
@@ -127,6 +134,7 @@ hd_p = C.POINTER(HydraulicDesc)
 fd_p = C.POINTER(FluvialDesc)
 fill_p = C.POINTER(FillDesc)
 drain_p = C.POINTER(DrainageDesc)
+mfd_p = C.POINTER(DrainageMfdDesc)
 shed_p = C.POINTER(WatershedDesc)
 order_p = C.POINTER(StreamOrderDesc)
 fimp_p = C.POINTER(FluvialImplicitDesc)
@@ -249,6 +257,10 @@ SIGNATURES = {
     "nz_drainage_stripe_round": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, stripe_p, drain_p, _i, dev_ptr, dev_ptr] + _tail),
     "nz_drainage_stripe_finalise": (_i, [ctx_p, dev_ptr, stripe_p, drain_p, dev_ptr] + _tail),
     "nz_debug_drainage_sweeps": (_i, [_i]),
+    "nz_drainage_mfd_work_floats": (_sz, [_i, _i]),
+    "nz_drainage_mfd": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, mfd_p, _i] + _tail),
+    "nz_drainage_mfd_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, mfd_p, _i, _i] + _tail),
+    "nz_debug_drainage_mfd_sweeps": (_i, [_i]),
     "nz_watershed_work_floats": (_sz, [_i, _i, _i]),
     "nz_watershed": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, dev_ptr, shed_p, _i] + _tail),
     "nz_watershed_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, dev_ptr, shed_p, _i, _i] + _tail),

@@ -474,6 +474,15 @@ int32_t nz_launch_drainage_stripe_pass(hipStream_t s, const unsigned char *donor
 int32_t nz_launch_drainage_stripe_finalise(hipStream_t s, float *a, const float *rain_map, const int *converged, float rain,
                                            const nz_geom &g);
 
+// multiple-flow drainage (nz_drainage_mfd.hip) on `count` tiles of res^2 cells stored back to back.  setup: heights -> eight
+// planes of count * res^2 incoming weights each (plane k: what neighbour k sends to the cell, +0: nothing), wts + k * count *
+// res^2.  pass: as nz_launch_drainage_pass, the weights in place of the donor bytes.  The finalise launch is
+// nz_launch_drainage_finalise
+int32_t nz_launch_drainage_mfd_setup(hipStream_t s, const float *h, float *wts, float sea, int res, int count, int exponent);
+int32_t nz_launch_drainage_mfd_pass(hipStream_t s, const float *wts, const float *rain_map, const float *a_in, float *a_out,
+                                    int *status, const unsigned char *flags_in, unsigned char *flags_out, float rain, int res,
+                                    int count, int pass, int sweeps);
+
 // watershed (nz_watershed.hip) on `count` tiles of res^2 cells stored back to back.  receivers: one receiver byte per cell
 // from the heights (the code 0..7, or 8 without a receiver).  pass `pass` of the series: label planes b_in -> b_out and,
 // when l_out is not NULL, length planes l_in -> l_out (pass 0 reads none: it derives the start state, own index and +0),

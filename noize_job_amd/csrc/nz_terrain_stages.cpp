@@ -415,7 +415,8 @@ extern "C" int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float 
 // ---------------------------------------------------------------------------------------------
 // depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
 // ---------------------------------------------------------------------------------------------
-// The five stages that iterate to rest -- this one, drainage area, watershed, stream order, implicit fluvial erosion --
+// The six stages that iterate to rest -- this one, drainage area, multiple-flow drainage, watershed, stream order, implicit
+// fluvial erosion --
 // share what follows.
 //
 // `work` in floats begins the same way for all of them: 16 status words (nz_relax_pass.hpp; the rest spare) and two
@@ -450,7 +451,7 @@ struct relax_work {
     int *ints(size_t n) { return reinterpret_cast<int *>(floats(n)); }
 };
 
-// The sweep cap of a stage: 16 for each of the five (measured per stage, 4 to 64: DESIGN.md section 4).  The debug entry
+// The sweep cap of a stage: 16 for each of the six (measured per stage, 4 to 64: DESIGN.md section 4).  The debug entry
 // may be called while another thread runs an entry; it returns the cap before, and a value < 1 puts the default back.
 constexpr int RELAX_SWEEPS = 16;
 struct sweep_cap {
@@ -751,6 +752,72 @@ extern "C" int32_t nz_drainage_stripe_finalise(nz_ctx *ctx, float *a, const nz_s
     nz_ctx_arm_last_launch(ctx);
     NZ_TRY(nz_launch_drainage_stripe_finalise(ctx->stream, a, desc->rainMap, converged, desc->rain, nz_geom_from_stripe(*st)));
     return nz_ctx_finish(ctx, out);
+}
+
+// ---------------------------------------------------------------------------------------------
+// multiple-flow drainage (new-framework feature, include/noize_hip.h, nz_drainage_mfd.hip)
+// ---------------------------------------------------------------------------------------------
+// `work`: the head, eight planes of incoming weights and one A plane; the other A plane is the caller's.  Everything that
+// is not about weights is drainage_impl's; the finalise launch is the same one.
+namespace {
+struct drainage_mfd_work { relax_work hd; float *wts; float *a; };
+drainage_mfd_work drainage_mfd_work_of(float *work, const relax_shape &sh) {
+    drainage_mfd_work k{relax_work(work, sh), nullptr, nullptr};
+    k.wts = k.hd.floats(8 * sh.n);
+    k.a = k.hd.floats(sh.n);
+    return k;
+}
+sweep_cap drainage_mfd_sweeps;
+}  // namespace
+
+extern "C" size_t nz_drainage_mfd_work_floats(int32_t resolution, int32_t count) {
+    return resolution > 0 && count > 0 ? drainage_mfd_work_of(nullptr, tile_shape(resolution, count)).hd.total : 0;
+}
+
+extern "C" int32_t nz_debug_drainage_mfd_sweeps(int32_t sweeps) { return drainage_mfd_sweeps.exchange(sweeps); }
+
+static int32_t drainage_mfd_impl(nz_ctx *ctx, const float *height, float *drainage, float *work, const nz_drainage_mfd_desc *d,
+                                 int res, int count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(drainage, "drainage is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(std::isfinite(d->rain), "rain is not finite");
+    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(d->rain >= 0.0f, "rain %g < 0", (double)d->rain);
+    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    NZ_REQUIRE(d->exponent >= 1 && d->exponent <= 16, "exponent %d outside 1..16", d->exponent);
+    const relax_shape sh = tile_shape(res, count);
+    const drainage_mfd_work k = drainage_mfd_work_of(work, sh);
+    const size_t n = sh.n;
+    const nz_named_plane writes[] = {{"drainage", drainage, n}, {"work", work, k.hd.total}};
+    const nz_named_plane reads[] = {{"height", height, n}, {"rainMap", d->rainMap, n}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    float *planes[2] = {drainage, k.a};
+    const int sweeps = drainage_mfd_sweeps.load();
+    NZ_TRY(nz_launch_drainage_mfd_setup(ctx->stream, height, k.wts, d->seaLevel, res, count, d->exponent));
+    return run_tile_series(
+        ctx, out, d->maxPasses, k.hd,
+        [&](int p, const unsigned char *flags_in, unsigned char *flags_out) {  // pass p writes plane p & 1
+            return nz_launch_drainage_mfd_pass(ctx->stream, k.wts, d->rainMap, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1],
+                                               k.hd.status, flags_in, flags_out, d->rain, res, count, p, sweeps);
+        },
+        // a series at rest holds the fixed point in both planes, so `drainage` has it whichever plane was written last
+        [&] { return nz_launch_drainage_finalise(ctx->stream, drainage, d->rainMap, k.hd.status, d->rain, n); });
+}
+
+extern "C" int32_t nz_drainage_mfd(nz_ctx *ctx, const float *height, float *drainage, float *work,
+                                   const nz_drainage_mfd_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out) {
+    return drainage_mfd_impl(ctx, height, drainage, work, desc, resolution, 1, dep, out);
+}
+
+extern "C" int32_t nz_drainage_mfd_batch(nz_ctx *ctx, const float *height, float *drainage, float *work,
+                                         const nz_drainage_mfd_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                                         nz_handle *out) {
+    return drainage_mfd_impl(ctx, height, drainage, work, desc, resolution, count, dep, out);
 }
 
 // ---------------------------------------------------------------------------------------------

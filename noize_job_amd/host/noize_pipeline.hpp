@@ -967,6 +967,69 @@ class DrainageAreaStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, plane;
 };
 
+// How ImplicitFluvialStage routes the drainage area: Steepest gives all of a cell's water to its steepest neighbour
+// (DrainageAreaStage's rule), Multiple a slope-weighted share to every lower neighbour (MfdDrainageStage's).
+enum class FlowRouting { Steepest, Multiple };
+
+// Multiple-flow drainage (new-framework feature; the model: nz_drainage_mfd in include/noize_hip.h): the flow accumulation
+// of the payload's heights with every lower neighbour taking the share (slope / steepest slope) ^ exponent of a cell's
+// water, normalised -- no parallel one-cell lines on hillsides, and water spreads on fans.  In every other respect the
+// stage is DrainageAreaStage: the heights pass through, drainage(), passes() and converged() describe the last payload,
+// seaLevel, rainMap and out mean the same, a budget that runs out is no error and leaves the start state.  exponent: 1..16;
+// 1 spreads most, larger values approach DrainageAreaStage.  maxPasses < 1 means the default, 128 + resolution / 2, twice
+// DrainageAreaStage's: the flow graph's paths are longer than the tree's.  The entry has no row-stripe form.
+class MfdDrainageStage : public PipelineStage {
+  public:
+    using PipelineStage::PipelineStage;
+    float rain = 1.f, seaLevel = -3.402823466e+38f;
+    int exponent = 1;
+    int maxPasses = 0;  // < 1: 128 + resolution / 2
+    const DeviceTile *rainMap = nullptr;
+    DeviceTile *out = nullptr;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        for (const DeviceTile *m : {rainMap, static_cast<const DeviceTile *>(out)})  // before any launch
+            if (m && m->Length != drainageLength()) throw std::runtime_error("MfdDrainageStage: a plane does not fit the payload");
+        // sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
+        const size_t need = nz_drainage_mfd_work_floats(resolution, count);
+        if (!work || work->Length != need) work.reset(new DeviceTile(ctx, need));
+        if (out) plane.reset();
+        else if (!plane || plane->Length != drainageLength()) plane.reset(new DeviceTile(ctx, drainageLength()));
+        const nz_drainage_mfd_desc desc{rain, seaLevel, maxPasses >= 1 ? maxPasses : 128 + resolution / 2, exponent,
+                                        rainMap ? rainMap->ptr : nullptr};
+        float *dst = out ? out->ptr : plane->ptr;
+        nz_handle h = 0;
+        if (auto *b = dynamic_cast<GeneratorDataBatch *>(d)) {
+            check(nz_drainage_mfd_batch(ctx, b->data->ptr, dst, work->ptr, &desc, b->resolution, b->count, dependency.id, &h),
+                  "nz_drainage_mfd_batch");
+        } else {
+            check(nz_drainage_mfd(ctx, d->data->ptr, dst, work->ptr, &desc, d->resolution, dependency.id, &h), "nz_drainage_mfd");
+        }
+        jobHandle = done(h);
+    }
+    const float *drainage() const { return !work ? nullptr : out ? out->ptr : plane->ptr; }  // nullptr before a payload
+    size_t drainageLength() const { return (size_t)count * resolution * resolution; }
+    int passes() const { return status(0); }                // -1 before the first run
+    bool converged() const { return status(1) == 1; }
+    void OnDestroy() override { work.reset(); plane.reset(); }
+
+  private:
+    int status(int k) const {
+        if (!work) return -1;
+        jobHandle.Complete();
+        int32_t words[2];
+        check(nz_tile_download(ctx, work->ptr, reinterpret_cast<float *>(words), 2, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[k];
+    }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, plane;  // work: nz_drainage_mfd_work_floats floats; its first two int32: {passes, converged}
+};
+
 // Watershed (new-framework feature; the model: nz_watershed in include/noize_hip.h): the steepest-descent tree of the
 // payload's heights read upstream -- which outlet or pit every cell drains to, how far along the river it lies, and the
 // tree itself.  The heights pass through untouched.  Once the handle completes, basin() holds the labels of the last
@@ -1110,7 +1173,9 @@ class StreamOrderStage : public PipelineStage {
 // payload's size the caller keeps alive.  maxPasses < 1 means the default, 64 + resolution / 4, for the drainage series and
 // for the solve each; a budget that runs out is no error: that iteration leaves the heights as they were.  drainage() is
 // the area the last iteration saw; steps(), passes() and converged() wait for the handle and read the stage's tally: the
-// iterations applied, the solve passes that did work, and steps() == iterations.
+// iterations applied, the solve passes that did work, and steps() == iterations.  routing: FlowRouting::Multiple makes the
+// drainage call of every iteration nz_drainage_mfd with flowExponent (1..16), chained through the same proceed word, its
+// default budget 128 + resolution / 2; the solve still lowers each cell along its steepest receiver, only the area changes.
 class ImplicitFluvialStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;
@@ -1118,6 +1183,8 @@ class ImplicitFluvialStage : public PipelineStage {
     float erodibility = .05f, uplift = .002f, dt = 1.f, rain = 1.f, seaLevel = -3.402823466e+38f;
     int maxPasses = 0;  // < 1: 64 + resolution / 4
     const DeviceTile *rainMap = nullptr, *hardness = nullptr, *upliftMap = nullptr;
+    FlowRouting routing = FlowRouting::Steepest;
+    int flowExponent = 1;
     void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
         auto *g = dynamic_cast<GeneratorData *>(requirements.data);
         if (!g) throw std::runtime_error("Unhandled stageio");
@@ -1128,13 +1195,16 @@ class ImplicitFluvialStage : public PipelineStage {
             if (m && m->Length != cells()) throw std::runtime_error("ImplicitFluvialStage: a plane does not fit the payload");
         // sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
         size(work, nz_fluvial_implicit_work_floats(resolution, count));
-        size(drainageWork, nz_drainage_area_work_floats(resolution, count));
+        const bool multiple = routing == FlowRouting::Multiple;
+        size(drainageWork, multiple ? nz_drainage_mfd_work_floats(resolution, count) : nz_drainage_area_work_floats(resolution, count));
         size(area, cells());
         if (d->write) plane.reset();
         else size(plane, cells());
         size(tally, 2);
         const int budget = maxPasses >= 1 ? maxPasses : 64 + resolution / 4;
         const nz_drainage_desc drain{rain, seaLevel, budget, rainMap ? rainMap->ptr : nullptr};
+        const nz_drainage_mfd_desc spread{rain, seaLevel, maxPasses >= 1 ? maxPasses : 128 + resolution / 2, flowExponent,
+                                          rainMap ? rainMap->ptr : nullptr};
         const nz_fluvial_implicit_desc solve{erodibility, uplift, dt, seaLevel, budget, hardness ? hardness->ptr : nullptr,
                                              upliftMap ? upliftMap->ptr : nullptr,
                                              reinterpret_cast<const int32_t *>(drainageWork->ptr) + 1,
@@ -1146,14 +1216,21 @@ class ImplicitFluvialStage : public PipelineStage {
         DeviceTile *cur = d->data, *other = d->write ? d->write : plane.get();
         auto *b = dynamic_cast<GeneratorDataBatch *>(d);
         for (int i = 0; i < iterations; i++) {
-            if (b) {
+            if (multiple) {
+                check(b ? nz_drainage_mfd_batch(ctx, cur->ptr, area->ptr, drainageWork->ptr, &spread, resolution, count, 0, nullptr)
+                        : nz_drainage_mfd(ctx, cur->ptr, area->ptr, drainageWork->ptr, &spread, resolution, 0, nullptr),
+                      "nz_drainage_mfd");
+            } else if (b) {
                 check(nz_drainage_area_batch(ctx, cur->ptr, area->ptr, drainageWork->ptr, &drain, resolution, count, 0, nullptr),
                       "nz_drainage_area_batch");
-                check(nz_fluvial_implicit_batch(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, count, 0, &h),
-                      "nz_fluvial_implicit_batch");
             } else {
                 check(nz_drainage_area(ctx, cur->ptr, area->ptr, drainageWork->ptr, &drain, resolution, 0, nullptr),
                       "nz_drainage_area");
+            }
+            if (b) {
+                check(nz_fluvial_implicit_batch(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, count, 0, &h),
+                      "nz_fluvial_implicit_batch");
+            } else {
                 check(nz_fluvial_implicit(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, 0, &h),
                       "nz_fluvial_implicit");
             }

@@ -1055,6 +1055,7 @@ class DrainageAreaStage(PipelineStage):
     that receives the drainage; without it the stage owns the plane."""
 
     SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+    _ENTRIES = ("nz_drainage_area", "nz_drainage_area_batch", "nz_drainage_area_work_floats")  # MfdDrainageStage has its own
 
     def __init__(self, ctx, rain=1.0, seaLevel=SEA_OFF, maxPasses=None, rainMap=None, out=None):
         super().__init__(ctx)
@@ -1067,6 +1068,11 @@ class DrainageAreaStage(PipelineStage):
         self.count = 0
         self.work = None    # nz_drainage_area_work_floats floats; its first two int32: {passes, converged}
         self._plane = None  # the stage's own drainage plane (no `out`)
+
+    def _desc(self, rainMap):
+        """The entry's descriptor for the current payload (MfdDrainageStage has its own)."""
+        budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
+        return N.DrainageDesc(self.rain, self.seaLevel, budget, rainMap)
 
     def DisposeArrays(self):
         for t in (self.work, self._plane):
@@ -1109,9 +1115,10 @@ class DrainageAreaStage(PipelineStage):
         n = self.count * self.resolution * self.resolution
         for name, m in (("rainMap", self.rainMap), ("out", self.out)):  # before any launch
             if m is not None and m.Length != n:
-                raise ValueError("DrainageAreaStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
+                raise ValueError("%s.%s holds %d floats, the payload %d" % (type(self).__name__, name, m.Length, n))
         # sized on (resolution, count) like DepressionFillStage's: the per-tile bytes depend on the number of 64 x 16 tiles
-        need = N.lib.nz_drainage_area_work_floats(self.resolution, self.count)
+        single, batched, floats = self._ENTRIES
+        need = getattr(N.lib, floats)(self.resolution, self.count)
         if self.work is None or self.work.Length != need:
             if self.work is not None and self.work.IsCreated:
                 self.work.Dispose()
@@ -1123,17 +1130,43 @@ class DrainageAreaStage(PipelineStage):
             if self._plane is not None:
                 self._plane.Dispose()
             self._plane = self.ctx.alloc(n)
-        budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
-        desc = N.DrainageDesc(self.rain, self.seaLevel, budget, self.rainMap.ptr if self.rainMap is not None else None)
+        desc = self._desc(self.rainMap.ptr if self.rainMap is not None else None)
         if isinstance(d, GeneratorDataBatch):
-            self.jobHandle = self.ctx.call("nz_drainage_area_batch", d.data.ptr, self.drainage.ptr, self.work.ptr,
+            self.jobHandle = self.ctx.call(batched, d.data.ptr, self.drainage.ptr, self.work.ptr,
                                            C.byref(desc), d.resolution, d.count, dep=dependency)
         else:
-            self.jobHandle = self.ctx.call("nz_drainage_area", d.data.ptr, self.drainage.ptr, self.work.ptr, C.byref(desc),
+            self.jobHandle = self.ctx.call(single, d.data.ptr, self.drainage.ptr, self.work.ptr, C.byref(desc),
                                            d.resolution, dep=dependency)
 
     def OnDestroy(self):
         self.DisposeArrays()
+
+
+class FlowRouting(enum.IntEnum):  # new-framework: how ImplicitFluvialStage routes the drainage area
+    Steepest = 0  # nz_drainage_area: all of a cell's water to its steepest neighbour
+    Multiple = 1  # nz_drainage_mfd: every lower neighbour takes a slope-weighted share
+
+
+class MfdDrainageStage(DrainageAreaStage):
+    """Multiple-flow drainage (new-framework feature; the model is the comment block of nz_drainage_mfd in
+    include/noize_hip.h): the flow accumulation of the payload's heights with every lower neighbour taking a share
+    (slope / steepest slope) ^ exponent of a cell's water, normalised -- no parallel one-cell lines on hillsides, and water
+    spreads on fans.  The stage is DrainageAreaStage in every other respect: the heights pass through, `drainage`, `passes`
+    and `converged` describe the last payload, seaLevel, rainMap and out mean the same, a budget that runs out leaves the
+    start state and converged False, and the plane is read wherever a drainage plane is.
+
+    exponent: 1..16; 1 spreads most, larger values approach DrainageAreaStage.  maxPasses: None means
+    128 + resolution // 2, twice DrainageAreaStage's: the flow graph's paths are longer than the tree's."""
+
+    _ENTRIES = ("nz_drainage_mfd", "nz_drainage_mfd_batch", "nz_drainage_mfd_work_floats")
+
+    def __init__(self, ctx, rain=1.0, seaLevel=DrainageAreaStage.SEA_OFF, exponent=1, maxPasses=None, rainMap=None, out=None):
+        super().__init__(ctx, rain, seaLevel, maxPasses, rainMap, out)
+        self.exponent = exponent
+
+    def _desc(self, rainMap):
+        budget = self.maxPasses if self.maxPasses is not None else 128 + self.resolution // 2
+        return N.DrainageMfdDesc(self.rain, self.seaLevel, budget, self.exponent, rainMap)
 
 
 class WatershedStage(PipelineStage):
@@ -1372,13 +1405,18 @@ class ImplicitFluvialStage(PipelineStage):
     the solve, each; None means 64 + resolution // 4.  A budget that runs out is no error: that iteration leaves the
     heights as they were, and `steps` stays below `iterations`.
 
+    routing: FlowRouting.Steepest (the default) or FlowRouting.Multiple; with Multiple the drainage call of every iteration
+    is nz_drainage_mfd with flowExponent (1..16), chained through the same proceed word, and its budget is
+    128 + resolution // 2 when maxPasses is None.  The solve still lowers each cell along its steepest receiver: only the
+    area A changes.
+
     After the handle completes: `drainage` is the drainage area the last iteration saw, `steps` the iterations that were
     applied, `passes` the solve passes that did work over all of them, `converged` whether steps == iterations."""
 
     SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
 
     def __init__(self, ctx, iterations=1, erodibility=0.05, uplift=0.002, dt=1.0, rain=1.0, seaLevel=SEA_OFF, maxPasses=None,
-                 rainMap=None, hardness=None, upliftMap=None):
+                 rainMap=None, hardness=None, upliftMap=None, routing=FlowRouting.Steepest, flowExponent=1):
         super().__init__(ctx)
         self.iterations = iterations
         self.erodibility = erodibility
@@ -1390,10 +1428,12 @@ class ImplicitFluvialStage(PipelineStage):
         self.rainMap = rainMap
         self.hardness = hardness
         self.upliftMap = upliftMap
+        self.routing = FlowRouting(routing)
+        self.flowExponent = flowExponent
         self.resolution = 0
         self.count = 0
         self.work = None           # nz_fluvial_implicit_work_floats floats
-        self.drainageWork = None   # nz_drainage_area_work_floats floats; its second int32: the solve's `proceed`
+        self.drainageWork = None   # the drainage entry's work floats; its second int32: the solve's `proceed`
         self._area = None          # the drainage plane
         self._plane = None         # the heights' second plane, for a payload without a WRITE plane
         self._tally = None         # two int32: {steps applied, passes that did work}
@@ -1455,22 +1495,33 @@ class ImplicitFluvialStage(PipelineStage):
                 raise ValueError("ImplicitFluvialStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
         # sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
         self.work = self._size(self.work, True, N.lib.nz_fluvial_implicit_work_floats(self.resolution, self.count))
-        self.drainageWork = self._size(self.drainageWork, True, N.lib.nz_drainage_area_work_floats(self.resolution, self.count))
+        multiple = self.routing == FlowRouting.Multiple
+        if multiple:
+            need = N.lib.nz_drainage_mfd_work_floats(self.resolution, self.count)
+        else:
+            need = N.lib.nz_drainage_area_work_floats(self.resolution, self.count)
+        self.drainageWork = self._size(self.drainageWork, True, need)
         self._area = self._size(self._area, True, n)
         self._plane = self._size(self._plane, d.write is None, n)
         self._tally = self._size(self._tally, True, 2, np.int32)
         budget = self.maxPasses if self.maxPasses is not None else 64 + self.resolution // 4
         opt = lambda m: m.ptr if m is not None else None
-        drain = N.DrainageDesc(self.rain, self.seaLevel, budget, opt(self.rainMap))
+        batch = isinstance(d, GeneratorDataBatch)
+        if multiple:
+            mfd_budget = self.maxPasses if self.maxPasses is not None else 128 + self.resolution // 2
+            drain = N.DrainageMfdDesc(self.rain, self.seaLevel, mfd_budget, self.flowExponent, opt(self.rainMap))
+            entry = "nz_drainage_mfd_batch" if batch else "nz_drainage_mfd"
+        else:
+            drain = N.DrainageDesc(self.rain, self.seaLevel, budget, opt(self.rainMap))
+            entry = "nz_drainage_area_batch" if batch else "nz_drainage_area"
         solve = N.FluvialImplicitDesc(self.erodibility, self.uplift, self.dt, self.seaLevel, budget, opt(self.hardness),
                                       opt(self.upliftMap), self.drainageWork.ptr + 4, self._tally.ptr)
-        batch = isinstance(d, GeneratorDataBatch)
         tail = (d.resolution, d.count) if batch else (d.resolution,)
         # the heights ping-pong between the payload's plane and the WRITE plane (or the stage's own)
         cur, other = d.data, d.write if d.write is not None else self._plane
         self.jobHandle = self.ctx.call("nz_tile_upload", self._tally.ptr, self._zeros.ctypes.data, 2, dep=dependency)
         for _ in range(self.iterations):
-            self.ctx.call("nz_drainage_area_batch" if batch else "nz_drainage_area", cur.ptr, self._area.ptr,
+            self.ctx.call(entry, cur.ptr, self._area.ptr,
                           self.drainageWork.ptr, C.byref(drain), *tail, handle=False)
             self.jobHandle = self.ctx.call("nz_fluvial_implicit_batch" if batch else "nz_fluvial_implicit", cur.ptr,
                                            self._area.ptr, other.ptr, self.work.ptr, C.byref(solve), *tail)
