@@ -416,11 +416,12 @@ constexpr int NZ_T1_N = 292, NZ_T2_N = 580;
 // limit (NaN included) take the direct evaluation, which follows the reference's arithmetic wherever it leads.
 constexpr float NZ_TAB_LIMIT = 1048576.0f;
 
-// (returns snoise / 2: see the end)
-__device__ __forceinline__ float snoise2_tab(float vx, float vy, const int *s_t1, const float4 *s_t2) {
-    const float Cx = 0.211324865405187f, Cy = 0.366025403784439f, Cz = -0.577350269189626f;
-    float s = vx * Cy + vy * Cy;
-    float fx = floorf(vx + s), fy = floorf(vy + s);
+// (returns snoise / 2: see the end).  (ux, uy) are the skewed coordinates v + s of (vx, vy): snoise2_tab below forms them
+// with the reference's operations, the power-of-two octave ladder scales octave 0's (fractal_simplex_tab_kernel).
+__device__ __forceinline__ float snoise2_tab_skewed(float vx, float vy, float ux, float uy, const int *s_t1,
+                                                    const float4 *s_t2) {
+    const float Cx = 0.211324865405187f, Cz = -0.577350269189626f;
+    float fx = floorf(ux), fy = floorf(uy);
     float t = fx * Cx + fy * Cx;
     float x0x = vx - fx + t, x0y = vy - fy + t;
     bool gt = x0x > x0y;
@@ -458,6 +459,11 @@ __device__ __forceinline__ float snoise2_tab(float vx, float vy, const int *s_t1
     // RN(65 n) and RN(1 + v) / 2 == RN(0.5 + v / 2) (where v is small enough for a halving to lose a denormal bit, both
     // forms return 0.5).  The caller adds the 0.5: one multiply and one add instead of two multiplies and an add.
     return 65.0f * (m0 * q0 + m1 * q1 + m2 * q2);
+}
+__device__ __forceinline__ float snoise2_tab(float vx, float vy, const int *s_t1, const float4 *s_t2) {
+    const float Cy = 0.366025403784439f;
+    float s = vx * Cy + vy * Cy;
+    return snoise2_tab_skewed(vx, vy, vx + s, vy + s, s_t1, s_t2);
 }
 __device__ __forceinline__ float rectify_half(float half_v) { return 0.5f + half_v; }  // rectify(v), given v / 2
 
@@ -535,6 +541,16 @@ __device__ __forceinline__ void octave_add(float &t, float &w, float a, float v,
     }
 }
 
+// The guard of the power-of-two octave ladder (fractal_simplex_tab_kernel has the proof): the table holds a ladder, every
+// octave of the row stays inside the tables' range, and every coordinate of this thread's cells is zero or at least
+// oct.ladder_lo in magnitude -- for all active lanes of the wave, so the branch on it is uniform.  A NaN fails.
+template <int VEC>
+__device__ __forceinline__ bool ladder_row(const nz_octave_table &oct, float fmax, float reach, const float (&xi)[VEC], float zi) {
+    bool ok = oct.ladder_lo > 0.0f && fmax * reach < NZ_TAB_LIMIT && (zi == 0.0f || fabsf(zi) >= oct.ladder_lo);
+#pragma unroll
+    for (int c = 0; c < VEC; c++) ok = ok && (xi[c] == 0.0f || fabsf(xi[c]) >= oct.ladder_lo);
+    return __builtin_amdgcn_ballot_w64(!ok) == 0;
+}
 
 template <int VEC, bool FAST, int SHAPE>
 __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restrict__ dst, int rows, int cols, int pitch,
@@ -598,6 +614,45 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
             }
 #pragma unroll
             for (int c = 0; c < VEC; c++) t[c] += bias;
+        } else if (!FAST && oct.n > 0 && ladder_row(oct, p.fmax, reach, xi, zi)) {
+            // Power-of-two octave ladder (oct.ladder_lo > 0: every oct.f[i] is 2^k, f > 0).  The reference skews octave i as
+            //   vx = f x, vz = f z;  s = vx Cy + vz Cy;  ux = vx + s, uz = vz + s                     (snoise2_tab)
+            // and this loop as ux = f Ux, uz = f Uz from the row's Ux = x + s0, Uz = z + s0, s0 = x Cy + z Cy.  The same
+            // bits, operation by operation, because RN(2^k r) == 2^k RN(r) for every real r as long as neither side is
+            // subnormal or overflows (the significand is rounded, the exponent only shifted):
+            //   vx Cy = RN(f x Cy) = f RN(x Cy);  s = RN(f (x Cy + z Cy)) = f s0;  ux = RN(f (x + s0)) = f Ux; uz alike,
+            // f x and f z being exact.  A zero scales exactly with its sign, so it needs no bound.  What ladder_row has shown:
+            //   * overflow: fmax |c| < NZ_TAB_LIMIT = 2^20 for every coordinate c of the wave's cells, fmax >= f[0] = 1 the
+            //     largest f, so every intermediate, scaled or not, stays below (1 + 2 Cy) 2^20 (1 + 2^-22) < 2^22;
+            //   * subnormals: every nonzero c has |c| >= lo = 2^-64 / g, g = min(1, min f[i]) (the host's oct.ladder_lo, so
+            //     descending ladders are covered).  A product c Cy is then > lo / 4.  A sum a + b of two floats is an
+            //     integer multiple of the smaller one's ulp, so it is 0 (x Cy = -(z Cy): exact cancellation) or at least
+            //     that ulp, > 2^-24 min(|a|, |b|): s0 is 0 or > 2^-26 lo, and Ux, Uz are 0 or > 2^-50 lo.  Times any
+            //     f[i] >= g that is > 2^-114: nothing nonzero comes within 2^12 of the subnormal range, in either form.
+            // NaN fails every comparison of ladder_row, and a wave with one lane outside these bounds takes the loops below
+            // as a whole: the ballot costs such a wave its speed-up, never a bit.  From the floors on the octave is
+            // snoise2_tab's, instruction for instruction; per pair of cells 7 multiplies open it instead of 12 operations.
+            const float Cy = 0.366025403784439f;
+            float Ux[VEC], Uz[VEC];
+            const float zs = zi * Cy;
+#pragma unroll
+            for (int c = 0; c < VEC; c++) {
+                const float s0 = xi[c] * Cy + zs;
+                Ux[c] = xi[c] + s0;
+                Uz[c] = zi + s0;
+            }
+            float fn = oct.f[0], an = oct.a[0];
+            for (int i = 0; i < oct.n; i++) {
+                f = fn; a = an;
+                const int nx = min(i + 1, NZ_OCT_TAB - 1);
+                fn = oct.f[nx]; an = oct.a[nx];
+                float zV = f * zi;
+#pragma unroll
+                for (int c = 0; c < VEC; c++) {
+                    float xV = f * xi[c];
+                    octave_add<SHAPE>(t[c], w[c], a, rectify_half(snoise2_tab_skewed(xV, zV, f * Ux[c], f * Uz[c], s_t1, s_t2)), rp);
+                }
+            }
         } else if (p.fmax * reach < NZ_TAB_LIMIT && oct.n > 0) {
             // ... and the host has run the wave-uniform recurrence (nz_octave_table: the same fp32 operations, so the same
             // bits): f and a are scalar loads from the kernel arguments, issued one octave ahead of their use

@@ -166,6 +166,11 @@ constexpr int NZ_OCT_TAB = 16;
 struct nz_octave_table {
     float f[NZ_OCT_TAB], a[NZ_OCT_TAB];
     int n = 0;  // entries filled: the octave count, or 0 (no table)
+    // Power-of-two ladder (appended: kernels that ignore it keep their argument layout).  > 0 when the table is filled and
+    // every f[i] is a positive, normal, exact power of two (stepdown 2, 4 or 0.5 without detune): then octave i's skewed
+    // simplex coordinates are octave 0's times f[i], bit for bit, for coordinates that are zero or at least this large in
+    // magnitude: 2^-64 / min(1, min f[i]) (fractal_simplex_tab_kernel has the proof).  0: no ladder.
+    float ladder_lo = 0.0f;
 };
 struct nz_fractal_params : nz_fractal_kparams {
     nz_ridge_params ridge;  // NZ_SHAPE_RIDGED only

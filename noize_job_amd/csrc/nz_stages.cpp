@@ -49,6 +49,15 @@ static void fractal_octave_table(float amp, float G, float stepdown, float detun
         a *= G;
     }
     t->n = octaves;
+    // the power-of-two ladder flag: every frequency in use is 2^k (frexp's mantissa is exactly 0.5), positive and normal
+    float g = 1.0f;
+    for (int i = 0; i < octaves; i++) {
+        int e;
+        const float fi = t->f[i];
+        if (!(std::isfinite(fi) && fi >= 0x1p-126f && frexpf(fi, &e) == 0.5f)) return;
+        if (fi < g) g = fi;
+    }
+    t->ladder_lo = 0x1p-64f / g;  // exact: at most 2^62
 }
 
 static int32_t fractal_impl(nz_ctx *ctx, hipStream_t stream, int noiseType, float *dst, int rows, int cols, int pitch,

@@ -1,7 +1,8 @@
 #!/bin/bash
 # tools/kernel_isa.sh <file.hip|.cpp> [extra hipcc flags] -- compiles one source of noize_job_amd/csrc for gfx950 with the
 # Makefile's flags, keeps the device assembly in /tmp/isa/<name>.s and prints, per kernel, VGPRs / SGPRs / spills / scratch /
-# LDS / occupancy (the .amdhsa metadata) -- what DESIGN.md quotes for register budgets and spills.
+# LDS / occupancy (the .amdhsa metadata) -- what DESIGN.md quotes for register budgets and spills -- and the VALU
+# instructions in the kernel's text (static_valu) and in each of its steady loops (loop_valu, in code order).
 set -e
 src=$1; shift
 name=$(basename "${src%.*}")
@@ -33,8 +34,20 @@ for n, d, b in zip(names, dem, blocks):
     # VALU instructions in the kernel body (static count)
     m = re.search(r'\n' + re.escape(n) + r':(.*?)s_endpgm', txt, re.S)
     body = m.group(1) if m else ''
+    is_valu = re.compile(r'\s+v_(?!readlane|readfirstlane)')
     valu = len(re.findall(r'\n\s+v_(?!readlane|readfirstlane)', body))
-    print('%-72s vgpr %3s sgpr %3s lds %6s code %6s scratch %4s occ %2s sgpr_spill %3s vgpr_spill %3s static_valu %5d' % (
+    # the steady loops: VALU instructions of every single-block loop (a label, no other label, a branch back to it) that
+    # has at least 32 of them, in code order
+    loops, label, count = [], None, 0
+    for line in body.split('\n'):
+        m = re.match(r'(\.LBB\w+):', line)
+        if m:
+            label, count = m.group(1), 0
+        elif is_valu.match(line):
+            count += 1
+        elif label and re.match(r'\s+s_c?branch\w*\s+' + re.escape(label) + r'\s*$', line):
+            if count >= 32: loops.append(count)
+    print('%-72s vgpr %3s sgpr %3s lds %6s code %6s scratch %4s occ %2s sgpr_spill %3s vgpr_spill %3s static_valu %5d loop_valu %s' % (
         d[:72], g('NumVgprs'), g('TotalNumSgprs'), g('LDSByteSize'), g('codeLenInByte'), g('ScratchSize'), g('Occupancy'),
-        spills.get(n, ('-', '-'))[0], spills.get(n, ('-', '-'))[1], valu))
+        spills.get(n, ('-', '-'))[0], spills.get(n, ('-', '-'))[1], valu, ','.join(map(str, loops)) or '-'))
 PY
