@@ -105,6 +105,16 @@ namespace xshazwar.noize.hip {
         public IntPtr hardness, upliftMap, proceed, tally;
     }
 
+    // the multiple-flow implicit fluvial step: NzFluvialImplicitDesc with the flow exponent behind maxPasses
+    // (nz_fluvial_implicit_mfd*); IntPtr.Zero = option off
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzFluvialImplicitMfdDesc {                                                         // nz_fluvial_implicit_mfd_desc
+        public float erodibility, uplift, dt, seaLevel;
+        public int maxPasses;
+        public int exponent;
+        public IntPtr hardness, upliftMap, proceed, tally;
+    }
+
     // the hillslope diffusion step's scalars (nz_hillslope_diffusion*)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzHillslopeDesc {                                                                  // nz_hillslope_desc

@@ -841,6 +841,99 @@ namespace xshazwar.noize.hip {
         }
     }
 
+    public class MfdFluvialStage : PipelineStage {
+        // Multiple-flow implicit stream-power erosion (new-framework feature; the model: nz_fluvial_implicit_mfd in
+        // include/noize_hip.h): ImplicitFluvialStage's step taken along EVERY lower neighbour of a cell, with the weights of
+        // MfdDrainageStage -- the fan the water is spread over is what erodes, where ImplicitFluvialStage with
+        // FlowRouting.Multiple cuts along the one steepest receiver.  Per iteration the stage computes the multiple-flow
+        // drainage of the current heights (nz_drainage_mfd, into its own plane) and solves the step
+        // (nz_fluvial_implicit_mfd), both with the same exponent (1..16), the solve told to proceed by the drainage call's
+        // converged word on the device; nothing is read back in between.  Pits stay pits: put DepressionFillStage in front.
+        // The heights ping-pong between the payload's plane and its WRITE plane (or a plane of the stage's); the result is
+        // in the payload's `data` when the handle completes.  seaLevel, rainMap / hardness / upliftMap: as
+        // ImplicitFluvialStage's.  maxPasses null means the default, 128 + resolution / 2, for the drainage series and for
+        // the solve each; a budget that runs out is no error: that iteration leaves the heights as they were.  Drainage is
+        // the area the last iteration saw; Steps, Passes and Converged wait for the handle and read the stage's tally: the
+        // iterations applied, the solve passes that did work, and Steps == iterations.
+        public int iterations = 1;
+        public float erodibility = 0.05f, uplift = 0.002f, dt = 1f, rain = 1f, seaLevel = -float.MaxValue;
+        public int exponent = 1;
+        public int? maxPasses = null;
+        public DeviceTile rainMap = null, hardness = null, upliftMap = null;
+        DeviceTile work;                         // nz_fluvial_implicit_mfd_work_floats floats
+        DeviceTile drainageWork;                 // nz_drainage_mfd's work floats; its second int32: the solve's `proceed`
+        DeviceTile area, plane, tally;           // the drainage, the heights' second plane, {steps applied, passes that did work}
+        int resolution, count = 1;
+        static readonly IntPtr Zeros = ZeroWords();   // what the tally is set to before a run; lives as long as the process
+        static IntPtr ZeroWords() {
+            IntPtr p = System.Runtime.InteropServices.Marshal.AllocHGlobal(8);
+            System.Runtime.InteropServices.Marshal.WriteInt64(p, 0L);
+            return p;
+        }
+        public MfdFluvialStage(GpuContext ctx) : base(ctx) {}
+        int Cells => count * resolution * resolution;
+        public DeviceTile Drainage => area;
+        public int? Steps => Counted(0);
+        public int? Passes => Counted(1);
+        public bool? Converged => Counted(0) is int s ? s == iterations : (bool?) null;
+        int? Counted(int k) {
+            if (tally == null) return null;
+            jobHandle.Complete();
+            return BitConverter.SingleToInt32Bits(tally.ToArray()[k]);
+        }
+        DeviceTile Size(DeviceTile t, bool want, int n) {   // a plane of the stage: resized with the payload, gone when not wanted
+            if (t != null && (!want || t.Length != n)) { t.Dispose(); t = null; }
+            return want && t == null ? ctx.Alloc(n) : t;
+        }
+        public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
+            if (requirements.data is GeneratorData g) {
+                resolution = g.resolution;
+                count = g is GeneratorDataBatch gb ? gb.count : 1;
+            }
+            CheckRequirements<GeneratorData>(requirements);
+            GeneratorData d = (GeneratorData) requirements.data;
+            foreach (DeviceTile m in new[] { rainMap, hardness, upliftMap })   // before any launch
+                if (m != null && m.Length != Cells) throw new Exception($"MfdFluvialStage: a plane of {m.Length} floats does not fit the payload's {Cells}");
+            work = Size(work, true, (int) (ulong) Native.nz_fluvial_implicit_mfd_work_floats(resolution, count));
+            drainageWork = Size(drainageWork, true, (int) (ulong) Native.nz_drainage_mfd_work_floats(resolution, count));
+            area = Size(area, true, Cells);
+            plane = Size(plane, d.write == null, Cells);
+            tally = Size(tally, true, 2);
+            int budget = maxPasses ?? 128 + resolution / 2;
+            NzDrainageMfdDesc drain = new NzDrainageMfdDesc {
+                rain = rain, seaLevel = seaLevel, maxPasses = budget, exponent = exponent,
+                rainMap = rainMap != null ? rainMap.Ptr : IntPtr.Zero };
+            // the solve's `proceed`: the drainage call's converged word, the second int32 of its work planes
+            NzFluvialImplicitMfdDesc solve = new NzFluvialImplicitMfdDesc {
+                erodibility = erodibility, uplift = uplift, dt = dt, seaLevel = seaLevel, maxPasses = budget, exponent = exponent,
+                hardness = hardness != null ? hardness.Ptr : IntPtr.Zero, upliftMap = upliftMap != null ? upliftMap.Ptr : IntPtr.Zero,
+                proceed = IntPtr.Add(drainageWork.Ptr, 4), tally = tally.Ptr };
+            ulong h;
+            Native.Check(Native.nz_tile_upload(ctx.Handle, tally.Ptr, Zeros, (UIntPtr) 2u, dependency.id, out h), "nz_tile_upload");
+            // the heights ping-pong between the payload's plane and the WRITE plane (or the stage's own)
+            DeviceTile cur = d.data, other = d.write ?? plane;
+            bool batch = d is GeneratorDataBatch;
+            for (int i = 0; i < iterations; i++) {
+                if (batch) {
+                    Native.Check(Native.nz_drainage_mfd_batch(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref drain, resolution, count, 0, IntPtr.Zero), "nz_drainage_mfd_batch");
+                    Native.Check(Native.nz_fluvial_implicit_mfd_batch(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, count, 0, out h), "nz_fluvial_implicit_mfd_batch");
+                } else {
+                    Native.Check(Native.nz_drainage_mfd(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref drain, resolution, 0, IntPtr.Zero), "nz_drainage_mfd");
+                    Native.Check(Native.nz_fluvial_implicit_mfd(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, 0, out h), "nz_fluvial_implicit_mfd");
+                }
+                DeviceTile s = cur; cur = other; other = s;
+            }
+            if (d.write != null) { d.data = cur; d.write = other; }   // the pair as the run left it: `data` holds the result
+            else if (cur != d.data)                                   // an odd count ended in the stage's plane
+                Native.Check(Native.nz_flush_write_slice(ctx.Handle, d.data.Ptr, cur.Ptr, (UIntPtr) (uint) Cells, 0, out h), "nz_flush_write_slice");
+            jobHandle = Done(h);
+        }
+        public override void OnDestroy() {
+            work?.Dispose(); work = null; drainageWork?.Dispose(); drainageWork = null; area?.Dispose(); area = null;
+            plane?.Dispose(); plane = null; tally?.Dispose(); tally = null;
+        }
+    }
+
     // Linear hillslope diffusion, dh/dt = diffusivity * laplace(h), as implicit steps of any size (new-framework feature; the
     // model: nz_hillslope_diffusion in include/noize_hip.h): backward Euler split by direction, two tridiagonal line solves
     // per step, stable and free of oscillation for every dt, the border cells held.  It rounds the knife-edge ridges and

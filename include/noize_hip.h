@@ -1386,6 +1386,84 @@ int32_t nz_hillslope_diffusion(nz_ctx *ctx, const float *height, float *out, flo
 int32_t nz_hillslope_diffusion_batch(nz_ctx *ctx, const float *height, float *out, float *work, const nz_hillslope_desc *desc,
                                      int32_t resolution, int32_t count, nz_handle dep, nz_handle *out_handle);
 
+/* ---- multiple-flow implicit fluvial erosion: the implicit step along every descent (new-framework feature) ---------------
+ * nz_fluvial_implicit above lowers each cell along its ONE steepest receiver, whatever plane A it is given: behind
+ * nz_drainage_mfd the water is spread over a fan and then cut into eight-direction grooves.  This entry takes the implicit
+ * Euler step of the same stream-power law along EVERY lower neighbour, with nz_drainage_mfd's weights: the step that goes
+ * with that drainage plane (fastscapelib solves its multiple-flow stream power the same way).
+ *
+ * THE MODEL (tests/fluvial_implicit_mfd_ref.py restates it as a walk lowest cell first; the kernels are
+ * nz_fluvial_implicit_mfd.hip):
+ *   Square tile res x res, row-major c = z * res + x, float32 throughout, every operation rounded once, no contraction, the
+ *   same in every float mode (nz_ctx_set_float_mode does not apply).  Outlets, the neighbour order W E S N SW SE NW NE,
+ *   DIAG, du, kc and b are exactly nz_fluvial_implicit's; the outgoing weights w_k of a cell are exactly nz_drainage_mfd's
+ *   at `exponent` (1..16) -- the same device code.  Inputs, all read only: heights h, a drainage plane A (required; e.g.
+ *   nz_drainage_mfd on the same heights with the same exponent) and the optional planes hardness and upliftMap.  Per cell c:
+ *     outlet (global border or h <= seaLevel):  h'[c] = h[c];
+ *     no k with w_k > 0 (a pit, a flat):        h'[c] = b = h[c] + du     (not through the division);
+ *     otherwise:  e = kc * sqrt(A[c]);
+ *                 f_k = ((e * invL_k) * dt) * w_k   for every k with w_k > 0, invL_k = 1 for k < 4 and 0x1.6a09e6p-1f else;
+ *                 N = b;  D = 1;  for k ascending with w_k > 0:  N = N + (f_k * h'[k]);  D = D + f_k;
+ *                 h'[c] = N / D                     one correctly rounded float32 division.
+ *   The gate is w_k > 0, never the value of f_k or of h'.
+ * Every neighbour that takes flow is strictly lower in the old heights, so the flow graph is a DAG whose leaves -- outlets,
+ * pits, flats -- are fixed from the start; a cell's new height is a fixed function of the new heights of lower cells, so
+ * the fixed point is unique: a walk lowest cell first, Jacobi and tile sweeps end in the same bits, from any start state
+ * (the kernels start from b).  The "nothing" of all or nothing is h' = h.  What follows:
+ *   - a cell with exactly one positive weight has w == 1 and takes nz_fluvial_implicit's value bit for bit, given the same
+ *     A and an equal h' below it;
+ *   - erodibility == 0 gives h + du off the outlets;
+ *   - outlets keep their bits;
+ *   - in exact arithmetic and without an upliftMap, min_k h'[k] <= h'[c] <= h[c] + du over the k with w_k > 0: no cell
+ *     rises above its uplifted height or sinks below the lowest cell it drains to.  In float32 rounding can decide
+ *     otherwise on tiles of tiny or equal heights;
+ *   - NaN heights send and receive nothing (HEIGHT DIFFERENCES MUST BE FINITE, as for nz_drainage_mfd); a NaN or negative
+ *     A gives a NaN in that cell and travels upstream, as in nz_fluvial_implicit.
+ * Say it plainly: an f that overflows gives inf / inf = NaN in that cell and in every cell upstream of it; and pits stay
+ * pits, so put nz_fill_depressions (DepressionFillStage) in front.
+ *
+ * The entry enqueues nz_fluvial_implicit's begin launch, one setup launch (heights at radius 1, A and the maps -> one gate
+ * byte, bit k: w_k > 0, the plane b and the eight planes f_k per cell, +0 where w_k is not > 0, into `work`; every square
+ * root and every weight division is here), maxPasses pass launches and nz_fluvial_implicit's finalise launch,
+ * stream-ordered; nothing is read back.  After the setup launch no pass looks at a height, A or a map.  A pass is
+ * nz_drainage_mfd's gather with h' in place of A, closed by the division; D is rebuilt from the f in registers, not stored.
+ * After completion the first two int32 of `work` hold {passes that did work, converged 0/1}.  The result is ALL OR NOTHING:
+ * when the last pass that ran changed nothing, `out` holds the fixed point; otherwise -- the budget was too small --
+ * out = h bit for bit and converged == 0, which is not an error.  A pass is at least one Jacobi step, so a budget of
+ * "cells of the longest path of the flow DAG" + 2 always suffices.  Defaults of the hosts' MfdFluvialStage: iterations 1,
+ * erodibility 0.05, uplift 0.002, dt 1, rain 1, seaLevel -FLT_MAX (off), exponent 1, maxPasses 128 + resolution / 2 for
+ * the drainage and for the solve, no maps.
+ *
+ * `proceed`, `tally`, the status words, the zero-size behaviour and the batch form are nz_fluvial_implicit's word for word;
+ * `proceed` takes the converged word of nz_drainage_mfd (the second int32 of its `work`) as it takes nz_drainage_area's.
+ * `work` = nz_fluvial_implicit_mfd_work_floats(resolution, count) floats, stage-owned: status words, tile bytes, the gate
+ * bytes, the plane b, the eight planes f and the second h' plane (the first is `out`).  0 for resolution <= 0 or count <= 0.
+ * The 16-byte path runs when every plane is 16-byte aligned and resolution % 4 == 0, the 4-byte path otherwise; both give
+ * the same bits.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: everything nz_fluvial_implicit
+ * refuses, and exponent outside 1..16.
+ * There is no row-stripe form and no _rw form. */
+typedef struct nz_fluvial_implicit_mfd_desc {
+    float erodibility, uplift, dt, seaLevel;
+    int32_t maxPasses;
+    int32_t exponent;         /* 1..16, nz_drainage_mfd_desc.exponent */
+    const float *hardness;    /* NULL: erodibility everywhere */
+    const float *upliftMap;   /* NULL: uplift everywhere */
+    const int32_t *proceed;   /* device word, NULL: always run; a word of 0: the step is not applied */
+    int32_t *tally;           /* device, 2 words, NULL: off; tally[0] += 1 when the step was applied, tally[1] += passes that did work */
+} nz_fluvial_implicit_mfd_desc;
+size_t nz_fluvial_implicit_mfd_work_floats(int32_t resolution, int32_t count);
+int32_t nz_fluvial_implicit_mfd(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                const nz_fluvial_implicit_mfd_desc *desc, int32_t resolution, nz_handle dep,
+                                nz_handle *out_handle);
+int32_t nz_fluvial_implicit_mfd_batch(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                      const nz_fluvial_implicit_mfd_desc *desc, int32_t resolution, int32_t count,
+                                      nz_handle dep, nz_handle *out_handle);
+/* Test hook, the twin of nz_debug_fluvial_implicit_sweeps with a cap of its own: the cap on a multiple-flow implicit pass's
+ * on-chip sweeps per tile (process-wide; <= 0 restores the default, 16).  Results must not change.  Returns the cap that
+ * was in force. */
+int32_t nz_debug_fluvial_implicit_mfd_sweeps(int32_t sweeps);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

@@ -125,6 +125,13 @@ class FluvialImplicitDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("hardness", "upliftMap", "proceed", "tally")])
 
 
+class FluvialImplicitMfdDesc(C.Structure):
+    """nz_fluvial_implicit_mfd_desc (include/noize_hip.h): FluvialImplicitDesc with the flow exponent behind maxPasses."""
+    _fields_ = ([(n, C.c_float) for n in ("erodibility", "uplift", "dt", "seaLevel")] +
+                [("maxPasses", C.c_int32), ("exponent", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("hardness", "upliftMap", "proceed", "tally")])
+
+
 class HillslopeDesc(C.Structure):
     """nz_hillslope_desc (include/noize_hip.h): the diffusivity, the time step and the number of steps."""
     _fields_ = [("diffusivity", C.c_float), ("dt", C.c_float), ("iterations", C.c_int32)]
@@ -138,6 +145,7 @@ mfd_p = C.POINTER(DrainageMfdDesc)
 shed_p = C.POINTER(WatershedDesc)
 order_p = C.POINTER(StreamOrderDesc)
 fimp_p = C.POINTER(FluvialImplicitDesc)
+fmfd_p = C.POINTER(FluvialImplicitMfdDesc)
 hill_p = C.POINTER(HillslopeDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
@@ -273,6 +281,10 @@ SIGNATURES = {
     "nz_fluvial_implicit": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i] + _tail),
     "nz_fluvial_implicit_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i, _i] + _tail),
     "nz_debug_fluvial_implicit_sweeps": (_i, [_i]),
+    "nz_fluvial_implicit_mfd_work_floats": (_sz, [_i, _i]),
+    "nz_fluvial_implicit_mfd": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fmfd_p, _i] + _tail),
+    "nz_fluvial_implicit_mfd_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fmfd_p, _i, _i] + _tail),
+    "nz_debug_fluvial_implicit_mfd_sweeps": (_i, [_i]),
     "nz_hillslope_diffusion_work_floats": (_sz, [_i, _i]),
     "nz_hillslope_diffusion": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, hill_p, _i] + _tail),
     "nz_hillslope_diffusion_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, hill_p, _i, _i] + _tail),

@@ -24,6 +24,7 @@
 // is w > 0, never the value of A.  The finalise launch is nz_drainage.hip's (nz_launch_drainage_finalise).
 // There is no row-stripe form.
 #include "nz_internal.hpp"
+#include "nz_mfd_weights.hpp"
 #include "nz_receiver.hpp"
 #include "nz_relax_pass.hpp"
 #include "nz_tile64.hpp"
@@ -32,35 +33,8 @@ namespace {
 
 using namespace nz_tile64;  // the tile, its LDS layout, ring_cell, halo2_cell
 using namespace nz_relax;   // the status words and the pass protocol
-
-// q ^ exponent, left to right: exponent - 1 multiplications
-__device__ __forceinline__ float mfd_power(float q, int exponent) {
-    float g = q;
-    for (int e = 1; e < exponent; e++) g = g * q;
-    return g;
-}
-
-// `best` and T of the cell at p in a height plane of pitch LP whose eight neighbours all exist
-__device__ __forceinline__ void mfd_send_terms(const float *p, int exponent, float &best, float &total) {
-    const float c = p[0];
-    const float hk[8] = {p[-1], p[1], p[-LP], p[LP], p[-LP - 1], p[-LP + 1], p[LP - 1], p[LP + 1]};
-    float s[8];
-    best = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const float d = c - hk[k];
-        s[k] = k < 4 ? d : d * nz_recv::DIAG;
-        if (s[k] > best) best = s[k];
-    }
-    total = 0.0f;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        if (s[k] > 0.0f) {
-            const float g = mfd_power(s[k] / best, exponent);
-            if (g > 0.0f) total = total + g;  // an infinite s gives a NaN g, an underflow +0: nothing
-        }
-    }
-}
+using nz_mfd::mfd_power;     // the weights of a cell: shared with nz_fluvial_implicit_mfd.hip
+using nz_mfd::mfd_send_terms;
 
 // ---- the setup launch: heights -> eight planes of incoming weights ----
 // VEC: 16-byte accesses to the float planes (all planes 16-byte aligned, res % 4 == 0); plane: the floats of one weight plane

@@ -531,6 +531,17 @@ int32_t nz_launch_fluvial_implicit_pass(hipStream_t s, const unsigned char *recv
                                         unsigned char *flags_out, int res, int count, int pass, int sweeps);
 int32_t nz_launch_fluvial_implicit_finalise(hipStream_t s, const float *h, float *out, int *status, int *tally, size_t n);
 
+// multiple-flow implicit fluvial erosion (nz_fluvial_implicit_mfd.hip); begin and finalise are the two launches above.
+// setup: heights, drainage `area` and the maps (NULL: none) -> one gate byte per cell (bit k: the weight towards neighbour k
+// is > 0), the plane bco and the eight planes fco (plane k at k * count * res^2).  pass: as nz_launch_fluvial_implicit_pass
+int32_t nz_launch_fluvial_implicit_mfd_setup(hipStream_t s, const float *h, const float *area, const float *hardness,
+                                             const float *uplift_map, unsigned char *gate, float *bco, float *fco,
+                                             const int *status, float erodibility, float uplift, float dt, float sea, int res,
+                                             int count, int exponent);
+int32_t nz_launch_fluvial_implicit_mfd_pass(hipStream_t s, const unsigned char *gate, const float *bco, const float *fco,
+                                            const float *h_in, float *h_out, int *status, const unsigned char *flags_in,
+                                            unsigned char *flags_out, int res, int count, int pass, int sweeps);
+
 // hillslope diffusion (nz_hillslope.hip).  tables: inv[i] and cp[i], i = 1 .. res-2, of r (res floats each; res >= 3).
 // step: one step on `count` tiles of res^2 cells stored back to back, `in` -> `out` (the same pointer: in place; otherwise
 // disjoint), as three launches: the rows' forward sweep, their backward sweep, the columns' two sweeps

@@ -1,6 +1,6 @@
 // nz_terrain_stages.cpp -- the extern "C" entry points of the terrain stages the reference does not have (grid hydraulic
 // erosion, fluvial erosion, depression filling, drainage area, watershed, stream order, implicit fluvial erosion, hillslope diffusion,
-// resampling; include/noize_hip.h): tile, batch,
+// multiple-flow drainage and multiple-flow implicit fluvial erosion, resampling; include/noize_hip.h): tile, batch,
 // read/write-pair and row-stripe forms.  The stripe geometry and the aliasing checks they share are in nz_planes.hpp.
 #include <atomic>
 #include <cmath>
@@ -415,9 +415,8 @@ extern "C" int32_t nz_fluvial_stripe(nz_ctx *ctx, const float *height_in, float 
 // ---------------------------------------------------------------------------------------------
 // depression filling (new-framework feature, include/noize_hip.h, nz_fill.hip)
 // ---------------------------------------------------------------------------------------------
-// The six stages that iterate to rest -- this one, drainage area, multiple-flow drainage, watershed, stream order, implicit
-// fluvial erosion --
-// share what follows.
+// The seven stages that iterate to rest -- this one, drainage area, multiple-flow drainage, watershed, stream order, implicit
+// fluvial erosion and its multiple-flow form -- share what follows.
 //
 // `work` in floats begins the same way for all of them: 16 status words (nz_relax_pass.hpp; the rest spare) and two
 // generations of per-tile bytes (nz_tile64.hpp); then come the stage's own byte planes (one byte per cell) and 4-byte
@@ -451,8 +450,9 @@ struct relax_work {
     int *ints(size_t n) { return reinterpret_cast<int *>(floats(n)); }
 };
 
-// The sweep cap of a stage: 16 for each of the six (measured per stage, 4 to 64: DESIGN.md section 4).  The debug entry
-// may be called while another thread runs an entry; it returns the cap before, and a value < 1 puts the default back.
+// The sweep cap of a stage: 16 for each of the seven.  Six were measured at caps of 4 to 64, the multiple-flow implicit
+// solve at 16 only.  The debug entry may be called while another thread runs an entry; it returns the
+// cap before, and a value < 1 puts the default back.
 constexpr int RELAX_SWEEPS = 16;
 struct sweep_cap {
     std::atomic<int> cap{RELAX_SWEEPS};
@@ -974,6 +974,51 @@ extern "C" int32_t nz_stream_order_batch(nz_ctx *ctx, const float *height, uint8
 // `work`: the head, one receiver byte per cell, the coefficient planes b and f and the second h' plane; the first h' plane
 // is the caller's `out`.
 namespace {
+// What nz_fluvial_implicit_desc and nz_fluvial_implicit_mfd_desc have in common, and the checks on it and on the planes:
+// the two entries refuse word for word because they run the same text.
+struct implicit_args {
+    float erodibility, uplift, dt, seaLevel;
+    int maxPasses;
+    const float *hardness, *upliftMap;
+    const int32_t *proceed;
+    int32_t *tally;
+};
+template <class Desc>
+implicit_args implicit_args_of(const Desc &d) {
+    return {d.erodibility, d.uplift, d.dt, d.seaLevel, d.maxPasses, d.hardness, d.upliftMap, d.proceed, d.tally};
+}
+int32_t check_implicit_scalars(const float *height, const float *drainage, const float *outp, const float *work,
+                               const implicit_args &a) {
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(drainage, "drainage is NULL");
+    NZ_REQUIRE(outp, "out is NULL");
+    NZ_REQUIRE(work, "work is NULL");
+    NZ_REQUIRE(std::isfinite(a.erodibility), "erodibility is not finite");
+    NZ_REQUIRE(std::isfinite(a.uplift), "uplift is not finite");
+    NZ_REQUIRE(std::isfinite(a.dt), "dt is not finite");
+    NZ_REQUIRE(std::isfinite(a.seaLevel), "seaLevel is not finite");
+    NZ_REQUIRE(a.erodibility >= 0.0f, "erodibility %g < 0", (double)a.erodibility);
+    NZ_REQUIRE(a.uplift >= 0.0f, "uplift %g < 0", (double)a.uplift);
+    NZ_REQUIRE(a.dt >= 0.0f, "dt %g < 0", (double)a.dt);
+    NZ_REQUIRE(a.maxPasses >= 1, "maxPasses %d < 1", a.maxPasses);
+    return NZ_OK;
+}
+// n: the cells of one plane; work_floats: what the entry's *_work_of hands out
+int32_t check_implicit_planes(const float *height, const float *drainage, float *outp, float *work, size_t work_floats,
+                              const implicit_args &a, int res, int count, size_t n) {
+    NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
+    const nz_named_plane writes[] = {{"out", outp, n}, {"work", work, work_floats}};
+    const nz_named_plane reads[] = {{"height", height, n}, {"drainage", drainage, n}, {"hardness", a.hardness, n},
+                                    {"upliftMap", a.upliftMap, n}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    for (const auto &p : {writes[0], writes[1], reads[0], reads[1], reads[2], reads[3]})  // the words are ints, not planes
+        NZ_REQUIRE(!nz_bytes_overlap(a.tally, 8, p.p, p.floats * sizeof(float)), "tally overlaps %s", p.name);
+    for (const auto &p : {writes[0], writes[1]})
+        NZ_REQUIRE(!nz_bytes_overlap(a.proceed, 4, p.p, p.floats * sizeof(float)), "proceed overlaps %s", p.name);
+    NZ_REQUIRE(!nz_bytes_overlap(a.tally, 8, a.proceed, 4), "tally overlaps proceed");
+    return NZ_OK;
+}
+
 struct fluvial_implicit_work { relax_work hd; unsigned char *recv; float *b, *f, *h2; };
 fluvial_implicit_work fluvial_implicit_work_of(float *work, const relax_shape &sh) {
     fluvial_implicit_work k{relax_work(work, sh), nullptr, nullptr, nullptr, nullptr};
@@ -998,31 +1043,12 @@ static int32_t fluvial_implicit_impl(nz_ctx *ctx, const float *height, const flo
     if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
     NZ_TRY(check_batch(res, count));
     NZ_REQUIRE(d, "desc is NULL");
-    NZ_REQUIRE(height, "height is NULL");
-    NZ_REQUIRE(drainage, "drainage is NULL");
-    NZ_REQUIRE(outp, "out is NULL");
-    NZ_REQUIRE(work, "work is NULL");
-    NZ_REQUIRE(std::isfinite(d->erodibility), "erodibility is not finite");
-    NZ_REQUIRE(std::isfinite(d->uplift), "uplift is not finite");
-    NZ_REQUIRE(std::isfinite(d->dt), "dt is not finite");
-    NZ_REQUIRE(std::isfinite(d->seaLevel), "seaLevel is not finite");
-    NZ_REQUIRE(d->erodibility >= 0.0f, "erodibility %g < 0", (double)d->erodibility);
-    NZ_REQUIRE(d->uplift >= 0.0f, "uplift %g < 0", (double)d->uplift);
-    NZ_REQUIRE(d->dt >= 0.0f, "dt %g < 0", (double)d->dt);
-    NZ_REQUIRE(d->maxPasses >= 1, "maxPasses %d < 1", d->maxPasses);
+    const implicit_args a = implicit_args_of(*d);
+    NZ_TRY(check_implicit_scalars(height, drainage, outp, work, a));
     const relax_shape sh = tile_shape(res, count);
     const fluvial_implicit_work k = fluvial_implicit_work_of(work, sh);
     const size_t n = sh.n;
-    NZ_REQUIRE(n <= (size_t)INT32_MAX, "count %d x resolution %d^2: %zu cells are beyond int32", count, res, n);
-    const nz_named_plane writes[] = {{"out", outp, n}, {"work", work, k.hd.total}};
-    const nz_named_plane reads[] = {{"height", height, n}, {"drainage", drainage, n}, {"hardness", d->hardness, n},
-                                    {"upliftMap", d->upliftMap, n}};
-    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
-    for (const auto &p : {writes[0], writes[1], reads[0], reads[1], reads[2], reads[3]})  // the words are ints, not planes
-        NZ_REQUIRE(!nz_bytes_overlap(d->tally, 8, p.p, p.floats * sizeof(float)), "tally overlaps %s", p.name);
-    for (const auto &p : {writes[0], writes[1]})
-        NZ_REQUIRE(!nz_bytes_overlap(d->proceed, 4, p.p, p.floats * sizeof(float)), "proceed overlaps %s", p.name);
-    NZ_REQUIRE(!nz_bytes_overlap(d->tally, 8, d->proceed, 4), "tally overlaps proceed");
+    NZ_TRY(check_implicit_planes(height, drainage, outp, work, k.hd.total, a, res, count, n));
     float *planes[2] = {outp, k.h2};
     const int sweeps = fluvial_implicit_sweeps.load();
     NZ_TRY(nz_launch_fluvial_implicit_begin(ctx->stream, k.hd.status, d->proceed));
@@ -1048,6 +1074,75 @@ extern "C" int32_t nz_fluvial_implicit_batch(nz_ctx *ctx, const float *height, c
                                              const nz_fluvial_implicit_desc *desc, int32_t resolution, int32_t count,
                                              nz_handle dep, nz_handle *out_handle) {
     return fluvial_implicit_impl(ctx, height, drainage, out, work, desc, resolution, count, dep, out_handle);
+}
+
+// ---------------------------------------------------------------------------------------------
+// multiple-flow implicit fluvial erosion: the implicit step along every descent (new-framework feature,
+// include/noize_hip.h, nz_fluvial_implicit_mfd.hip)
+// ---------------------------------------------------------------------------------------------
+// `work`: the head, one gate byte per cell, the plane b, the eight planes f and the second h' plane; the first h' plane is
+// the caller's `out`.  The checks (check_implicit_scalars, check_implicit_planes), the begin and the finalise launch are
+// fluvial_implicit_impl's.
+namespace {
+struct fluvial_mfd_work { relax_work hd; unsigned char *gate; float *b, *f, *h2; };
+fluvial_mfd_work fluvial_mfd_work_of(float *work, const relax_shape &sh) {
+    fluvial_mfd_work k{relax_work(work, sh), nullptr, nullptr, nullptr, nullptr};
+    k.gate = k.hd.bytes(sh.n);
+    k.b = k.hd.floats(sh.n);
+    k.f = k.hd.floats(8 * sh.n);
+    k.h2 = k.hd.floats(sh.n);
+    return k;
+}
+sweep_cap fluvial_implicit_mfd_sweeps;
+}  // namespace
+
+extern "C" size_t nz_fluvial_implicit_mfd_work_floats(int32_t resolution, int32_t count) {
+    if (resolution <= 0 || count <= 0) return 0;
+    return fluvial_mfd_work_of(nullptr, tile_shape(resolution, count)).hd.total;
+}
+
+extern "C" int32_t nz_debug_fluvial_implicit_mfd_sweeps(int32_t sweeps) { return fluvial_implicit_mfd_sweeps.exchange(sweeps); }
+
+static int32_t fluvial_implicit_mfd_impl(nz_ctx *ctx, const float *height, const float *drainage, float *outp, float *work,
+                                         const nz_fluvial_implicit_mfd_desc *d, int res, int count, nz_handle dep,
+                                         nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    const implicit_args a = implicit_args_of(*d);
+    NZ_TRY(check_implicit_scalars(height, drainage, outp, work, a));
+    NZ_REQUIRE(d->exponent >= 1 && d->exponent <= 16, "exponent %d outside 1..16", d->exponent);
+    const relax_shape sh = tile_shape(res, count);
+    const fluvial_mfd_work k = fluvial_mfd_work_of(work, sh);
+    const size_t n = sh.n;
+    NZ_TRY(check_implicit_planes(height, drainage, outp, work, k.hd.total, a, res, count, n));
+    float *planes[2] = {outp, k.h2};
+    const int sweeps = fluvial_implicit_mfd_sweeps.load();
+    NZ_TRY(nz_launch_fluvial_implicit_begin(ctx->stream, k.hd.status, d->proceed));
+    NZ_TRY(nz_launch_fluvial_implicit_mfd_setup(ctx->stream, height, drainage, d->hardness, d->upliftMap, k.gate, k.b, k.f,
+                                                k.hd.status, d->erodibility, d->uplift, d->dt, d->seaLevel, res, count,
+                                                d->exponent));
+    return run_tile_series(
+        ctx, out, d->maxPasses, k.hd,
+        [&](int p, const unsigned char *flags_in, unsigned char *flags_out) {  // pass p writes plane p & 1
+            return nz_launch_fluvial_implicit_mfd_pass(ctx->stream, k.gate, k.b, k.f, p ? planes[(p - 1) & 1] : nullptr,
+                                                       planes[p & 1], k.hd.status, flags_in, flags_out, res, count, p, sweeps);
+        },
+        // a series at rest holds the fixed point in both planes, so `out` has it whichever plane was written last
+        [&] { return nz_launch_fluvial_implicit_finalise(ctx->stream, height, outp, k.hd.status, d->tally, n); });
+}
+
+extern "C" int32_t nz_fluvial_implicit_mfd(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                           const nz_fluvial_implicit_mfd_desc *desc, int32_t resolution, nz_handle dep,
+                                           nz_handle *out_handle) {
+    return fluvial_implicit_mfd_impl(ctx, height, drainage, out, work, desc, resolution, 1, dep, out_handle);
+}
+
+extern "C" int32_t nz_fluvial_implicit_mfd_batch(nz_ctx *ctx, const float *height, const float *drainage, float *out,
+                                                 float *work, const nz_fluvial_implicit_mfd_desc *desc, int32_t resolution,
+                                                 int32_t count, nz_handle dep, nz_handle *out_handle) {
+    return fluvial_implicit_mfd_impl(ctx, height, drainage, out, work, desc, resolution, count, dep, out_handle);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1267,6 +1267,99 @@ class ImplicitFluvialStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work, drainageWork, area, plane, tally;
 };
 
+class MfdFluvialStage : public PipelineStage {
+    // Multiple-flow implicit stream-power erosion (new-framework feature; the model: nz_fluvial_implicit_mfd in
+    // include/noize_hip.h): ImplicitFluvialStage's step taken along EVERY lower neighbour of a cell, with the weights of
+    // MfdDrainageStage -- the fan the water is spread over is what erodes, where ImplicitFluvialStage with
+    // FlowRouting::Multiple cuts along the one steepest receiver.  Per iteration the stage computes the multiple-flow
+    // drainage of the current heights (nz_drainage_mfd, into its own plane) and solves the step (nz_fluvial_implicit_mfd),
+    // both with the same exponent (1..16), the solve told to proceed by the drainage call's converged word on the device;
+    // nothing is read back in between.  Pits stay pits: put DepressionFillStage in front.  The heights ping-pong between the
+    // payload's plane and its WRITE plane (or a plane of the stage's); the result is in the payload's `data` when the handle
+    // completes.  seaLevel, rainMap / hardness / upliftMap: as ImplicitFluvialStage's.  maxPasses < 1 means the default,
+    // 128 + resolution / 2, for the drainage series and for the solve each; a budget that runs out is no error: that
+    // iteration leaves the heights as they were.  drainage() is the area the last iteration saw; steps(), passes() and
+    // converged() wait for the handle and read the stage's tally: the iterations applied, the solve passes that did work,
+    // and steps() == iterations.
+  public:
+    using PipelineStage::PipelineStage;
+    int iterations = 1;
+    float erodibility = .05f, uplift = .002f, dt = 1.f, rain = 1.f, seaLevel = -3.402823466e+38f;
+    int exponent = 1;
+    int maxPasses = 0;  // < 1: 128 + resolution / 2
+    const DeviceTile *rainMap = nullptr, *hardness = nullptr, *upliftMap = nullptr;
+    void Schedule(PipelineWorkItem &requirements, JobHandle dependency) override {
+        auto *g = dynamic_cast<GeneratorData *>(requirements.data);
+        if (!g) throw std::runtime_error("Unhandled stageio");
+        resolution = g->resolution;
+        count = tile_count(g);
+        auto *d = CheckRequirements<GeneratorData>(requirements);
+        for (const DeviceTile *m : {rainMap, hardness, upliftMap})  // before any launch
+            if (m && m->Length != cells()) throw std::runtime_error("MfdFluvialStage: a plane does not fit the payload");
+        size(work, nz_fluvial_implicit_mfd_work_floats(resolution, count));
+        size(drainageWork, nz_drainage_mfd_work_floats(resolution, count));
+        size(area, cells());
+        if (d->write) plane.reset();
+        else size(plane, cells());
+        size(tally, 2);
+        const int budget = maxPasses >= 1 ? maxPasses : 128 + resolution / 2;
+        const nz_drainage_mfd_desc drain{rain, seaLevel, budget, exponent, rainMap ? rainMap->ptr : nullptr};
+        // the solve's `proceed`: the drainage call's converged word, the second int32 of its work planes
+        const nz_fluvial_implicit_mfd_desc solve{erodibility, uplift, dt, seaLevel, budget, exponent,
+                                                 hardness ? hardness->ptr : nullptr, upliftMap ? upliftMap->ptr : nullptr,
+                                                 reinterpret_cast<const int32_t *>(drainageWork->ptr) + 1,
+                                                 reinterpret_cast<int32_t *>(tally->ptr)};
+        static const int32_t zeros[2] = {0, 0};
+        nz_handle h = 0;
+        check(nz_tile_upload(ctx, tally->ptr, reinterpret_cast<const float *>(zeros), 2, dependency.id, &h), "nz_tile_upload");
+        // the heights ping-pong between the payload's plane and the WRITE plane (or the stage's own)
+        DeviceTile *cur = d->data, *other = d->write ? d->write : plane.get();
+        auto *b = dynamic_cast<GeneratorDataBatch *>(d);
+        for (int i = 0; i < iterations; i++) {
+            if (b) {
+                check(nz_drainage_mfd_batch(ctx, cur->ptr, area->ptr, drainageWork->ptr, &drain, resolution, count, 0, nullptr),
+                      "nz_drainage_mfd_batch");
+                check(nz_fluvial_implicit_mfd_batch(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, count, 0, &h),
+                      "nz_fluvial_implicit_mfd_batch");
+            } else {
+                check(nz_drainage_mfd(ctx, cur->ptr, area->ptr, drainageWork->ptr, &drain, resolution, 0, nullptr),
+                      "nz_drainage_mfd");
+                check(nz_fluvial_implicit_mfd(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, 0, &h),
+                      "nz_fluvial_implicit_mfd");
+            }
+            std::swap(cur, other);
+        }
+        if (d->write) {  // the pair as the run left it: `data` holds the result
+            d->data = cur;
+            d->write = other;
+        } else if (cur != d->data) {  // an odd count ended in the stage's plane
+            check(nz_flush_write_slice(ctx, d->data->ptr, cur->ptr, cells(), 0, &h), "nz_flush_write_slice");
+        }
+        jobHandle = done(h);
+    }
+    const float *drainage() const { return area ? area->ptr : nullptr; }  // nullptr before a payload
+    size_t cells() const { return (size_t)count * resolution * resolution; }
+    int steps() const { return counted(0); }                 // -1 before the first run
+    int passes() const { return counted(1); }
+    bool converged() const { return counted(0) == iterations; }
+    void OnDestroy() override { work.reset(); drainageWork.reset(); area.reset(); plane.reset(); tally.reset(); }
+
+  private:
+    void size(std::unique_ptr<DeviceTile> &t, size_t need) {
+        if (!t || t->Length != need) t.reset(new DeviceTile(ctx, need));
+    }
+    int counted(int k) const {
+        if (!tally) return -1;
+        jobHandle.Complete();
+        int32_t words[2];
+        check(nz_tile_download(ctx, tally->ptr, reinterpret_cast<float *>(words), 2, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[k];
+    }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, drainageWork, area, plane, tally;
+};
+
 // Linear hillslope diffusion, dh/dt = diffusivity * laplace(h), as implicit steps of any size (new-framework feature; the
 // model: nz_hillslope_diffusion in include/noize_hip.h): backward Euler split by direction, two tridiagonal line solves per
 // step, stable and free of oscillation for every dt, the border cells held.  It rounds the knife-edge ridges and one-cell

@@ -1535,6 +1535,137 @@ class ImplicitFluvialStage(PipelineStage):
         self.DisposeArrays()
 
 
+class MfdFluvialStage(PipelineStage):
+    """Multiple-flow implicit stream-power erosion (new-framework feature; the model is the comment block of
+    nz_fluvial_implicit_mfd in include/noize_hip.h): ImplicitFluvialStage's step taken along EVERY lower neighbour of a
+    cell, with the weights of MfdDrainageStage -- the water is spread over a fan and the fan is what erodes, where
+    ImplicitFluvialStage(routing=FlowRouting.Multiple) cuts along the one steepest receiver.  Per iteration the stage
+    computes the multiple-flow drainage of the current heights (nz_drainage_mfd, into its own plane) and then solves the
+    step (nz_fluvial_implicit_mfd), both with the same `exponent` (1..16); the solve is told to proceed by the drainage
+    call's converged word on the device, nothing is read back in between.  Pits stay pits: put DepressionFillStage in
+    front.  The heights ping-pong between the payload's plane and its WRITE plane (or a plane of the stage's); the result
+    is in the payload's `data` when the stage's handle completes.
+
+    seaLevel: cells at or below it are outlets like the border cells (the default, -FLT_MAX, switches it off).  rainMap /
+    hardness / upliftMap: device planes of the payload's size the caller supplies and keeps alive -- rain is multiplied by
+    rainMap, erodibility by 1 - hardness, uplift by upliftMap.  maxPasses: the pass launches of the drainage
+    series and of the solve, each; None means 128 + resolution // 2.  A budget that runs out is no error: that iteration
+    leaves the heights as they were, and `steps` stays below `iterations`.
+
+    After the handle completes: `drainage` is the drainage area the last iteration saw, `steps` the iterations that were
+    applied, `passes` the solve passes that did work over all of them, `converged` whether steps == iterations."""
+
+    SEA_OFF = -3.4028234663852886e38  # -FLT_MAX
+
+    def __init__(self, ctx, iterations=1, erodibility=0.05, uplift=0.002, dt=1.0, rain=1.0, seaLevel=SEA_OFF, exponent=1,
+                 maxPasses=None, rainMap=None, hardness=None, upliftMap=None):
+        super().__init__(ctx)
+        self.iterations = iterations
+        self.erodibility = erodibility
+        self.uplift = uplift
+        self.dt = dt
+        self.rain = rain
+        self.seaLevel = seaLevel
+        self.exponent = exponent
+        self.maxPasses = maxPasses
+        self.rainMap = rainMap
+        self.hardness = hardness
+        self.upliftMap = upliftMap
+        self.resolution = 0
+        self.count = 0
+        self.work = None           # nz_fluvial_implicit_mfd_work_floats floats
+        self.drainageWork = None   # nz_drainage_mfd's work floats; its second int32: the solve's `proceed`
+        self._area = None          # the drainage plane
+        self._plane = None         # the heights' second plane, for a payload without a WRITE plane
+        self._tally = None         # two int32: {steps applied, passes that did work}
+        self._zeros = np.zeros(2, np.int32)  # what the tally is set to before a run (kept alive: the upload reads it)
+
+    def DisposeArrays(self):
+        for t in (self.work, self.drainageWork, self._area, self._plane, self._tally):
+            if t is not None and t.IsCreated:
+                t.Dispose()
+        self.work = self.drainageWork = self._area = self._plane = self._tally = None
+
+    @property
+    def drainage(self):
+        """The drainage area the last iteration saw, or None before the first payload and after OnDestroy."""
+        return self._area
+
+    def _counts(self):
+        if self._tally is None:
+            return None
+        self.jobHandle.Complete()
+        return self._tally.ToArray()
+
+    @property
+    def steps(self):
+        """Iterations of the last run that were applied; None before the first run."""
+        t = self._counts()
+        return None if t is None else int(t[0])
+
+    @property
+    def passes(self):
+        """Solve passes of the last run that did work, over all applied iterations; None before the first run."""
+        t = self._counts()
+        return None if t is None else int(t[1])
+
+    @property
+    def converged(self):
+        """Whether every iteration of the last run was applied; None before the first run."""
+        t = self._counts()
+        return None if t is None else int(t[0]) == self.iterations
+
+    def _size(self, tile, want, n, dtype=np.float32):
+        """A plane of the stage: n cells when wanted, resized with the payload, disposed of when not."""
+        if tile is not None and (not want or tile.Length != n):
+            tile.Dispose()
+            tile = None
+        if want and tile is None:
+            tile = self.ctx.alloc(n, dtype=dtype)
+        return tile
+
+
+    def Schedule(self, requirements, dependency):
+        d = requirements.data
+        if not isinstance(d, GeneratorData):
+            raise Exception("Unhandled stageio %s" % type(d).__name__)
+        self.resolution, self.count = d.resolution, getattr(d, "count", 1)
+        self.CheckRequirements(GeneratorData, requirements)
+        n = self.count * self.resolution * self.resolution
+        for name, m in (("rainMap", self.rainMap), ("hardness", self.hardness), ("upliftMap", self.upliftMap)):
+            if m is not None and m.Length != n:  # before any launch
+                raise ValueError("MfdFluvialStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
+        self.work = self._size(self.work, True, N.lib.nz_fluvial_implicit_mfd_work_floats(self.resolution, self.count))
+        self.drainageWork = self._size(self.drainageWork, True, N.lib.nz_drainage_mfd_work_floats(self.resolution, self.count))
+        self._area = self._size(self._area, True, n)
+        self._plane = self._size(self._plane, d.write is None, n)
+        self._tally = self._size(self._tally, True, 2, np.int32)
+        budget = self.maxPasses if self.maxPasses is not None else 128 + self.resolution // 2
+        opt = lambda m: m.ptr if m is not None else None
+        batch = isinstance(d, GeneratorDataBatch)
+        drain = N.DrainageMfdDesc(self.rain, self.seaLevel, budget, self.exponent, opt(self.rainMap))
+        # the solve's `proceed`: the drainage call's converged word, the second int32 of its work planes
+        solve = N.FluvialImplicitMfdDesc(self.erodibility, self.uplift, self.dt, self.seaLevel, budget, self.exponent,
+                                         opt(self.hardness), opt(self.upliftMap), self.drainageWork.ptr + 4, self._tally.ptr)
+        tail = (d.resolution, d.count) if batch else (d.resolution,)
+        # the heights ping-pong between the payload's plane and the WRITE plane (or the stage's own)
+        cur, other = d.data, d.write if d.write is not None else self._plane
+        self.jobHandle = self.ctx.call("nz_tile_upload", self._tally.ptr, self._zeros.ctypes.data, 2, dep=dependency)
+        for _ in range(self.iterations):
+            self.ctx.call("nz_drainage_mfd_batch" if batch else "nz_drainage_mfd", cur.ptr, self._area.ptr,
+                          self.drainageWork.ptr, C.byref(drain), *tail, handle=False)
+            self.jobHandle = self.ctx.call("nz_fluvial_implicit_mfd_batch" if batch else "nz_fluvial_implicit_mfd", cur.ptr,
+                                           self._area.ptr, other.ptr, self.work.ptr, C.byref(solve), *tail)
+            cur, other = other, cur
+        if d.write is not None:
+            d.data, d.write = cur, other  # the pair as the run left it: `data` holds the result
+        elif cur is not d.data:           # an odd count ended in the stage's plane
+            self.jobHandle = self.ctx.call("nz_flush_write_slice", d.data.ptr, cur.ptr, n)
+
+    def OnDestroy(self):
+        self.DisposeArrays()
+
+
 class HillslopeDiffusionStage(PipelineStage):
     """Linear hillslope diffusion, dh/dt = diffusivity * laplace(h), as implicit steps of any size (new-framework feature;
     the model is the comment block of nz_hillslope_diffusion in include/noize_hip.h): backward Euler split by direction, two
