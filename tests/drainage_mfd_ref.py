@@ -14,7 +14,7 @@ A[c] = A[c] + (w * A[k]).  Flow goes strictly downhill, so the graph has no cycl
     step(A, I, rain_c)                      one Jacobi step of the gather
     walk(h, ...) -> (A, height)             cells highest first, height = cells of the longest path of the DAG
     jacobi(h, ...) -> (A, steps)            step from rain_c until nothing changes
-    tiled(h, ..., sweeps) -> (A, passes)    the kernel's schedule: 64 x 16 tiles swept against frozen rings
+    tiled(h, ..., sweeps) -> (A, passes)    Jacobi inside the kernel's tiles: 64 x 16 tiles swept against frozen rings
     walk64(h, ...) -> A                     the same text in float64: what float32 rounds"""
 import numpy as np
 

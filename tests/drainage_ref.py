@@ -5,7 +5,7 @@ every schedule of updates ends in the same floats:
     accumulate(h, ...) -> (A, height)  the model as a topological walk: cells highest first (stable sort), each cell
                                        gathering its donors for k ascending; height = cells of the longest flow path
     jacobi(h, ...) -> (A, steps)       fluvial_ref.drainage from rain_c until a step changes nothing
-    tiled(h, ..., sweeps) -> (A, passes)  the kernel's schedule: 64 x 16 tiles swept against frozen rings, at most `sweeps`
+    tiled(h, ..., sweeps) -> (A, passes)  Jacobi inside the kernel's tiles: 64 x 16 tiles swept against frozen rings, at most `sweeps`
                                        sweeps per tile and pass
     serpentine(res) -> h               one channel of res^2 / 2 cells between walls: the long chain"""
 import numpy as np

@@ -9,7 +9,7 @@ Three schedules that must give the same floats:
     flood(h, epsilon, seaLevel)                       a heap priority-flood, cell by cell in order of W
     jacobi(h, epsilon, seaLevel) -> (W, passes)       the whole grid at once, pass after pass
     tiled(h, epsilon, seaLevel, tile, sweeps) -> (W, passes)
-                                                      the kernel's schedule: per pass every tile of `tile` = (columns, rows)
+                                                      Jacobi inside the kernel's tiles: per pass every tile of `tile` = (columns, rows)
                                                       cells sweeps against the frozen ring of the pass before, until a sweep
                                                       changes nothing or `sweeps` of them are done
 `passes` counts the passes that changed a cell.  tiled(..., record=[]) appends one bool array per pass, the last one

@@ -16,7 +16,7 @@ the graph is a DAG whose leaves are fixed, and every schedule of updates ends in
     walk(h, A, ...) -> (h', height)                 the model as a walk, cells lowest first (stable sort); height = the cells
                                                     of the longest path of the flow DAG
     jacobi(h, A, ..., start) -> (h', steps)         step until no bit changes; start "b" (the kernels') or "h"
-    tiled(h, A, ..., tile, sweeps) -> (h', passes)  the kernel's schedule: 64 x 16 tiles swept against frozen rings
+    tiled(h, A, ..., tile, sweeps) -> (h', passes)  Jacobi inside the kernel's tiles: 64 x 16 tiles swept against frozen rings
     one_sweep_passes(h, A, limit, ...) -> passes    the pass launches the kernels need at a sweep cap of 1: a thread's four
                                                     cells left to right and back, everything else as the pass before
     single_closure(h, seaLevel, exponent) -> mask   the cells with exactly one positive weight whose whole downstream path

@@ -17,7 +17,7 @@ start state:
     walk(h, A, ...) -> h'                          the model as a walk, cells lowest first (stable sort)
     jacobi(h, A, ..., start) -> (h', steps)        every cell from its receiver's value of the step before, until a step
                                                    changes no bit; start "b" (the kernels') or "h" (the nothing of all or nothing)
-    tiled(h, A, ..., tile, sweeps) -> (h', passes) the kernel's schedule: 64 x 16 tiles swept against frozen rings
+    tiled(h, A, ..., tile, sweeps) -> (h', passes) Jacobi inside the kernel's tiles: 64 x 16 tiles swept against frozen rings
     step(hn, has, q, b, f) -> h'                   one Jacobi step, for fixed-point checks of a result
     chain(h, iterations, ...) -> (h', A)           the hosts' ImplicitFluvialStage: drainage_ref.accumulate, then walk, per
                                                    iteration"""

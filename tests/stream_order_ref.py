@@ -14,7 +14,7 @@ final values and every schedule of updates ends in the same bytes:
                                                             of the longest chain of channel donors (0: no channel cell)
     jacobi(h, ...) -> (order, link, steps)                  every cell from its donors' values of the step before, from the
                                                             start state ch ? 1 : 0 and ch ? c : -1, until a step changes nothing
-    tiled(h, ..., tile, sweeps) -> (order, link, passes)    the kernel's schedule: 64 x 16 tiles swept against frozen rings, at
+    tiled(h, ..., tile, sweeps) -> (order, link, passes)    Jacobi inside the kernel's tiles: 64 x 16 tiles against frozen rings, at
                                                             most `sweeps` sweeps per tile and pass"""
 import numpy as np
 

@@ -5,7 +5,10 @@ notices rest one pass late, ends in the same floats more slowly.  The count is d
 ring of a tile is frozen during its sweeps and barriers separate the phases -- so it is an integer to compare, not a time
 to bound.  tests/golden/relax_passes.json holds what the series took before the protocol moved into its own header, and what the
 watershed and stream-order series took before their mask kernels, launchers and host drivers were shared; `measure` is
-what recorded either table, on the commit its key names."""
+what recorded either table, on the commit its key names.
+The counts are now also derived: tests/relax_schedule.py is the protocol and the tile schedule in numpy,
+tests/test_relax_schedule.py finds every single-call entry of the table with it on the CPU, and
+tests/test_gpu_relax_schedule.py holds all seven series to it."""
 import json
 import os
 

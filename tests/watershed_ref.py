@@ -12,7 +12,7 @@ cell's final value and every schedule of updates ends in the same bits:
                                                             receiver has its final value already; hops = moves to the label
     jacobi(h, ...) -> (basin, length, steps)                every cell from its receiver's value of the step before, until a
                                                             step changes nothing
-    tiled(h, ..., tile, sweeps) -> (basin, length, passes)  the kernel's schedule: 64 x 16 tiles swept against frozen rings, at
+    tiled(h, ..., tile, sweeps) -> (basin, length, passes)  Jacobi inside the kernel's tiles: 64 x 16 tiles against frozen rings, at
                                                             most `sweeps` sweeps per tile and pass"""
 import numpy as np
 
