@@ -84,6 +84,13 @@ __device__ __forceinline__ float cnoise2(float Px, float Py) {
     return 2.3f * lerpf_(nx0, nx1, fdy);
 }
 
+// A corner falloff max(c - r2, 0) with c < 1 (0.5, or 0.6 in three dimensions), written so that it is ONE instruction:
+// c - r2 <= c < 1, so the upper bound never binds and fminf(fmaxf(v, 0), 1) == fmaxf(v, 0) for every v -- v = NaN gives 0
+// in both (fmaxf returns the other operand), v = -Inf gives 0, and a zero difference is +0 (round-to-nearest) in both.
+// The [0, 1] pair is what the compiler folds into the subtraction's (or the FMA's) clamp bit (the code objects run with
+// DX10_CLAMP, where a clamped NaN is 0 as well): no v_max_f32 behind the v_sub_f32.
+__device__ __forceinline__ float falloff_clamped(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+
 // noise.snoise(float2), Appendix A.3
 __device__ __forceinline__ float snoise2(float vx, float vy) {
     const float Cx = 0.211324865405187f, Cy = 0.366025403784439f;
@@ -103,9 +110,9 @@ __device__ __forceinline__ float snoise2(float vx, float vy) {
     float p0 = permutei(permutei(iy) + ix);
     float p1 = permutei(permutei(iy + i1y) + ix + i1x);
     float p2 = permutei(permutei(iy + 1.0f) + ix + 1.0f);
-    float m0 = fmaxf(0.5f - (x0x * x0x + x0y * x0y), 0.0f);
-    float m1 = fmaxf(0.5f - (x12x * x12x + x12y * x12y), 0.0f);
-    float m2 = fmaxf(0.5f - (x12z * x12z + x12w * x12w), 0.0f);
+    float m0 = falloff_clamped(0.5f - (x0x * x0x + x0y * x0y));
+    float m1 = falloff_clamped(0.5f - (x12x * x12x + x12y * x12y));
+    float m2 = falloff_clamped(0.5f - (x12z * x12z + x12w * x12w));
     m0 = m0 * m0; m1 = m1 * m1; m2 = m2 * m2;
     m0 = m0 * m0; m1 = m1 * m1; m2 = m2 * m2;
     float xa = twice_minus_one(fracf_(p0 * Cw));
@@ -357,7 +364,7 @@ __device__ __forceinline__ float snoise3(float vx, float vy, float vz) {
     for (int k = 0; k < 4; k++) {
         float nr = taylor_inv_sqrt(P[k][0] * P[k][0] + P[k][1] * P[k][1] + P[k][2] * P[k][2]);
         float px = P[k][0] * nr, py = P[k][1] * nr, pz = P[k][2] * nr;
-        m[k] = fmaxf(0.6f - (xs[k][0] * xs[k][0] + xs[k][1] * xs[k][1] + xs[k][2] * xs[k][2]), 0.0f);
+        m[k] = falloff_clamped(0.6f - (xs[k][0] * xs[k][0] + xs[k][1] * xs[k][1] + xs[k][2] * xs[k][2]));
         m[k] = m[k] * m[k];
         pd[k] = px * xs[k][0] + py * xs[k][1] + pz * xs[k][2];
     }
@@ -407,17 +414,46 @@ __device__ __forceinline__ float noise_value(float x, float z, const psr_tables 
 // sequence therefore return bit-identical gradients:
 //   T1[i]  = 16 * permute(i)                                   (a byte offset into T2)
 //   T2[j]  = {a0, h, 1.79284291400159 - 0.85373472095314*(a0*a0 + h*h), 0} of p = permute(j)
-// and a corner costs one ds_read_b32, one ds_read_b128 and three integer adds instead of two
-// permutes and the gradient decode (26 fp32 ops + 4 floors).  About 87 VALU slots per octave-cell
-// instead of 151.
+// and a corner costs one ds_read_b128 and its share of a cell's ds_read2_b32, shift, two shift-adds and select (below)
+// instead of two permutes and the gradient decode (26 fp32 ops + 4 floors).  Per octave-cell 72.5 VALU instructions in
+// the ladder loop of fractal_simplex_tab_kernel<2, false, 0>, 75 in its table loop, 77 with the recurrence, instead of 151.
 constexpr int NZ_T1_N = 292, NZ_T2_N = 580;
 // The tables hold hashes of lattice coordinates reduced to [0, 289]; fp32 mod289 only guarantees that range
 // for |integer| < 2.3e6 (and the skew of snoise stretches a coordinate by up to 1.73).  Samples beyond this
 // limit (NaN included) take the direct evaluation, which follows the reference's arithmetic wherever it leads.
 constexpr float NZ_TAB_LIMIT = 1048576.0f;
 
+// The simplex table kernels stage T1 as PAIRS, U[2 i] = k(i), U[2 i + 1] = k(i) - step (step: one T2 entry, 16 bytes strict,
+// 8 halved), k(i) the global table's entry (or half of it).  A cell reads k0 = U[2 iy] and k2m = U[2 iy + 3] = k(iy + 1) - step
+// with one ds_read2_b32; its corner addresses are a0 = ix * step + k0, a1 = (gt ? a0 : a2m) + step, a2 = a2m + 2 step with
+// a2m = ix * step + k2m: the same 32-bit sums as k0 + ix * step, gt ? a0 + step : a2 and a2 + step, but the steps are
+// constants behind the select and go into the offset field of the gradient reads.  iy <= 289, so the last entry read is
+// U[581], from k(290): inside the global table's NZ_T1_N entries.  k(289) = 0, so k2m and (for ix = 0) a2m can be -step:
+// the LDS address is base + offset in 32 bits, and what is read lies at a2m + step >= 0.
+template <int SH>
+__device__ __forceinline__ void stage_t1_pairs(int *u, const int *__restrict__ t1g) {
+    static_assert(2 * 289 + 3 < 2 * NZ_T1_N, "U[2 iy + 3] for iy <= 289");
+    for (int i = threadIdx.x; i < NZ_T1_N; i += 256) {
+        const int k = t1g[i] >> SH;
+        u[2 * i] = k;
+        u[2 * i + 1] = k - (16 >> SH);
+    }
+}
+// ix * (16 >> SH) + k as one v_lshl_add_u32 each (left to itself the compiler shares one shift between a cell's two sums
+// and spends two adds on top)
+template <int SH>
+__device__ __forceinline__ int corner_base(int ix, int k) {
+    int a;
+    if constexpr (SH == 0)
+        asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(a) : "v"(ix), "v"(k));
+    else
+        asm("v_lshl_add_u32 %0, %1, 3, %2" : "=v"(a) : "v"(ix), "v"(k));
+    return a;
+}
+
 // (returns snoise / 2: see the end).  (ux, uy) are the skewed coordinates v + s of (vx, vy): snoise2_tab below forms them
 // with the reference's operations, the power-of-two octave ladder scales octave 0's (fractal_simplex_tab_kernel).
+// s_t1 is the staged pair form of T1 (stage_t1_pairs<0>).
 __device__ __forceinline__ float snoise2_tab_skewed(float vx, float vy, float ux, float uy, const int *s_t1,
                                                     const float4 *s_t2) {
     const float Cx = 0.211324865405187f, Cz = -0.577350269189626f;
@@ -433,20 +469,19 @@ __device__ __forceinline__ float snoise2_tab_skewed(float vx, float vy, float ux
     // fp32 mod289 returns 289 (not 0) for some negative multiples of 289 (-8959, -17629, ...): the tables carry
     // that index.  Callers guarantee |v| < NZ_TAB_LIMIT (or NaN, which converts to index 0 and poisons the result
     // through x0 anyway), so both indices are in [0, 289] without a clamp
-    int ix16 = ixi << 4;
     // corner 1 is (ix + 1, iy) or (ix, iy + 1): its T1 entry is one of the two already read, selected, not re-read
-    int k0 = s_t1[iyi], k2 = s_t1[iyi + 1];
+    int k0 = s_t1[2 * iyi], k2m = s_t1[2 * iyi + 3];
     const char *t2 = reinterpret_cast<const char *>(s_t2);
-    int a0 = k0 + ix16, a2 = k2 + ix16;
-    int a1 = gt ? a0 + 16 : a2;
+    int a0 = corner_base<0>(ixi, k0), a2m = corner_base<0>(ixi, k2m);
+    int a1m = gt ? a0 : a2m;
     float4 g0 = *reinterpret_cast<const float4 *>(t2 + a0);
-    float4 g1 = *reinterpret_cast<const float4 *>(t2 + a1);
-    float4 g2 = *reinterpret_cast<const float4 *>(t2 + (a2 + 16));
+    float4 g1 = *reinterpret_cast<const float4 *>(t2 + a1m + 16);
+    float4 g2 = *reinterpret_cast<const float4 *>(t2 + a2m + 32);
     // keep the padding lane live: a 16-byte LDS read takes 4 LDS cycles per wave, the 12-byte form 8
     asm volatile("" ::"v"(g0.w), "v"(g1.w), "v"(g2.w));
-    float m0 = fmaxf(0.5f - (x0x * x0x + x0y * x0y), 0.0f);
-    float m1 = fmaxf(0.5f - (x12x * x12x + x12y * x12y), 0.0f);
-    float m2 = fmaxf(0.5f - (x12z * x12z + x12w * x12w), 0.0f);
+    float m0 = falloff_clamped(0.5f - (x0x * x0x + x0y * x0y));
+    float m1 = falloff_clamped(0.5f - (x12x * x12x + x12y * x12y));
+    float m2 = falloff_clamped(0.5f - (x12z * x12z + x12w * x12w));
     m0 = m0 * m0; m1 = m1 * m1; m2 = m2 * m2;
     m0 = m0 * m0; m1 = m1 * m1; m2 = m2 * m2;
     m0 *= g0.z;
@@ -474,7 +509,7 @@ __device__ __forceinline__ float rectify_half(float half_v) { return 0.5f + half
 // indices -- and contracts only the smooth polynomial tail: the corner falloffs m = 0.5 - x.x as two FMAs, the gradient
 // dots and the corner sum as FMAs, the corner normalisation folded into the staged gradient table (g * norm, one rounding
 // more per component), 130 * n -> rectify -> a * r folded into one FMA per octave-cell (t += (65 a) * n; the 0.5 a terms are
-// wave-uniform and added once per cell).  Per octave-cell 63 VALU instructions instead of 83; every difference from the strict
+// wave-uniform and added once per cell).  Per octave-cell 59 VALU instructions instead of 75; every difference from the strict
 // form is a rounding of relative size 2^-24 in a term of the octave, i.e. <= ~2e-7 relative on the fBm sum.
 __device__ __forceinline__ float snoise2_tab_fast(float vx, float vy, const int *s_t1, const float2 *s_t2) {
     const float Cx = 0.211324865405187f, Cy = 0.366025403784439f, Cz = -0.577350269189626f;
@@ -487,17 +522,16 @@ __device__ __forceinline__ float snoise2_tab_fast(float vx, float vy, const int 
     float x12x = x0x + (gt ? Cx - 1.0f : Cx), x12y = x0y + (gt ? Cx : Cx - 1.0f);
     float x12z = x0x + Cz, x12w = x0y + Cz;
     int ixi = (int)mod289i(fx), iyi = (int)mod289i(fy);
-    int ix8 = ixi << 3;
-    int k0 = s_t1[iyi], k2 = s_t1[iyi + 1];  // 8 * permute (staged halved)
+    int k0 = s_t1[2 * iyi], k2m = s_t1[2 * iyi + 3];  // 8 * permute, 8 * permute - 8 (stage_t1_pairs<1>)
     const char *t2 = reinterpret_cast<const char *>(s_t2);
-    int a0 = k0 + ix8, a2 = k2 + ix8;
-    int a1 = gt ? a0 + 8 : a2;
+    int a0 = corner_base<1>(ixi, k0), a2m = corner_base<1>(ixi, k2m);
+    int a1m = gt ? a0 : a2m;
     float2 g0 = *reinterpret_cast<const float2 *>(t2 + a0);
-    float2 g1 = *reinterpret_cast<const float2 *>(t2 + a1);
-    float2 g2 = *reinterpret_cast<const float2 *>(t2 + (a2 + 8));
-    float m0 = fmaxf(__builtin_fmaf(-x0y, x0y, __builtin_fmaf(-x0x, x0x, 0.5f)), 0.0f);
-    float m1 = fmaxf(__builtin_fmaf(-x12y, x12y, __builtin_fmaf(-x12x, x12x, 0.5f)), 0.0f);
-    float m2 = fmaxf(__builtin_fmaf(-x12w, x12w, __builtin_fmaf(-x12z, x12z, 0.5f)), 0.0f);
+    float2 g1 = *reinterpret_cast<const float2 *>(t2 + a1m + 8);
+    float2 g2 = *reinterpret_cast<const float2 *>(t2 + a2m + 16);
+    float m0 = falloff_clamped(__builtin_fmaf(-x0y, x0y, __builtin_fmaf(-x0x, x0x, 0.5f)));
+    float m1 = falloff_clamped(__builtin_fmaf(-x12y, x12y, __builtin_fmaf(-x12x, x12x, 0.5f)));
+    float m2 = falloff_clamped(__builtin_fmaf(-x12w, x12w, __builtin_fmaf(-x12z, x12z, 0.5f)));
     m0 = m0 * m0; m1 = m1 * m1; m2 = m2 * m2;
     m0 = m0 * m0; m1 = m1 * m1; m2 = m2 * m2;
     float q0 = __builtin_fmaf(g0.x, x0x, g0.y * x0y);
@@ -558,17 +592,25 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
                                                                  const int *__restrict__ t1g,
                                                                  const float4 *__restrict__ t2g, nz_ridge_params rp,
                                                                  nz_octave_table oct) {
-    __shared__ int s_t1[NZ_T1_N];
-    __shared__ float4 s_t2[FAST ? 1 : NZ_T2_N];
-    __shared__ float2 s_t2f[FAST ? NZ_T2_N : 1];  // tolerance mode: {a0, h} * norm, 8-byte entries (T1 staged as 8 * permute)
+    // one block, T1's pairs first: they sit at LDS offset 0, so a cell's T1 address is iy << 3 alone, and T2's base
+    // (2 NZ_T1_N ints = 2336 bytes, a multiple of 16) goes into the offset field of the gradient reads
+    struct simplex_lds {
+        int t1[2 * NZ_T1_N];
+        float4 t2[FAST ? 1 : NZ_T2_N];
+        float2 t2f[FAST ? NZ_T2_N : 1];  // tolerance mode: {a0, h} * norm, 8-byte entries (T1 staged as 8 * permute)
+    };
+    __shared__ simplex_lds s_tab;
+    int *const s_t1 = s_tab.t1;
+    float4 *const s_t2 = s_tab.t2;
+    float2 *const s_t2f = s_tab.t2f;
     if constexpr (FAST) {
-        for (int i = threadIdx.x; i < NZ_T1_N; i += 256) s_t1[i] = t1g[i] >> 1;
+        stage_t1_pairs<1>(s_t1, t1g);
         for (int i = threadIdx.x; i < NZ_T2_N; i += 256) {
             const float4 g = t2g[i];
             s_t2f[i] = make_float2(g.x * g.z, g.y * g.z);
         }
     } else {
-        for (int i = threadIdx.x; i < NZ_T1_N; i += 256) s_t1[i] = t1g[i];
+        stage_t1_pairs<0>(s_t1, t1g);
         for (int i = threadIdx.x; i < NZ_T2_N; i += 256) s_t2[i] = t2g[i];
     }
     __syncthreads();
@@ -944,7 +986,7 @@ __device__ __forceinline__ float snoise3_tab(float vx, float vy, float vz, const
         int h = s_p[s_p[s_p[ii[2] + oz[k]] + ii[1] + oy[k]] + ii[0] + ox[k]];
         float4 p = s_g[h];
         asm volatile("" ::"v"(p.w));
-        float m = fmaxf(0.6f - (xs[k][0] * xs[k][0] + xs[k][1] * xs[k][1] + xs[k][2] * xs[k][2]), 0.0f);
+        float m = falloff_clamped(0.6f - (xs[k][0] * xs[k][0] + xs[k][1] * xs[k][1] + xs[k][2] * xs[k][2]));
         m = m * m;
         float pd = p.x * xs[k][0] + p.y * xs[k][1] + p.z * xs[k][2];
         acc[k] = (m * m) * pd;

@@ -24,14 +24,15 @@ struct warp_lds {
     static constexpr bool TAB2 = BASIS == NZ_NOISE_PERLIN || BASIS == NZ_NOISE_CELLULAR;
     static constexpr bool TAB3 = BASIS == NZ_NOISE_DOMAIN_ROTATED_PERLIN || BASIS == NZ_NOISE_DOMAIN_ROTATED_SIMPLEX;
     static constexpr bool PSR = BASIS == NZ_NOISE_PERIODIC_PERLIN || BASIS == NZ_NOISE_ROTATED_SIMPLEX;
-    static constexpr int BYTES = SIMPLEX ? NZ_T1_N * 4 + NZ_T2_N * 16 + (FAST ? NZ_T1_N * 4 + NZ_T2_N * 8 : 0)
+    static constexpr int T1_PAIRS = 2 * NZ_T1_N * 4;  // simplex T1 as staged: stage_t1_pairs, 2336 bytes (a multiple of 16)
+    static constexpr int BYTES = SIMPLEX ? T1_PAIRS + NZ_T2_N * 16 + (FAST ? T1_PAIRS + NZ_T2_N * 8 : 0)
                                  : TAB2  ? NZ_TB1_N * 4 + NZ_TB2_N * 8
                                  : TAB3  ? NZ_P3_N * 4 + NZ_G3_N * 16
                                  : PSR   ? NZ_PSR_T2 * 8 + NZ_PSR_T1 * 4
                                          : 16;
-    const int *i1;      // simplex T1 / P1 / C1 / P3 / psr T1
+    const int *i1;      // simplex T1 (pairs) / P1 / C1 / P3 / psr T1
     const void *t2;     // simplex T2 (float4) / P2 / C2 (float2) / G3 (float4) / psr T2 (float2)
-    const int *i1f;     // FAST simplex: T1 / 2
+    const int *i1f;     // FAST simplex: T1 / 2 (pairs)
     const float2 *t2f;  // FAST simplex: {a0, h} * norm
 
     // stage the tables from `tab` (the context's table block of this basis, see nz_launch_fractal_warped) into `s`
@@ -39,17 +40,17 @@ struct warp_lds {
         char *b = reinterpret_cast<char *>(s);
         if constexpr (SIMPLEX) {
             int *t1 = reinterpret_cast<int *>(b);
-            float4 *g = reinterpret_cast<float4 *>(b + NZ_T1_N * 4);
+            float4 *g = reinterpret_cast<float4 *>(b + T1_PAIRS);
             const int *t1g = reinterpret_cast<const int *>(tab);
             const float4 *t2g = reinterpret_cast<const float4 *>(t1g + NZ_T1_N);
-            for (int i = threadIdx.x; i < NZ_T1_N; i += 256) t1[i] = t1g[i];
+            stage_t1_pairs<0>(t1, t1g);
             for (int i = threadIdx.x; i < NZ_T2_N; i += 256) g[i] = t2g[i];
             i1 = t1;
             t2 = g;
             if constexpr (FAST) {
-                int *h1 = reinterpret_cast<int *>(b + NZ_T1_N * 4 + NZ_T2_N * 16);
-                float2 *h2 = reinterpret_cast<float2 *>(b + 2 * NZ_T1_N * 4 + NZ_T2_N * 16);
-                for (int i = threadIdx.x; i < NZ_T1_N; i += 256) h1[i] = t1g[i] >> 1;
+                int *h1 = reinterpret_cast<int *>(b + T1_PAIRS + NZ_T2_N * 16);
+                float2 *h2 = reinterpret_cast<float2 *>(b + 2 * T1_PAIRS + NZ_T2_N * 16);
+                stage_t1_pairs<1>(h1, t1g);
                 for (int i = threadIdx.x; i < NZ_T2_N; i += 256) {
                     const float4 v = t2g[i];
                     h2[i] = make_float2(v.x * v.z, v.y * v.z);
