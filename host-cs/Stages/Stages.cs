@@ -282,6 +282,7 @@ namespace xshazwar.noize.hip {
             }
             CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
             GeneratorData d = (GeneratorData) requirements.data;
+            if (!recordMasks) { masks?.Dispose(); masks = null; }  // switched off after a payload of this length: Wear and Deposits are empty again
             ulong h;
             if (border != HydraulicBorder.Closed || rainMap != null || hardness != null || recordMasks) {
                 foreach (DeviceTile m in new[] { rainMap, hardness })   // before any launch

@@ -17,6 +17,10 @@
 //                            1 exchange, 2 exchange_once)
 //          host_demo <resolution> <out.f32> sharded-rank <rank> <world> <idfile> [mode]   (one process per GPU, device =
 //                            rank; rank 0 writes the ncclUniqueId to <idfile>; every rank writes its rows to <out.f32>.<rank>)
+//          host_demo <resolution> <out.bin> stage <StageName> <in.f32>   (one stage class through its scenario of
+//                            host_demo_stages.hpp on the planes of <in.f32>: every plane read back goes to <out.bin>, a
+//                            "plane <name> <type> <elements>" line each and a "value <name> <int>" line per scalar on stdout)
+//          host_demo 0 - stage --list   (the scenario names, one per line; needs no device)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,6 +29,7 @@
 #include <vector>
 
 #include "noize_pipeline.hpp"
+#include "host_demo_stages.hpp"
 
 using namespace noize;
 
@@ -40,6 +45,7 @@ int main(int argc, char **argv) {
         std::fprintf(stderr, "usage: %s <resolution> <out.f32> [G F E]\n", argv[0]);
         return 2;
     }
+    if (argc > 4 && std::strcmp(argv[3], "stage") == 0) return stage_demo::main_stage(argc, argv);
     int res = std::atoi(argv[1]);
     const bool reduce = argc > 3 && std::strcmp(argv[3], "reduce") == 0;
     const bool context = argc > 3 && std::strcmp(argv[3], "context") == 0;

@@ -666,6 +666,7 @@ class HydraulicErosionStage : public PipelineStage {
         resolution = g->resolution;
         count = tile_count(g);
         auto *d = CheckRequirements<GeneratorData>(requirements);  // sized on the payload's count * resolution^2 cells
+        if (!recordMasks) masks.reset();  // switched off after a payload of this length: wear() and deposits() are empty again
         nz_handle h = 0;
         if (border != HydraulicBorder::Closed || rainMap || hardness || recordMasks) {
             for (const DeviceTile *m : {rainMap, hardness})  // before any launch
@@ -952,6 +953,7 @@ class DrainageAreaStage : public PipelineStage {
     size_t drainageLength() const { return (size_t)count * resolution * resolution; }
     int passes() const { return status(0); }                // -1 before the first run
     bool converged() const { return status(1) == 1; }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); plane.reset(); }
 
   private:
@@ -1015,6 +1017,7 @@ class MfdDrainageStage : public PipelineStage {
     size_t drainageLength() const { return (size_t)count * resolution * resolution; }
     int passes() const { return status(0); }                // -1 before the first run
     bool converged() const { return status(1) == 1; }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); plane.reset(); }
 
   private:
@@ -1081,6 +1084,7 @@ class WatershedStage : public PipelineStage {
     size_t cells() const { return (size_t)count * resolution * resolution; }
     int passes() const { return status(0); }                // -1 before the first run
     bool converged() const { return status(1) == 1; }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); labels.reset(); lengths.reset(); codes.reset(); }
 
   private:
@@ -1147,6 +1151,7 @@ class StreamOrderStage : public PipelineStage {
     size_t cells() const { return (size_t)count * resolution * resolution; }
     int passes() const { return status(0); }                // -1 before the first run
     bool converged() const { return status(1) == 1; }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); orders.reset(); linkPlane.reset(); }
 
   private:
@@ -1249,6 +1254,7 @@ class ImplicitFluvialStage : public PipelineStage {
     int steps() const { return counted(0); }                 // -1 before the first run
     int passes() const { return counted(1); }
     bool converged() const { return counted(0) == iterations; }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); drainageWork.reset(); area.reset(); plane.reset(); tally.reset(); }
 
   private:
@@ -1342,6 +1348,7 @@ class MfdFluvialStage : public PipelineStage {
     int steps() const { return counted(0); }                 // -1 before the first run
     int passes() const { return counted(1); }
     bool converged() const { return counted(0) == iterations; }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); drainageWork.reset(); area.reset(); plane.reset(); tally.reset(); }
 
   private:
@@ -1390,6 +1397,7 @@ class HillslopeDiffusionStage : public PipelineStage {
                   "nz_hillslope_diffusion");
         jobHandle = done(h);
     }
+    size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); }
 
   private:

@@ -818,6 +818,10 @@ class HydraulicErosionStage(PipelineStage):
 
     def _desc(self):
         """The nz_hydraulic_desc of the extended entries, or None when every option is at its default."""
+        if not self.recordMasks and self.masks is not None:  # (switched off after a payload: wear and deposits are empty again)
+            if self.masks.IsCreated:
+                self.masks.Dispose()
+            self.masks = None
         if (int(self.border) == HydraulicBorder.Closed and self.rainMap is None and self.hardness is None
                 and not self.recordMasks):
             return None

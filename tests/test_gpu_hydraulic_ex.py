@@ -240,3 +240,23 @@ def test_refusals_write_nothing(nj, ctx):
     assert_bits(wear.ToArray((res, res)), want[2], "after the refusals: wear")
     for t in (d, other, wear, deposits, rain, work, small):
         t.Dispose()
+
+
+# 7. recordMasks switched off between two payloads of equal length: the stage drops the planes, wear and deposits are empty again
+def test_masks_switched_off_are_dropped(nj, ctx):
+    res = 64
+    h = relief(res)
+    hyd = nj.HydraulicErosionStage(ctx, iterations=3, recordMasks=True)
+    d = nj.GeneratorData("h", ctx.from_host(h), res, 0, 0)
+    hyd.ReceiveHandledInput(nj.PipelineWorkItem(d), nj.JobHandle())
+    hyd.jobHandle.Complete()
+    want = X.run(h, 3)
+    assert_bits(hyd.wear.ToArray((res, res)), want[2], "wear")
+    hyd.recordMasks = False
+    d.data.CopyFrom(h)
+    hyd.ReceiveHandledInput(nj.PipelineWorkItem(d), nj.JobHandle())
+    hyd.jobHandle.Complete()
+    assert hyd.wear is None and hyd.deposits is None
+    assert_bits(d.data.ToArray((res, res)), want[0], "the plain entries after the masks")
+    hyd.Destroy()
+    d.data.Dispose()
