@@ -969,6 +969,37 @@ namespace xshazwar.noize.hip {
         public override void OnDestroy() { work?.Dispose(); work = null; }
     }
 
+    public class ImplicitFluvialStripe {
+        // The implicit stream-power solve on one row stripe of a larger grid (nz_implicit_fluvial_stripe_round / _finalise): the
+        // round and the finalise that DrainageAreaStage has for the drainage area, for the solve behind it.  No pipeline stage --
+        // a stripe has no payload -- so no base class: the planes and words are the caller's, and so are the exchanges and the
+        // votes.  Per step on every rank: DrainageAreaStage's rounds on the current heights; then rounds of ScheduleStripe -- 1
+        // row of heightRows exchanged before the round with `first`, 1 row of outRows before every later one, a vote after each
+        // (nz_comm_allreduce_max_i32 on `changed`, which the next round takes as its `proceed`; IntPtr.Zero in the first) -- and
+        // FinaliseStripe with the verdict "the last vote was 0"; then the two height planes swap.
+        readonly GpuContext ctx;
+        public float erodibility = 0.05f, uplift = 0.002f, dt = 1f, seaLevel = -3.402823466e+38f;
+        public IntPtr hardnessRows = IntPtr.Zero, upliftMapRows = IntPtr.Zero;  // stripe-shaped planes, owned rows filled; Zero: off
+        public ImplicitFluvialStripe(GpuContext ctx) { this.ctx = ctx; }
+        // one round: at most `passes` passes over the owned rows against one frozen ghost row of h' on each side (stripeWork:
+        // Native.nz_implicit_fluvial_stripe_work_floats, the same buffer in every round of a solve)
+        public GpuJobHandle ScheduleStripe(IntPtr heightRows, IntPtr drainageRows, IntPtr outRows, IntPtr stripeWork, ref NzStripe st,
+                                           int passes, bool first, IntPtr proceed, IntPtr changed, GpuJobHandle dependency) {
+            var desc = new NzFluvialImplicitDesc { erodibility = erodibility, uplift = uplift, dt = dt, seaLevel = seaLevel, maxPasses = passes,
+                                                   hardness = hardnessRows, upliftMap = upliftMapRows, proceed = IntPtr.Zero, tally = IntPtr.Zero };
+            ulong h;
+            Native.Check(Native.nz_implicit_fluvial_stripe_round(ctx.Handle, heightRows, drainageRows, outRows, stripeWork, ref st, ref desc, first ? 1 : 0, proceed, changed, dependency.id, out h), "nz_implicit_fluvial_stripe_round");
+            return ctx.Wrap(h);
+        }
+        // ... and the end of the rounds: all or nothing on the owned rows by the device word `converged` -- outRows stays, or
+        // takes heightRows bit for bit
+        public GpuJobHandle FinaliseStripe(IntPtr heightRows, IntPtr outRows, ref NzStripe st, IntPtr converged, GpuJobHandle dependency) {
+            ulong h;
+            Native.Check(Native.nz_implicit_fluvial_stripe_finalise(ctx.Handle, heightRows, outRows, ref st, converged, dependency.id, out h), "nz_implicit_fluvial_stripe_finalise");
+            return ctx.Wrap(h);
+        }
+    }
+
     public class MeshTileStage : PipelineStage {
         public MeshType meshType = MeshType.SquareGridHeightMap;
         public MeshTileStage(GpuContext ctx) : base(ctx) {}

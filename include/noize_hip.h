@@ -1315,7 +1315,8 @@ int32_t nz_debug_stream_order_sweeps(int32_t sweeps);
  * work; erodibility, uplift, dt or seaLevel not finite (-FLT_MAX switches the sea off); erodibility, uplift or dt < 0;
  * maxPasses < 1; count * resolution^2 beyond int32; out or work overlapping height, drainage, a map or each other (`out`
  * must not be `height`: the solve is not in place); tally overlapping a plane or proceed; proceed inside out or work.
- * There is no row-stripe form and no _rw pair form. */
+ * The row-stripe form is nz_implicit_fluvial_stripe_round / _finalise, below; there is no _rw pair form (DESIGN.md
+ * section 9). */
 typedef struct nz_fluvial_implicit_desc {
     float erodibility, uplift, dt, seaLevel;
     int32_t maxPasses;
@@ -1333,6 +1334,50 @@ int32_t nz_fluvial_implicit_batch(nz_ctx *ctx, const float *height, const float 
 /* Test hook, the twin of nz_debug_watershed_sweeps: the cap on an implicit-fluvial pass's on-chip sweeps per tile
  * (process-wide; <= 0 restores the default, 16).  Results must not change.  Returns the cap that was in force. */
 int32_t nz_debug_fluvial_implicit_sweeps(int32_t sweeps);
+/* The same model on a row stripe of a larger grid (nz_stripe), one ROUND per call, in the wording of
+ * nz_drainage_stripe_round.  The receiver graph is a forest whose roots are fixed and a cell's h' is a fixed function of one
+ * other cell's h', so rounds of per-stripe relaxation against one frozen ghost row of h' on each side, with one row of
+ * `out` exchanged between them, reach the monolithic plane bit for bit, from any start state.  All planes have the stripe's
+ * shape and pitch, `drainage`, desc->hardness and desc->upliftMap included; grids may be rectangular.
+ *   (The four entries carry the hosts' word order, nz_implicit_fluvial_stripe_*, after ImplicitFluvialStripe: the prefix
+ *   nz_fluvial_implicit_ stays that of the tile and batch entries, the test hook and the desc.)
+ *   nz_implicit_fluvial_stripe_round runs at most desc->maxPasses passes of the tile entry's pass (the sweep cap
+ *     nz_debug_fluvial_implicit_sweeps included) over the owned rows; the first pass of a round starts a fresh series and
+ *     visits every tile, because the ghost rows may have changed.  The one ghost row of `out` on each side is FROZEN: read,
+ *     never written, whichever plane a pass alternates to.  Outlets, and neighbours that do not exist, follow the GLOBAL grid
+ *     (global rows 0 and grows-1, columns 0 and cols-1; h <= seaLevel); a cut is no border.  Rows beyond the ghost row are
+ *     neither read nor written, nor are the floats between cols and pitch.
+ *   first != 0: a stripe form of the setup launch stores, for the owned rows only, the receiver byte, b and f into `work`.
+ *     The heights are read at radius 1, so `height` needs ONE valid ghost row towards every cut; `drainage`, hardness and
+ *     upliftMap are read on the owned rows only.  `out` is not read: the start state is b on the owned rows, and the frozen
+ *     rows are the ghost rows of `height` as they stand (any start gives the same fixed point, and this needs no ghost row
+ *     of the maps).  `changed` receives 1.
+ *   first == 0: `height`, `drainage` and the maps are not read; `work` must be the buffer of the round before, untouched in
+ *     between (it carries the receiver bytes and the coefficients); the current h' is read from `out`, whose ghost rows the
+ *     caller has exchanged.  `changed` (device) receives 1 if any single update of any pass of the round changed a bit, a
+ *     budget that ran out before rest included; 0 only when the round's first pass found every owned cell at rest against
+ *     the ghost rows.
+ *   On return the owned rows of `out` hold the stripe's h', whatever the parity of the passes that ran.
+ *   proceed (device, may be NULL): a word of zero makes every launch of the call return at once -- `out` untouched,
+ *     `changed` 0 -- so that a host can enqueue a fixed budget of rounds without reading anything back.  desc->proceed and
+ *     desc->tally must be NULL here: the round's own argument and the driver take their place.
+ *   `work` = nz_implicit_fluvial_stripe_work_floats(st) floats, the tile entry's layout over the stripe's plane: status
+ *     words and tile bytes (over the owned rows), the receiver bytes, b, f, a second h' plane.
+ *   nz_implicit_fluvial_stripe_finalise, on the owned rows: where *converged != 0, `out` stays; otherwise out = height bit
+ *     for bit -- all or nothing, as in the tile entry.  `converged` is the caller's verdict: the vote over all ranks after
+ *     the last round was 0 (nz_comm_allreduce_max_i32).
+ *   One stripe over a square grid with `first`, a second round whose `changed` is 0, then finalise with a word of 1, equals
+ *     nz_fluvial_implicit bit for bit, on the 16-byte path (all planes 16-byte aligned, pitch % 4 == 0) and the 4-byte one.
+ * NZ_ERR_INVALID, the message naming the argument, and nothing written: everything nz_fluvial_implicit refuses; a non-NULL
+ * desc->proceed or desc->tally; a missing ghost row; a NULL plane or word; out, work, the read planes or the two words
+ * overlapping where one of them is written. */
+int32_t nz_implicit_fluvial_stripe_halo_rows(void); /* 1: the heights, and `out` between rounds */
+size_t nz_implicit_fluvial_stripe_work_floats(const nz_stripe *st);
+int32_t nz_implicit_fluvial_stripe_round(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                         const nz_stripe *st, const nz_fluvial_implicit_desc *desc, int32_t first,
+                                         const int32_t *proceed, int32_t *changed, nz_handle dep, nz_handle *out_handle);
+int32_t nz_implicit_fluvial_stripe_finalise(nz_ctx *ctx, const float *height, float *out, const nz_stripe *st,
+                                            const int32_t *converged, nz_handle dep, nz_handle *out_handle);
 
 /* ---- hillslope diffusion: dh/dt = kappa * laplace(h) in one implicit step of any size (new-framework feature) ------------
  * The second term of every landscape-evolution model beside stream power (FastScape pairs the two): linear diffusion rounds

@@ -281,6 +281,11 @@ SIGNATURES = {
     "nz_fluvial_implicit": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i] + _tail),
     "nz_fluvial_implicit_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fimp_p, _i, _i] + _tail),
     "nz_debug_fluvial_implicit_sweeps": (_i, [_i]),
+    "nz_implicit_fluvial_stripe_halo_rows": (_i, []),
+    "nz_implicit_fluvial_stripe_work_floats": (_sz, [stripe_p]),
+    "nz_implicit_fluvial_stripe_round": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, stripe_p, fimp_p, _i, dev_ptr,
+                                              dev_ptr] + _tail),
+    "nz_implicit_fluvial_stripe_finalise": (_i, [ctx_p, dev_ptr, dev_ptr, stripe_p, dev_ptr] + _tail),
     "nz_fluvial_implicit_mfd_work_floats": (_sz, [_i, _i]),
     "nz_fluvial_implicit_mfd": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fmfd_p, _i] + _tail),
     "nz_fluvial_implicit_mfd_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fmfd_p, _i, _i] + _tail),

@@ -530,6 +530,21 @@ int32_t nz_launch_fluvial_implicit_pass(hipStream_t s, const unsigned char *recv
                                         const float *h_in, float *h_out, int *status, const unsigned char *flags_in,
                                         unsigned char *flags_out, int res, int count, int pass, int sweeps);
 int32_t nz_launch_fluvial_implicit_finalise(hipStream_t s, const float *h, float *out, int *status, int *tally, size_t n);
+// the stripe form, one round (nz_implicit_fluvial_stripe_round), between the fill stripe's round_begin and round_end launches:
+// setup stores the receiver byte, b and f of the owned rows [g.or0, g.or1) at the cells' plane indices, from heights up to one
+// row beyond them; a pass works on the owned rows of stripe-shaped planes against the frozen rows or0 - 1 and or1 of the
+// caller's plane -- h_in of an even pass, h_out of an odd one -- or, with first, of ghost_h, the heights; [zlo, zhi] the
+// global grid in buffer rows; finalise is all or nothing on the owned rows by the caller's verdict
+int32_t nz_launch_fluvial_implicit_stripe_setup(hipStream_t s, const float *h, const float *area, const float *hardness,
+                                                const float *uplift_map, unsigned char *recv, float *bco, float *fco,
+                                                const int *status, float erodibility, float uplift, float dt, float sea,
+                                                const nz_geom &g, int zlo, int zhi);
+int32_t nz_launch_fluvial_implicit_stripe_pass(hipStream_t s, const unsigned char *recv, const float *bco, const float *fco,
+                                               const float *h_in, float *h_out, const float *ghost_h, int *status,
+                                               const unsigned char *flags_in, unsigned char *flags_out, int *changed,
+                                               const nz_geom &g, int zlo, int zhi, int first, int pass, int sweeps);
+int32_t nz_launch_fluvial_implicit_stripe_finalise(hipStream_t s, const float *h, float *out, const int *converged,
+                                                   const nz_geom &g);
 
 // multiple-flow implicit fluvial erosion (nz_fluvial_implicit_mfd.hip); begin and finalise are the two launches above.
 // setup: heights, drainage `area` and the maps (NULL: none) -> one gate byte per cell (bit k: the weight towards neighbour k

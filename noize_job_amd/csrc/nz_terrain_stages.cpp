@@ -1076,6 +1076,69 @@ extern "C" int32_t nz_fluvial_implicit_batch(nz_ctx *ctx, const float *height, c
     return fluvial_implicit_impl(ctx, height, drainage, out, work, desc, resolution, count, dep, out_handle);
 }
 
+// ---- the stripe form (include/noize_hip.h): one round of passes on the owned rows against one frozen row of h' on each side ----
+// `work` is laid out as in the tile form, over the stripe's plane.  The round's begin and end launches are the fill stripe's:
+// they know status words and planes only.
+extern "C" int32_t nz_implicit_fluvial_stripe_halo_rows(void) { return 1; }
+
+extern "C" size_t nz_implicit_fluvial_stripe_work_floats(const nz_stripe *st) {
+    return stripe_has_work(st) ? fluvial_implicit_work_of(nullptr, stripe_shape(*st)).hd.total : 0;
+}
+
+extern "C" int32_t nz_implicit_fluvial_stripe_round(nz_ctx *ctx, const float *height, const float *drainage, float *outp,
+                                                    float *work, const nz_stripe *st, const nz_fluvial_implicit_desc *desc,
+                                                    int32_t first, const int32_t *proceed, int32_t *changed, nz_handle dep,
+                                                    nz_handle *out_handle) {
+    NZ_BEGIN(ctx, dep);
+    NZ_REQUIRE(desc, "desc is NULL");
+    const implicit_args a = implicit_args_of(*desc);
+    NZ_TRY(check_implicit_scalars(height, drainage, outp, work, a));
+    NZ_REQUIRE(!desc->proceed, "desc->proceed must be NULL in a stripe round: the round has its own proceed word");
+    NZ_REQUIRE(!desc->tally, "desc->tally must be NULL in a stripe round: the driver counts");
+    NZ_TRY(nz_check_stripe(st, 1));  // the heights, and `out` between rounds, at radius 1
+    NZ_REQUIRE(changed, "changed is NULL");
+    const nz_geom g = nz_geom_from_stripe(*st);
+    const fluvial_implicit_work k = fluvial_implicit_work_of(work, stripe_shape(*st));
+    const size_t span = nz_stripe_span(*st);
+    NZ_REQUIRE(nz_stripe_plane_floats(st) <= (size_t)INT32_MAX, "stripe: %zu cells are beyond int32", nz_stripe_plane_floats(st));
+    const nz_named_plane writes[] = {{"out", outp, span}, {"work", work, k.hd.total}};
+    const nz_named_plane reads[] = {{"height", height, span}, {"drainage", drainage, span}, {"hardness", a.hardness, span},
+                                    {"upliftMap", a.upliftMap, span}};
+    NZ_TRY(nz_require_disjoint(writes, std::size(writes), reads, std::size(reads)));
+    const nz_named_plane all[] = {writes[0], writes[1], reads[0], reads[1], reads[2], reads[3]};
+    NZ_TRY(check_stripe_words(changed, "changed", proceed, "proceed", all, std::size(all)));
+    const int sweeps = fluvial_implicit_sweeps.load();
+    const int zlo = nz_stripe_grid_lo(*st), zhi = nz_stripe_grid_hi(*st) - 1;
+    return run_stripe_round(
+        ctx, out_handle, desc->maxPasses, k.hd, outp, k.h2, proceed, changed, first, g,
+        [&]() -> int32_t {  // the receiver bytes and coefficients of a round that continues stand in `work`
+            if (!first) return NZ_OK;
+            return nz_launch_fluvial_implicit_stripe_setup(ctx->stream, height, drainage, a.hardness, a.upliftMap, k.recv, k.b,
+                                                           k.f, k.hd.status, a.erodibility, a.uplift, a.dt, a.seaLevel, g, zlo,
+                                                           zhi);
+        },
+        [&](int p, const float *h_in, float *h_out, const unsigned char *flags_in, unsigned char *flags_out) {
+            return nz_launch_fluvial_implicit_stripe_pass(ctx->stream, k.recv, k.b, k.f, h_in, h_out, height, k.hd.status,
+                                                          flags_in, flags_out, changed, g, zlo, zhi, first != 0, p, sweeps);
+        });
+}
+
+extern "C" int32_t nz_implicit_fluvial_stripe_finalise(nz_ctx *ctx, const float *height, float *outp, const nz_stripe *st,
+                                                       const int32_t *converged, nz_handle dep, nz_handle *out_handle) {
+    NZ_BEGIN(ctx, dep);
+    NZ_TRY(nz_check_stripe(st, 0));
+    NZ_REQUIRE(height, "height is NULL");
+    NZ_REQUIRE(outp, "out is NULL");
+    NZ_REQUIRE(converged, "converged is NULL");
+    const size_t span = nz_stripe_span(*st);
+    NZ_REQUIRE(!nz_planes_overlap(outp, span, height, span), "out overlaps height");
+    NZ_REQUIRE(!nz_bytes_overlap(converged, 4, outp, span * 4), "converged overlaps out");
+    nz_ctx_handle_rides(ctx, out_handle != nullptr);
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_fluvial_implicit_stripe_finalise(ctx->stream, height, outp, converged, nz_geom_from_stripe(*st)));
+    return nz_ctx_finish(ctx, out_handle);
+}
+
 // ---------------------------------------------------------------------------------------------
 // multiple-flow implicit fluvial erosion: the implicit step along every descent (new-framework feature,
 // include/noize_hip.h, nz_fluvial_implicit_mfd.hip)

@@ -10,6 +10,10 @@
 //          host_demo <resolution> <out.f32> drainage-stripe   (a filled simplex tile as ONE row stripe through
 //                            DrainageAreaStage::ScheduleStripe with `first` and FinaliseStripe with a word of 1: heights,
 //                            drainage back to back; the round's `changed` word on stdout)
+//          host_demo <resolution> <out.f32> fluvial-implicit-stripe   (a filled simplex tile as ONE row stripe: its drainage
+//                            through DrainageAreaStage's round and finalise, then ImplicitFluvialStripe::ScheduleStripe with
+//                            `first`, a second, quiet round and FinaliseStripe with a word of 1: heights, result back to
+//                            back; the second round's `changed` word on stdout)
 //          host_demo <resolution> <out.f32> live <particles> <cycles>   (cellular fBm -> LiveErosion, seeds 3, 14, 25, ...:
 //                                                                         height, pool, flow planes back to back)
 //          host_demo <resolution> <out.f32> sharded <stripes> [mode overlap]   (ShardedPipeline on ONE rank: the grid as
@@ -51,6 +55,7 @@ int main(int argc, char **argv) {
     const bool context = argc > 3 && std::strcmp(argv[3], "context") == 0;
     const bool fill = argc > 3 && std::strcmp(argv[3], "fill") == 0;
     const bool drainage_stripe = argc > 3 && std::strcmp(argv[3], "drainage-stripe") == 0;
+    const bool fluvial_implicit_stripe = argc > 3 && std::strcmp(argv[3], "fluvial-implicit-stripe") == 0;
     const int batch = argc > 4 && std::strcmp(argv[3], "batch") == 0 ? std::atoi(argv[4]) : 0;
     // `rw`: the tile is a READ / WRITE plane pair and the stencil stages swap it instead of flushing (nz_*_rw)
     const bool live = argc > 5 && std::strcmp(argv[3], "live") == 0;
@@ -272,6 +277,47 @@ int main(int argc, char **argv) {
             area.CopyTo(host.data() + n);
             words.CopyTo(got.data());
             std::printf("%d\n", reinterpret_cast<const int32_t *>(got.data())[0]);
+            FILE *f = std::fopen(argv[2], "wb");
+            if (!f || std::fwrite(host.data(), sizeof(float), host.size(), f) != host.size()) throw std::runtime_error("write failed");
+            std::fclose(f);
+            pipe.Destroy();
+        } else if (fluvial_implicit_stripe) {
+            const size_t n = (size_t)res * res;
+            DeviceTile tile(ctx, n), area(ctx, n), result(ctx, n), words(ctx, 4);
+            NoiseStage noise(ctx);
+            noise.noiseType = FractalNoise::Simplex;
+            noise.hurst = 0.4f;
+            noise.octaves = 6;
+            noise.noiseSize = 300;
+            DepressionFillStage lakes(ctx);
+            BasePipeline pipe({&noise, &lakes});
+            GeneratorData gd;
+            gd.uuid = "host-demo-fluvial-implicit-stripe";
+            gd.data = &tile;
+            gd.resolution = res;
+            gd.xpos = 37;
+            gd.zpos = 11;
+            pipe.Enqueue(&gd);
+            pipe.RunToCompletion();
+            const nz_stripe st{res, res, 0, res, 0, res, 0};  // the whole grid as one stripe: no cut, no ghost row
+            DeviceTile drainWork(ctx, nz_drainage_stripe_work_floats(&st)), work(ctx, nz_implicit_fluvial_stripe_work_floats(&st));
+            const int32_t start[4] = {-7, -7, 1, -7};  // changed of the two rounds, the verdict, the drainage round's changed
+            words.CopyFrom(reinterpret_cast<const float *>(start));
+            int32_t *w = reinterpret_cast<int32_t *>(words.ptr);
+            const int passes = 64 + res / 4;
+            DrainageAreaStage rivers(ctx);
+            JobHandle h = rivers.ScheduleStripe(tile.ptr, area.ptr, drainWork.ptr, nullptr, st, passes, true, nullptr, w + 3, JobHandle());
+            h = rivers.FinaliseStripe(area.ptr, nullptr, st, w + 2, h);
+            ImplicitFluvialStripe solve(ctx);
+            solve.dt = 100.f;
+            h = solve.ScheduleStripe(tile.ptr, area.ptr, result.ptr, work.ptr, st, passes, true, nullptr, w, h);
+            h = solve.ScheduleStripe(tile.ptr, area.ptr, result.ptr, work.ptr, st, passes, false, w, w + 1, h);
+            solve.FinaliseStripe(tile.ptr, result.ptr, st, w + 2, h).Complete();
+            std::vector<float> host(2 * n), got(4);
+            tile.CopyTo(host.data());
+            result.CopyTo(host.data() + n);
+            words.CopyTo(got.data());
+            std::printf("%d\n", reinterpret_cast<const int32_t *>(got.data())[1]);
             FILE *f = std::fopen(argv[2], "wb");
             if (!f || std::fwrite(host.data(), sizeof(float), host.size(), f) != host.size()) throw std::runtime_error("write failed");
             std::fclose(f);

@@ -1405,6 +1405,44 @@ class HillslopeDiffusionStage : public PipelineStage {
     std::unique_ptr<DeviceTile> work;  // nz_hillslope_diffusion_work_floats floats
 };
 
+class ImplicitFluvialStripe {
+    // The implicit stream-power solve on one row stripe of a larger grid (nz_implicit_fluvial_stripe_round / _finalise): the
+    // round and the finalise that DrainageAreaStage has for the drainage area, for the solve behind it.  No pipeline stage -- a
+    // stripe has no payload -- so no base class: the planes and words are the caller's, and so are the exchanges and the votes.
+    // Per step on every rank: DrainageAreaStage's rounds on the current heights; then rounds of ScheduleStripe -- 1 row of
+    // heightRows exchanged before the round with `first`, 1 row of outRows before every later one, a vote after each
+    // (nz_comm_allreduce_max_i32 on `changed`, which the next round takes as its `proceed`; NULL in the first) -- and
+    // FinaliseStripe with the verdict "the last vote was 0"; then the two height planes swap.
+  public:
+    explicit ImplicitFluvialStripe(nz_ctx *c) : ctx(c) {}
+    float erodibility = 0.05f, uplift = 0.002f, dt = 1.f, seaLevel = -3.402823466e+38f;
+    const float *hardnessRows = nullptr, *upliftMapRows = nullptr;  // stripe-shaped planes, owned rows filled; NULL: off
+    // one round: at most `passes` passes over the owned rows against one frozen ghost row of h' on each side (stripeWork:
+    // nz_implicit_fluvial_stripe_work_floats, the same buffer in every round of a solve)
+    JobHandle ScheduleStripe(const float *heightRows, const float *drainageRows, float *outRows, float *stripeWork,
+                             const nz_stripe &st, int passes, bool first, const int32_t *proceed, int32_t *changed,
+                             JobHandle dependency) {
+        const nz_fluvial_implicit_desc desc{erodibility, uplift, dt, seaLevel, passes, hardnessRows, upliftMapRows, nullptr, nullptr};
+        nz_handle h = 0;
+        check(nz_implicit_fluvial_stripe_round(ctx, heightRows, drainageRows, outRows, stripeWork, &st, &desc, first, proceed,
+                                               changed, dependency.id, &h),
+              "nz_implicit_fluvial_stripe_round");
+        return JobHandle{ctx, h};
+    }
+    // ... and the end of the rounds: all or nothing on the owned rows by the device word `converged` -- outRows stays, or
+    // takes heightRows bit for bit
+    JobHandle FinaliseStripe(const float *heightRows, float *outRows, const nz_stripe &st, const int32_t *converged,
+                             JobHandle dependency) {
+        nz_handle h = 0;
+        check(nz_implicit_fluvial_stripe_finalise(ctx, heightRows, outRows, &st, converged, dependency.id, &h),
+              "nz_implicit_fluvial_stripe_finalise");
+        return JobHandle{ctx, h};
+    }
+
+  private:
+    nz_ctx *ctx;
+};
+
 class MeshTileStage : public PipelineStage {
   public:
     using PipelineStage::PipelineStage;

@@ -530,6 +530,71 @@ def run_drainage_lockstep(ops_list, plans, params, bufs_list, copy_rows):
                                copy_rows)
 
 
+# ---- implicit fluvial erosion on row stripes (nz_implicit_fluvial_stripe_round) -------------------------------------------
+FLUVIAL_IMPLICIT_SCALARS = ("erodibility", "uplift", "dt", "seaLevel")
+FLUVIAL_IMPLICIT_DEFAULTS = dict(iterations=1, erodibility=0.05, uplift=0.002, dt=1.0, rain=1.0,
+                                 seaLevel=-3.4028234663852886e38, maxPasses=64, maxRounds=64)
+FLUVIAL_IMPLICIT_MAPS = ("hardness", "upliftMap")
+
+
+def fluvial_implicit_steps(ops, plan, params, bufs):
+    """Implicit fluvial erosion on one rank's stripe as a generator like drainage_steps.  Per iteration:
+      the drainage area of the current heights (yield from drainage_steps: rain, seaLevel, maxPasses and maxRounds are
+      shared with it); when it does not converge the step is not applied and the loop ends;
+      rounds of ops.fluvial_implicit (at most maxPasses passes over the owned rows against one frozen ghost row of h' on
+      each side), with an exchange request (planes, 1, 1) before each -- the height plane before round 0, the `out` plane
+      before every later round -- and a vote request (VOTE, word) after each; round r > 0 is handed the vote of round
+      r - 1 as its `proceed` word; the rounds stop when the vote is 0 or after maxRounds;
+      ops.fluvial_implicit_finalise with the verdict vote == 0 on every rank (all or nothing), and the height and `out`
+      planes swap; a solve that did not converge ends the loop.
+    bufs: "H" (the heights on the owned rows), "out", "A", "work" (nz_implicit_fluvial_stripe_work_floats), "drainageWork"
+    (nz_drainage_stripe_work_floats), "words" (int32[3]) and optionally "rainMap", "hardness", "upliftMap" (owned rows
+    filled); plan.halo >= 2.  Returns (height plane, A plane, steps applied, rounds of the last solve, converged)."""
+    prm = _stage_params(FLUVIAL_IMPLICIT_DEFAULTS, "a parameter of the sharded implicit fluvial erosion", params)
+    assert plan.halo >= 2, "the drainage area needs 2 ghost rows of the heights"
+    words = bufs["words"]
+    maps = {k: bufs[k] for k in FLUVIAL_IMPLICIT_MAPS if bufs.get(k) is not None}
+    drain_prm = {k: prm[k] for k in DRAINAGE_DEFAULTS}
+    h, out = bufs["H"], bufs["out"]
+    steps, rounds, converged = 0, 0, True
+    for _ in range(prm["iterations"]):
+        dbufs = dict(H=h, A=bufs["A"], work=bufs["drainageWork"], words=words)
+        if bufs.get("rainMap") is not None:
+            dbufs["rainMap"] = bufs["rainMap"]
+        _, _, converged = yield from drainage_steps(ops, plan, drain_prm, dbufs)
+        if not converged:
+            break
+        vote, rounds = 1, 0
+        while vote != 0 and rounds < prm["maxRounds"]:
+            yield [h if rounds == 0 else out], 1, 1
+            word = words[rounds & 1:(rounds & 1) + 1]
+            ops.fluvial_implicit(h, bufs["A"], out, bufs["work"], plan, prm, rounds == 0,
+                                 None if rounds == 0 else words[(rounds - 1) & 1:((rounds - 1) & 1) + 1], word, **maps)
+            vote = yield VOTE, word
+            rounds += 1
+        converged = vote == 0
+        words[2:3].fill_(1 if converged else 0)
+        ops.fluvial_implicit_finalise(h, out, plan, words[2:3])
+        h, out = out, h
+        if not converged:
+            break
+        steps += 1
+    return h, bufs["A"], steps, rounds, converged
+
+
+def run_fluvial_implicit(ops, comm, plan, params, bufs):
+    """fluvial_implicit_steps on this rank: exchanges through comm.exchange, votes through comm.allreduce_max (TorchComm,
+    NativeComm, NoComm); returns (height plane, A plane, steps applied, rounds of the last solve, converged)."""
+    return _run_steps(fluvial_implicit_steps(ops, plan, params, bufs), comm, plan)
+
+
+def run_fluvial_implicit_lockstep(ops_list, plans, params, bufs_list, copy_rows):
+    """All ranks inside one process, as run_drainage_lockstep; returns every rank's (height plane, A plane, steps applied,
+    rounds of the last solve, converged)."""
+    return _run_steps_lockstep([fluvial_implicit_steps(o, pl, params, b) for o, pl, b in zip(ops_list, plans, bufs_list)],
+                               plans, copy_rows)
+
+
 class HipStripeOps:
     """Stripe operations on device memory through the C ABI.  Buffers are objects with `.data_ptr()`
     (torch CUDA tensors used as plain HBM allocations); state buffers are indexable by plane."""
@@ -625,6 +690,21 @@ class HipStripeOps:
         desc = self._drainage_desc(prm, rainMap)
         self._call("nz_drainage_stripe_finalise", a.data_ptr(), C.byref(st), C.byref(desc), converged.data_ptr())
 
+    def fluvial_implicit(self, h, a, out, work, plan, prm, first, proceed, changed, hardness=None, upliftMap=None, pitch=0):
+        """nz_implicit_fluvial_stripe_round: one round, at most prm["maxPasses"] passes.  proceed: an int32 device word or
+        None; changed: one."""
+        st = plan.stripe(pitch)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        desc = N.FluvialImplicitDesc(*[prm[k] for k in FLUVIAL_IMPLICIT_SCALARS], prm["maxPasses"], ptr(hardness),
+                                     ptr(upliftMap), None, None)
+        self._call("nz_implicit_fluvial_stripe_round", h.data_ptr(), a.data_ptr(), out.data_ptr(), work.data_ptr(),
+                   C.byref(st), C.byref(desc), int(first), ptr(proceed), changed.data_ptr())
+
+    def fluvial_implicit_finalise(self, h, out, plan, converged, pitch=0):
+        """nz_implicit_fluvial_stripe_finalise on the owned rows, by the int32 device word `converged`."""
+        st = plan.stripe(pitch)
+        self._call("nz_implicit_fluvial_stripe_finalise", h.data_ptr(), out.data_ptr(), C.byref(st), converged.data_ptr())
+
     def upsample_halo_rows(self, filter):
         return self.lib.nz_upsample_stripe_halo_rows(int(filter))
 
@@ -646,6 +726,27 @@ class HipStripeOps:
         """NormalizeMap on the stripe's owned rows with args = device {min, max, range}."""
         owned = buf.data_ptr() + plan.own0 * plan.cols * 4
         self._call("nz_normalize_cells_dev", owned, plan.nown * plan.cols, args.data_ptr())
+
+
+class ImplicitFluvialStripe:
+    """The compiled hosts' ImplicitFluvialStripe (noize_pipeline.hpp, Stages.cs) under the same name: the scalars and the
+    two optional stripe-shaped map planes of the implicit solve, and one round / the finalise of its stripe form on the
+    caller's planes and device words -- a thin wrapper over HipStripeOps.fluvial_implicit(_finalise).  The exchanges and the
+    votes between the rounds are the caller's: fluvial_implicit_steps is the schedule."""
+
+    def __init__(self, ctx, erodibility=0.05, uplift=0.002, dt=1.0, seaLevel=-3.4028234663852886e38, hardnessRows=None,
+                 upliftMapRows=None):
+        self.ops = HipStripeOps(ctx)
+        self.erodibility, self.uplift, self.dt, self.seaLevel = erodibility, uplift, dt, seaLevel
+        self.hardnessRows, self.upliftMapRows = hardnessRows, upliftMapRows
+
+    def ScheduleStripe(self, heightRows, drainageRows, outRows, stripeWork, plan, passes, first, proceed, changed, pitch=0):
+        prm = dict(erodibility=self.erodibility, uplift=self.uplift, dt=self.dt, seaLevel=self.seaLevel, maxPasses=passes)
+        self.ops.fluvial_implicit(heightRows, drainageRows, outRows, stripeWork, plan, prm, first, proceed, changed,
+                                  hardness=self.hardnessRows, upliftMap=self.upliftMapRows, pitch=pitch)
+
+    def FinaliseStripe(self, heightRows, outRows, plan, converged, pitch=0):
+        self.ops.fluvial_implicit_finalise(heightRows, outRows, plan, converged, pitch=pitch)
 
 
 def map_range_work_floats(world):
