@@ -1,7 +1,8 @@
-"""The cases and the models of tests/test_gpu_sweep_relax.py: the five newer terrain stages -- watershed, stream order, the
-implicit fluvial step, hillslope diffusion, multiple-flow drainage -- on the adversarial tiles of tests/terrain_tiles.py and on
-one tile more, `faint`, whose heights are themselves subnormal.  Plain numpy and the case helpers of the existing sweep
-(tests/test_gpu_sweep_terrain.py): nothing here opens a GPU, and tests/test_relax_sweep_cases.py runs without one.
+"""The cases and the models of tests/test_gpu_sweep_relax.py: six newer terrain stages -- watershed, stream order, the
+implicit fluvial step, hillslope diffusion, multiple-flow drainage, the multiple-flow implicit fluvial step -- on the
+adversarial tiles of tests/terrain_tiles.py and on one tile more, `faint`, whose heights are themselves subnormal.  Plain
+numpy and the case helpers of the existing sweep (tests/test_gpu_sweep_terrain.py): nothing here opens a GPU, and
+tests/test_relax_sweep_cases.py runs without one.
 
 A case is a dict (family, form, hh = count x res x res heights, parameters).  model(case) gives the planes of
 PLANES[family], each count x res x res, and the bound on passes the stage's own GPU test uses (None for the hillslope stage,
@@ -12,18 +13,23 @@ which is no relaxation):
     fluvial_implicit  fluvial_implicit_ref.walk                      hops.max() + 2 (the watershed's dependency graph)
     hillslope         hillslope_ref.diffuse                          --
     drainage_mfd      drainage_mfd_ref.walk                          DAG height + 1
+    fluvial_implicit_mfd  fluvial_implicit_mfd_ref.walk              DAG height + 1 (the budget: one pass more)
 
 Forms are "tile" and "batch", for the hillslope stage also "inplace".  The drainage plane of a stream-order case
-(drainage=True) and of every implicit-fluvial case is drainage_ref.accumulate of the same heights and sea under unit rain; a
+(drainage=True) and of every implicit-fluvial case is drainage_ref.accumulate of the same heights and sea under unit rain;
+that of a multiple-flow implicit case is drainage_mfd_ref.walk of the same heights, sea, rain, rain map and exponent -- the
+rain map is positive or none: a signed one gives negative areas, whose square root is no number.  A
 plane handed in as an array (the chain of the GPU test, kernel feeding kernel) is used as it is.  keys: one hashable per
 tile under which its model is shared between cases; with a plane handed in the key has to name that plane too.
 
-The seeded sweep, relax_sweep_cases(seed), is pinned by tests/test_relax_sweep_cases.py; a case of it is replayed alone with
-check(nj, ctx, relax_sweep_cases(seed)[i]) of the GPU test."""
+The seeded sweep, relax_sweep_cases(seed), draws from SWEEP_FAMILIES, the five older families, and is pinned by
+tests/test_relax_sweep_cases.py; the multiple-flow implicit step has a stream of its own, mfd_sweep_cases(seed), pinned there
+too.  A case of either is replayed alone with check(nj, ctx, relax_sweep_cases(seed)[i]) of the GPU test."""
 import numpy as np
 
 import drainage_mfd_ref as M
 import drainage_ref as D
+import fluvial_implicit_mfd_ref as R2
 import fluvial_implicit_ref as R
 import fluvial_ref as F
 import hillslope_ref as HS
@@ -35,16 +41,20 @@ from test_gpu_sweep_terrain import SWEEP_SIZES, drainage_rain_map
 
 f32 = np.float32
 OFF = float(F.SEA_OFF)
-FAMILIES = ("watershed", "stream_order", "fluvial_implicit", "hillslope", "drainage_mfd")
-RELAXATIONS = ("watershed", "stream_order", "fluvial_implicit", "drainage_mfd")  # the four with a pass count and a sweep cap
+# the five relax_sweep_cases draws from: its pinned digests hang on this tuple.  The sixth has a stream of its own
+SWEEP_FAMILIES = ("watershed", "stream_order", "fluvial_implicit", "hillslope", "drainage_mfd")
+FAMILIES = SWEEP_FAMILIES + ("fluvial_implicit_mfd",)
+# the five with a pass count and a sweep cap
+RELAXATIONS = ("watershed", "stream_order", "fluvial_implicit", "drainage_mfd", "fluvial_implicit_mfd")
 PLANES = {"watershed": ("basin", "length", "receivers"), "stream_order": ("order", "link"), "fluvial_implicit": ("out",),
-          "hillslope": ("out",), "drainage_mfd": ("out",)}
+          "hillslope": ("out",), "drainage_mfd": ("out",), "fluvial_implicit_mfd": ("out",)}
 # what a case of each family carries, in the order describe() prints it
 PARAMETERS = {"watershed": ("sea", "cellSize", "length", "receivers"),
               "stream_order": ("sea", "drained", "threshold", "links"),
               "fluvial_implicit": ("erodibility", "uplift", "dt", "sea", "maps", "seed"),
               "hillslope": ("diffusivity", "dt", "iterations"),
-              "drainage_mfd": ("rain", "sea", "exponent", "rainmap", "seed")}
+              "drainage_mfd": ("rain", "sea", "exponent", "rainmap", "seed"),
+              "fluvial_implicit_mfd": ("erodibility", "uplift", "dt", "sea", "exponent", "rain", "maps", "rainmap", "seed")}
 _OUTPUT_ONLY = ("length", "receivers", "links")  # which planes are asked for: the model does not depend on it
 EXPONENTS = (1, 2, 3, 4, 16)
 RS = (0.01, 1.0, 100.0, 1e4)
@@ -92,8 +102,10 @@ def case(family, hh, form="tile", keys=None, seed=11, budget=None, sea=OFF, cell
     assert family in FAMILIES and form in ("tile", "batch", "inplace") and (form == "batch" or len(hh) == 1)
     assert form != "inplace" or family == "hillslope"
     assert rainmap in (None, "positive", "signed") and (keys is None or len(keys) == len(hh))
+    mfd = family == "fluvial_implicit_mfd"
+    assert not mfd or rainmap in (None, "positive")  # a signed map gives negative A: sqrt(A) leaves the finite numbers
     given = isinstance(drainage, np.ndarray)
-    drained = True if family == "fluvial_implicit" else given or bool(drainage)
+    drained = True if family in ("fluvial_implicit", "fluvial_implicit_mfd") else given or bool(drainage)
     c = dict(family=family, hh=hh, form=form, keys=keys, seed=seed, budget=budget, sea=sea, cellSize=cellSize, length=length,
              receivers=receivers, drained=drained, given=given, threshold=threshold, links=links, erodibility=erodibility,
              uplift=uplift, dt=dt, maps=bool(maps), diffusivity=diffusivity, iterations=iterations, rain=rain,
@@ -105,11 +117,22 @@ def case(family, hh, form="tile", keys=None, seed=11, budget=None, sea=OFF, cell
             area = lambda k: D.accumulate(hh[k], 1.0, sea)[0]  # noqa: E731
             c["drainage"] = np.stack([area(k) if keys is None else memo(("relax area", keys[k], hh.shape[-1], sea), lambda: area(k))
                                       for k in range(len(hh))])
-    if family == "fluvial_implicit" and maps:
+    if family in ("fluvial_implicit", "fluvial_implicit_mfd") and maps:
         c["hardness"], c["upliftMap"] = memo(("relax implicit maps", hh.shape, seed), lambda: implicit_maps(hh.shape, seed))
-    if family == "drainage_mfd" and rainmap:
+    if family in ("drainage_mfd", "fluvial_implicit_mfd") and rainmap:
         c["rainMap"] = memo(("terrain rain map", hh.shape, seed, rainmap == "signed"),
                             lambda: drainage_rain_map(hh.shape, seed, rainmap == "signed"))
+    if mfd:  # the multiple-flow drainage of the same heights, sea, rain and exponent
+        if given:
+            c["drainage"] = np.ascontiguousarray(drainage, f32).reshape(hh.shape)
+        else:
+            rm = c["rainMap"]
+            area = lambda k: M.walk(hh[k], rain, sea, rm[k] if rm is not None else None, exponent)[0]  # noqa: E731
+            # (the rain map of tile k depends on the shape of the whole case)
+            where = lambda k: (hh.shape, k, seed) if rm is not None else hh.shape[-1]  # noqa: E731
+            c["drainage"] = np.stack([area(k) if keys is None else
+                                      memo(("relax mfd area", keys[k], where(k), rain, sea, exponent), lambda: area(k))
+                                      for k in range(len(hh))])
     return c
 
 
@@ -137,6 +160,10 @@ def _model_tile(c, k):
         out = R.walk(h, c["drainage"][k], erodibility=c["erodibility"], uplift=c["uplift"], dt=c["dt"], seaLevel=sea,
                      hardness=at(c["hardness"]), upliftMap=at(c["upliftMap"]))
         return (out,), int(hops(h, sea).max()) + 2
+    if fam == "fluvial_implicit_mfd":
+        out, height = R2.walk(h, c["drainage"][k], erodibility=c["erodibility"], uplift=c["uplift"], dt=c["dt"], seaLevel=sea,
+                              exponent=c["exponent"], hardness=at(c["hardness"]), upliftMap=at(c["upliftMap"]))
+        return (out,), height + 1
     if fam == "hillslope":
         return (HS.diffuse(h, c["diffusivity"], c["dt"], c["iterations"]),), None
     A, height = M.walk(h, c["rain"], sea, at(c["rainMap"]), c["exponent"])
@@ -174,7 +201,9 @@ def odd_cases(res):
                     ("fluvial_implicit", dict(maps=True, sea=sea, dt=200.0)),
                     ("hillslope", dict(diffusivity=100.0, dt=1.0, iterations=3)),
                     ("drainage_mfd", dict(rain=0.75, exponent=1, rainmap="positive")),
-                    ("drainage_mfd", dict(rain=0.75, exponent=16, rainmap="positive"))):
+                    ("drainage_mfd", dict(rain=0.75, exponent=16, rainmap="positive")),
+                    ("fluvial_implicit_mfd", dict(maps=True, sea=sea, dt=200.0, exponent=1, rain=0.75, rainmap="positive")),
+                    ("fluvial_implicit_mfd", dict(maps=True, sea=sea, dt=200.0, exponent=16, rain=0.75, rainmap="positive"))):
         for k in (0, 1):
             for form in ("tile", "inplace") if fam == "hillslope" else ("tile",):
                 out.append(case(fam, batch[k], form, keys[k:k + 1], **kw))
@@ -203,6 +232,7 @@ def tie_cases(name, res):
         for e in (1, 3, 16):
             out.append(case("drainage_mfd", h, keys=keys, sea=s, exponent=e, rain=1.0 if s == OFF else 0.75,
                             rainmap=None if s == OFF else "positive"))
+            out.append(case("fluvial_implicit_mfd", h, keys=keys, sea=s, exponent=e, dt=200.0, maps=s != OFF))
     out.append(case("hillslope", h, keys=keys, diffusivity=0.01))
     out.append(case("hillslope", h, "inplace", keys, diffusivity=1e4, iterations=3))
     # once per tile the batch of three, every family; the stream-order stage runs singly on these tiles in its own file
@@ -212,6 +242,7 @@ def tie_cases(name, res):
     out.append(case("fluvial_implicit", hhh, "batch", keys3, sea=sea, dt=50.0))
     out.append(case("hillslope", hhh, "batch", keys3, diffusivity=1e4))
     out.append(case("drainage_mfd", hhh, "batch", keys3, sea=sea, exponent=3, rain=0.3, rainmap="signed"))
+    out.append(case("fluvial_implicit_mfd", hhh, "batch", keys3, sea=sea, exponent=3, dt=50.0))
     return out
 
 
@@ -237,13 +268,20 @@ def scale_cases(name, res):
     for e in (4, 16):
         out.append(case("drainage_mfd", h, keys=keys, exponent=e, rain=0.3, rainmap="signed"))
     out.append(case("drainage_mfd", hhh, "batch", keys3, sea=sea, exponent=16, rain=0.3, rainmap="signed"))
+    out += [case("fluvial_implicit_mfd", h, keys=keys, exponent=4, dt=50.0, maps=True),
+            case("fluvial_implicit_mfd", h, keys=keys, exponent=16, dt=200.0),
+            case("fluvial_implicit_mfd", hhh, "batch", keys3, sea=sea, exponent=16, dt=200.0),
+            case("fluvial_implicit_mfd", h, keys=keys, uplift=0.0, dt=1.0),
+            case("fluvial_implicit_mfd", h, keys=keys, uplift=0.0, dt=200.0),
+            identity_case(h, keys, "fluvial_implicit_mfd")]
     return out
 
 
-def identity_case(h, keys=None):
+def identity_case(h, keys=None, family="fluvial_implicit"):
     """erodibility 0 and uplift 0: f = +0 and du = +0 everywhere, so out = (h + 0) / 1 -- the heights bit for bit, but that a
-    -0 with a receiver comes back as +0."""
-    return case("fluvial_implicit", h, keys=keys, erodibility=0.0, uplift=0.0, dt=200.0)
+    -0 with a receiver comes back as +0.  In the multiple-flow step every f_k is +0 too: N = (h + 0) plus zeros, D = 1, and
+    where no gate is open out = b = h + 0 -- the heights again, but that every -0 that is no outlet comes back as +0."""
+    return case(family, h, keys=keys, erodibility=0.0, uplift=0.0, dt=200.0)
 
 
 # ---- f. the seeded sweep -------------------------------------------------------------------------------------------------------
@@ -263,7 +301,7 @@ def relax_sweep_cases(seed, n=5):
     for _ in range(n):
         res = int(rng.choice(SWEEP_SIZES))
         name = pick(names)
-        family = pick(FAMILIES)
+        family = pick(SWEEP_FAMILIES)
         form = pick(("tile", "batch"))
         count = int(rng.integers(2, 5))
         in_place = coin()
@@ -281,6 +319,39 @@ def relax_sweep_cases(seed, n=5):
         if family == "hillslope":
             prm["dt"] = 1.0  # r is the one product: the list RS holds it
         c = case(family, hh, form, **prm)
+        c["name"] = name
+        out.append(c)
+    return out
+
+
+# 13000 + seed reaches both forms, `faint`, exponent 16 and a rain map in seeds 0 to 7, but its exponent-16 cases and its
+# faint ones all have erodibility 0 and one of its tiles is 194^2; this is the first offset from there on at which a faint
+# tile and an exponent-16 case that is neither flat nor the checkerboard erode, at sizes up to 131
+MFD_SWEEP_OFFSET = 13028
+
+
+def mfd_sweep_cases(seed, n=3):
+    """The multiple-flow implicit step's sweep, a stream of its own so that relax_sweep_cases stays as it is pinned: size,
+    tile, form, count, heights, sea, erodibility, uplift, dt, maps, exponent, rain, rain map (positive or none) and seed,
+    every case the same draws in the same order."""
+    rng = np.random.default_rng(MFD_SWEEP_OFFSET + seed)
+    names = sorted(TILES)
+    pick = lambda values: values[int(rng.integers(len(values)))]  # noqa: E731
+    coin = lambda: bool(rng.random() < 0.5)  # noqa: E731
+    out = []
+    for _ in range(n):
+        res = int(rng.choice(SWEEP_SIZES))
+        name = pick(names)
+        form = pick(("tile", "batch"))
+        count = int(rng.integers(2, 5))
+        if form == "tile":
+            count = 1
+        hh = np.stack([TILES[name](res, rng) for _ in range(count)])
+        sea = T.sea_at(hh[0], 0.3) if coin() else OFF
+        prm = dict(sea=sea, erodibility=pick(ERODIBILITIES), uplift=pick(UPLIFTS), dt=pick(DTS), maps=coin(),
+                   exponent=pick(EXPONENTS), rain=pick((0.3, 0.75, 1.0)), rainmap="positive" if coin() else None,
+                   seed=int(rng.integers(1 << 30)))
+        c = case("fluvial_implicit_mfd", hh, form, **prm)
         c["name"] = name
         out.append(c)
     return out

@@ -1,5 +1,6 @@
 """The stripe sweep shared by tests/test_sweep_stripes_ref.py (CPU, the numpy stripe ops) and tests/test_gpu_sweep_stripes.py
-(nz_hydraulic_stripe, nz_fluvial_stripe, nz_fill_stripe(_finalise), nz_drainage_stripe_round(_finalise)): a square adversarial
+(nz_hydraulic_stripe, nz_fluvial_stripe, nz_fill_stripe(_finalise), nz_drainage_stripe_round(_finalise),
+nz_implicit_fluvial_stripe_round(_finalise)): a square adversarial
 tile of tests/terrain_tiles.py cut into row stripes and driven by the run_*_lockstep functions of noize_job_amd.sharded has to
 equal the whole tile's model bit for bit, in every plane the family returns.
 
@@ -18,16 +19,29 @@ equal the whole tile's model bit for bit, in every plane the family returns.
               fill        epsilon 0, 1e-4, 0.25 with and without a sea level that is a cell value, depth recorded
               drainage    the tile as it is (pits and flats) and flooded with 1e-4; unit rain, a sea with fractional
                           rain on a positive map, the same on a map of both signs; the maps cut into stripes
+              fluvial_implicit  the tile as it is (pits, plateaus, flats that span the cuts) through
+                          run_fluvial_implicit_lockstep, drainage rounds and solve rounds on the same stripes: the stage's
+                          defaults at dt 200 in 1 iteration; a sea level that is a cell value with the hardness and uplift
+                          maps of fluvial_implicit_stripe_cases at dt 50 in 2 iterations, the second on heights the first
+                          solve wrote and finalise swapped.  Heights and the last iteration's drainage area against
+                          fluvial_implicit_ref.chain; in the first set the area is integral and sums to res * res over
+                          the cells without a receiver, with no model asked
 A stripe has to hold the ghost rows its neighbour asks for, 2 * exchange_every <= rows // world in the drivers' tests: the
 thinnest stripes here have 8 rows, so no exchange_every 2 case is dropped (every_for() returns (1, 2) for every split).
 
 The whole-grid models are the tile models through test_gpu_sweep_terrain.model, under the tile sweep's keys: where the
-parameters coincide they are computed once for both sweeps.  Budgets: FILL_BUDGET (test_gpu_fill_stripe.PARAMS) and
-drainage_stripe_cases.PARAMS; the CPU half asserts that every case converges inside them."""
+parameters coincide they are computed once for both sweeps; the implicit family's chain is kept under a key of the same kind.
+Budgets: FILL_BUDGET (test_gpu_fill_stripe.PARAMS), drainage_stripe_cases.PARAMS and, for the implicit family,
+fluvial_implicit_stripe_cases.PARAMS -- 128 passes and 128 rounds, which its driver shares with the drainage rounds; the CPU
+half asserts that every case converges inside them.  The implicit family through the numpy ops, all nine tiles at the three
+splits and the pitched case dense: at most 7 rounds of a solve (tiny, 65^2 over 8, the first set) and 66 Jacobi steps in one
+round (manh_pit, 130^2 over 3), every case well under a second."""
 import numpy as np
 
 import drainage_stripe_cases as DC
 import fill_stripe_cases as LC
+import fluvial_implicit_ref as R
+import fluvial_implicit_stripe_cases as IC
 import fluvial_ref as F
 import fluvial_stripe_cases as FC
 import terrain_tiles as T
@@ -42,6 +56,7 @@ PITCHED = ("terraces16", 67, 3, 72)  # tile, size, world, pitch
 ITS = 6
 FILL_BUDGET = dict(maxPasses=400, maxRounds=400)
 DRAINAGE_BUDGET = DC.PARAMS
+FLUVIAL_IMPLICIT_BUDGET = IC.PARAMS  # shared by the drainage rounds and the solve rounds of an iteration
 HYDRAULIC_SETS = ((0, ()), (1, S.ALL_ON))  # (index into PARAMS, options of the _ex entry)
 FILL_EPS = (0.0, 1e-4, 0.25)
 FLOOD_EPS = 1e-4
@@ -64,19 +79,24 @@ class Backend:
     def work_floats(self, module, pitch):
         return module.work_floats(self.nj, pitch or 0) if self.nj is not None else (lambda plan: 0)
 
+    def drain_floats(self, module, pitch):
+        """The drainage rounds' work plane of a family that runs them before its own."""
+        return module.drain_floats(self.nj, pitch or 0) if self.nj is not None else (lambda plan: 0)
+
 
 def cpu_backend():
     from drainage_stripe_ops import DrainageStripeOps
     from fill_stripe_ops import FillStripeOps
+    from fluvial_implicit_stripe_ops import FluvialImplicitStripeOps
     from fluvial_stripe_ops import FluvialStripeOps
     from hydraulic_stripe_ops import HydraulicStripeOps
     from noize_job_amd import sharded as sh
     return Backend(sh, dict(hydraulic=HydraulicStripeOps(), fluvial=FluvialStripeOps(), fill=FillStripeOps(),
-                            drainage=DrainageStripeOps()))
+                            drainage=DrainageStripeOps(), fluvial_implicit=FluvialImplicitStripeOps()))
 
 
 def gpu_backend(nj, sh, ops):
-    return Backend(sh, dict.fromkeys(("hydraulic", "fluvial", "fill", "drainage"), ops), "cuda", nj)
+    return Backend(sh, dict.fromkeys(("hydraulic", "fluvial", "fill", "drainage", "fluvial_implicit"), ops), "cuda", nj)
 
 
 class Pitched:
@@ -225,5 +245,46 @@ def drainage(be, name, res, world, pitch=None):
     return rounds_of
 
 
-FAMILIES = dict(hydraulic=hydraulic, fluvial=fluvial, fill=fill, drainage=drainage)
+def fluvial_implicit_sets(h):
+    """(scalars, iterations, maps?) of the two parameter sets."""
+    return ((dict(dt=200.0), 1, False), (dict(dt=50.0, seaLevel=T.sea_at(h, 0.3)), 2, True))
+
+
+def fluvial_implicit(be, name, res, world, pitch=None):
+    """The tile as it is -- pits, plateaus and flats that span the cuts -- through run_fluvial_implicit_lockstep: drainage
+    rounds, then solve rounds, per iteration on the same stripes.  -> the rounds of the last solve of every case."""
+    h, pitch = tile(name, res), be.pitch(pitch)
+    sh, ops = be.sh, be.ops["fluvial_implicit"]
+    sized, drain_sized = be.work_floats(IC, pitch), be.drain_floats(IC, pitch)
+    rounds_of = []
+    for k, (scalars, iterations, mapped) in enumerate(fluvial_implicit_sets(h)):
+        maps = dict(hardness=IC.hard_map(h.shape), upliftMap=IC.uplift_map(h.shape)) if mapped else {}
+        what = "fluvial_implicit %s %d^2 over %d, set %d %r x %d maps %r, pitch %s" % (
+            name, res, world, k + 1, scalars, iterations, mapped, pitch)
+        want, want_a = S.memo(("terrain", "fluvial_implicit chain", name, res, iterations, tuple(sorted(scalars.items())), mapped),
+                              lambda: R.chain(h, iterations, **scalars, **maps))
+        params = dict(FLUVIAL_IMPLICIT_BUDGET, iterations=iterations, **scalars)
+        if pitch is None:
+            got, A, steps, rounds, converged, _, _ = IC.lockstep(sh, ops, world, h, params, sized, drain_sized, be.device, **maps)
+        else:
+            plans = [sh.StripePlan(r, world, res, res, IC.HALO) for r in range(world)]
+            bufs = [IC.stripe_bufs(pl, h, sized(pl), drain_sized(pl), be.device, pitch, **maps) for pl in plans]
+            out = sh.run_fluvial_implicit_lockstep([Pitched(ops, pitch)] * world, plans, params, bufs, HC.copy_rows)
+            assert len({r[2:] for r in out}) == 1, "%s: the ranks disagree about steps / rounds / converged" % what
+            got, A = FC.gather(plans, out)
+            steps, rounds, converged = out[0][2:]
+            assert_pads(bufs, res, pitch, what)
+        assert converged and steps == iterations and 1 <= rounds <= FLUVIAL_IMPLICIT_BUDGET["maxRounds"], (
+            what, steps, rounds, converged)
+        assert np.isfinite(want).all() and np.isfinite(want_a).all(), what
+        IC.assert_bits(A, want_a, what + ": the drainage area of the last iteration")
+        IC.assert_bits(got, want, what + ": heights")
+        if k == 0:  # unit rain, one iteration: every cell's rain arrives at exactly one cell without a receiver
+            roots = F.receivers(h)[0] == F.NONE
+            assert (A == np.floor(A)).all() and float(A[roots].astype(np.float64).sum()) == res * res, what
+        rounds_of.append(rounds)
+    return rounds_of
+
+
+FAMILIES = dict(hydraulic=hydraulic, fluvial=fluvial, fill=fill, drainage=drainage, fluvial_implicit=fluvial_implicit)
 CASES = [(name, res, world) for name in TILES for res, world in SPLITS]

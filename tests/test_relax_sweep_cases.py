@@ -1,14 +1,21 @@
 """The cases and models of tests/relax_sweep_cases.py, on the CPU: what tests/test_gpu_sweep_relax.py takes for granted.
 
     the stream      relax_sweep_cases(seed), seeds 0 to 7, is pinned -- describe(c), the tile's name, the bytes of the heights
-                    and of the maps -- and reaches every family, every form, the faint tile, exponent 16 and a signed rain map
+                    and of the maps -- and reaches every one of its five families, every form, the faint tile, exponent 16 and a
+                    signed rain map; mfd_sweep_cases(seed), the multiple-flow implicit step's own stream, is pinned the same way
+                    and reaches both forms, a faint tile and an exponent-16 case that erode, both maps and a rain map, on
+                    drainage planes that are positive everywhere
     the models      walk, jacobi and tiled (the kernels' schedule, at sweep caps 1, 3 and 16) agree bit for bit on every tile of
-                    TILES at 65^2, and every plane is finite
+                    TILES at 65^2, and every plane is finite -- the multiple-flow implicit step with a sea on a cell value, both
+                    maps, exponent 16 and a positive rain map
     the tiles       `faint` is subnormal in a quarter to a half of its cells; the hillslope model keeps the -0 of the held border
                     of `zeros`, leaves none inside and leaves subnormal cells, as it does on `faint`; so does the implicit fluvial
                     model on `faint`; exponent 16 gives subnormal and vanished weights where exponent 3 gives none; on every tie
                     tile receivers are chosen among equal drops, on all but the cones among equal slopes, and there the first in
-                    the order W E S N SW SE NW NE wins; erodibility 0 with uplift 0 returns the heights
+                    the order W E S N SW SE NW NE wins; erodibility 0 with uplift 0 returns the heights, from both implicit
+                    models, bit for bit on every tile but `zeros`; at exponent 16 the multiple-flow implicit model has cells
+                    with a lower neighbour and no open edge -- outlets, all of them: the steepest neighbour's quotient is 1.0
+                    and its gate never shuts -- and cells inside with single gates shut, and both come back as the text says
     the invariants  of the GPU test's chain: the cells that carry a basin label are the unit-rain drainage area of that outlet
 
 The figures (printed with -s), seed 3, at 66^2 / 97^2 (65^2 for the ties and basins):
@@ -18,6 +25,8 @@ The figures (printed with -s), seed 3, at 66^2 / 97^2 (65^2 for the ties and bas
     implicit        faint, uplift 0: 1948 / 2334 subnormal cells at dt 1, 3269 / 5825 at dt 200
     exponent 16     uniform 31 / 96 subnormal and 21 / 49 vanished weights, metres 47 / 77 and 18 / 53; none on terraces16, none
                     at exponent 3
+    exponent 16,    uniform 219 / 324 cells with a drop > 0 and no open edge, metres 249 / 375, every one an outlet of the
+    implicit        border, none inside; uniform 21 / 49 cells inside with a gate shut on a drop > 0, metres 18 / 53
     tied receivers  among equal slopes, sea off: terraces4 220, terraces16 604, cheb_pit 125, manh_pit 125, checker 1984, the
                     cones 0 (among equal drops 3840 and 3844)
     basins          terraces4 3436, checker 2241: nearly every cell a flat without a receiver"""
@@ -28,6 +37,7 @@ import pytest
 
 import drainage_mfd_ref as M
 import drainage_ref as D
+import fluvial_implicit_mfd_ref as R2
 import fluvial_implicit_ref as R
 import fluvial_ref as F
 import hillslope_ref as HS
@@ -40,6 +50,10 @@ f32 = np.float32
 OFF = C.OFF
 SWEEP_DIGESTS = {0: "c30593638ecd412f", 1: "27158f9a7d8292bc", 2: "b073a7dcb36d7682", 3: "331d255d50068171",
                  4: "28a3929e70d833be", 5: "b4ffdb1bb452dfc0", 6: "d311f4fa5942a708", 7: "43eea763de7ff492"}
+
+
+MFD_SWEEP_DIGESTS = {0: "23e49ed551127135", 1: "c9d459cfd1ab3975", 2: "e7741748861c55de", 3: "55bd92938868d3ca",
+                     4: "cb674fb710fd852e", 5: "3929ccfafecdf62a", 6: "61ee8738a17a4ce9", 7: "c182a9731f2dbcc8"}
 
 
 def make(name, res):
@@ -67,12 +81,37 @@ def test_the_seeded_sweep_is_pinned(seed):
     assert digest(cases) == SWEEP_DIGESTS[seed], [C.describe(c) for c in cases]
 
 
+@pytest.mark.parametrize("seed", range(8))
+def test_the_seeded_multiple_flow_sweep_is_pinned(seed):
+    cases = C.mfd_sweep_cases(seed)
+    print("%d: %r" % (seed, digest(cases)))
+    assert len(cases) == 3 and all(c["hh"].shape[-1] in C.SWEEP_SIZES for c in cases)
+    assert digest(cases) == MFD_SWEEP_DIGESTS[seed], [C.describe(c) for c in cases]
+
+
+def test_the_seeded_multiple_flow_sweep_reaches_every_form_and_edge():
+    cases = [c for seed in range(8) for c in C.mfd_sweep_cases(seed)]
+    assert len(cases) == 24 and len({C.describe(c) + c["name"] for c in cases}) == 24
+    assert {c["family"] for c in cases} == {"fluvial_implicit_mfd"}
+    assert {c["form"] for c in cases} == {"tile", "batch"}
+    assert any(c["name"] == "faint" for c in cases) and any(c["exponent"] == 16 for c in cases)
+    assert any(c["name"] == "faint" and c["erodibility"] > 0 for c in cases)
+    assert any(c["exponent"] == 16 and c["erodibility"] > 0 and c["name"] not in ("zeros", "checker") for c in cases)
+    assert max(c["hh"].shape[-1] for c in cases) <= 131
+    assert any(c["rainmap"] == "positive" and c["rainMap"] is not None for c in cases) and any(c["maps"] for c in cases)
+    assert {c["rainmap"] for c in cases} == {None, "positive"}
+    for c in cases:
+        assert (c["drainage"] > 0).all(), C.describe(c)  # sqrt(A) stays among the finite numbers
+        planes, bound = C.model(c)
+        assert all(np.isfinite(p).all() for p in planes) and bound >= 2, C.describe(c)
+
+
 def test_the_seeded_sweep_reaches_every_family_form_and_edge():
     cases = [c for seed in range(8) for c in C.relax_sweep_cases(seed)]
     assert len(cases) == 40 and len({C.describe(c) + c["name"] for c in cases}) == 40
-    assert {c["family"] for c in cases} == set(C.FAMILIES)
+    assert {c["family"] for c in cases} == set(C.SWEEP_FAMILIES) == set(C.FAMILIES) - {"fluvial_implicit_mfd"}
     assert {c["form"] for c in cases} == {"tile", "batch", "inplace"}
-    for fam in C.FAMILIES:
+    for fam in C.SWEEP_FAMILIES:
         assert {c["form"] for c in cases if c["family"] == fam} >= {"tile", "batch"}, fam
     assert any(c["name"] == "faint" for c in cases)
     mfd = [c for c in cases if c["family"] == "drainage_mfd"]
@@ -112,6 +151,13 @@ def test_walk_jacobi_and_tiled_agree(name, family):
         rm = C.drainage_rain_map(h.shape, 11, signed=True)
         walk = M.walk(h, 0.3, sea, rm, 16)[:1]
         others = [M.jacobi(h, 0.3, sea, rm, 16)[:1]] + [M.tiled(h, 0.3, sea, rm, 16, sweeps=s)[:1] for s in (1, 3, 16)]
+    elif family == "fluvial_implicit_mfd":
+        A = M.walk(h, 0.75, sea, C.drainage_rain_map(h.shape, 11), 16)[0]
+        assert (A > 0).all()
+        hard, upl = C.implicit_maps(h.shape, 11)
+        kw = dict(dt=200.0, seaLevel=sea, exponent=16, hardness=hard, upliftMap=upl)
+        walk = R2.walk(h, A, **kw)[:1]
+        others = [R2.jacobi(h, A, **kw)[:1]] + [R2.tiled(h, A, sweeps=s, **kw)[:1] for s in (1, 3, 16)]
     else:  # no relaxation: three iterations are one iteration three times, the border is held
         walk = (HS.diffuse(h, 100.0, 1.0, 3),)
         once = h
@@ -253,6 +299,56 @@ def test_without_erosion_and_uplift_the_implicit_step_returns_the_heights(name):
         assert np.array_equal(out[0], h) and changed.any() and (np.signbit(h[changed]) & (h[changed] == 0)).all()
     else:
         assert same(out[0], h), name
+
+
+@pytest.mark.parametrize("name", sorted(C.TILES))
+def test_without_erosion_and_uplift_the_multiple_flow_step_returns_the_heights(name):
+    h = make(name, 65)
+    (out,), _ = C.model(C.identity_case(h, family="fluvial_implicit_mfd"))
+    if name == "zeros":  # no cell of it has a lower neighbour: b = -0 + +0 is +0 on every cell that is no outlet
+        changed = out[0].view(np.uint32) != h.view(np.uint32)
+        assert np.array_equal(out[0], h) and changed.any() and (np.signbit(h[changed]) & (h[changed] == 0)).all()
+        assert not F.outlets(h, OFF)[changed].any()
+    else:
+        assert same(out[0], h), name
+
+
+def drops_and_gates(h, exponent):
+    """(the cells with a drop > 0 to some neighbour, the drops > 0 per direction, the gates of the multiple-flow model)."""
+    drop = np.zeros((8,) + h.shape, bool)
+    for k, (dx, dz) in enumerate(F.NEIGHBOURS):
+        c, n = F._window(h.shape, dx, dz)
+        drop[k][c] = h[c] - h[n] > 0
+    return drop.any(axis=0), drop, M.weights(h, OFF, exponent) > 0
+
+
+@pytest.mark.parametrize("res", [66, 97])
+@pytest.mark.parametrize("name", ["uniform", "metres"])
+def test_at_exponent_16_a_cell_without_an_open_edge_comes_back_as_b(name, res):
+    """Exponent 16, uplift 0, the sea off.  The cells with a drop > 0 to some neighbour and no open edge exist, and every one
+    of them is an outlet of the border: the steepest neighbour's quotient s / best is 1.0 exactly and so are its powers, so a
+    cell inside keeps that gate whatever underflows around it.  What underflow does shut is single gates (the vanished
+    weights of the test above): cells inside with a lower neighbour the step does not look at.  Both come back as the model
+    says: the first as b, the second from their open gates alone."""
+    h = make(name, res)
+    lower, drop, G = drops_and_gates(h, 16)
+    opens = G.any(axis=0)
+    shut = lower & ~opens
+    inside = ~F.outlets(h, OFF)
+    some_shut = inside & (drop & ~G).any(axis=0)
+    print("%s %d exponent 16: %d cells with a drop > 0 and no open edge, %d of them inside; %d cells inside with a gate shut "
+          "on a drop > 0" % (name, res, int(shut.sum()), int((shut & inside).sum()), int(some_shut.sum())))
+    assert shut.sum() > 0 and not (shut & inside).any() and (opens[inside] == lower[inside]).all()
+    assert some_shut.sum() > 0 and opens[some_shut].all()
+    A = M.walk(h, exponent=16)[0]
+    assert (A > 0).all()
+    for dt in (1.0, 200.0):
+        kw = dict(uplift=0.0, dt=dt, exponent=16)
+        out = R2.walk(h, A, **kw)[0]
+        _, b, Fk = R2.coefficients(h, A, **kw)
+        assert np.isfinite(out).all() and same(out[~opens], b[~opens]) and same(b, h)  # uplift 0: b is the heights
+        assert not Fk[~G].any() and same(R2.step(out, G, b, Fk), out)
+        assert (out[some_shut] < h[some_shut]).all()  # they erode along the gates that stayed open
 
 
 # ---- the invariants of the GPU test's chain ------------------------------------------------------------------------------------
