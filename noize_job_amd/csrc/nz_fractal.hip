@@ -91,6 +91,36 @@ __device__ __forceinline__ float cnoise2(float Px, float Py) {
 // DX10_CLAMP, where a clamped NaN is 0 as well): no v_max_f32 behind the v_sub_f32.
 __device__ __forceinline__ float falloff_clamped(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
+// The corner-1 step of the 2-D simplex, x12.xy -= i1 with i1 = gt ? (1, 0) : (0, 1), as two masked adds: "where gt,
+// x12x += -1" and "where not gt, x12y += -1".  The same bits: v - 1 is v + (-1) in IEEE arithmetic, and the component
+// that the reference subtracts +0 from is unchanged by that subtraction whatever it holds (v - (+0) == v for every
+// finite and infinite v, -0 - (+0) == -0 under round-to-nearest, and a NaN stays that NaN: x12 comes out of an addition,
+// so it is quiet before the step and nothing is left for the subtraction to quieten).  Two VALU instructions per cell
+// instead of two selects and two subtractions; the three scalar instructions issue beside the other waves' VALU work.
+// The block saves exec and puts it back, so it composes with any exec it meets: lanes that enter inactive (the right
+// edge's partial wave, a divergent caller) keep both values -- the first AND takes them out, the XOR against the saved
+// mask cannot bring them back -- and a wave whose gt is uniform runs one of the adds with exec = 0, which writes nothing.
+// gt false covers NaN, as in `gt ? 0 : 1`.
+// Wait states: none are needed, and none are inside the string.  A scalar write of exec is interlocked against the
+// next vector instruction on gfx9 / CDNA (the ISA's table of manually inserted wait states has rows for VALU writes of
+// exec -- before DPP, readlane, EXECZ as a source -- and none for an SALU write followed by an ordinary VALU
+// instruction), and the compiler's own code shows the same: its hazard recogniser leaves `s_or_b64 exec, exec, s[n:n+1]`
+// directly in front of a VALU instruction where the divergent branches of this file join (the row's t / norm behind the
+// octave loops, for one), with no s_nop between them.  The mask is written by a v_cmp and read by an SALU instruction:
+// interlocked as well (the rows for a VALU write of an SGPR concern VMEM and lane-select readers).
+__device__ __forceinline__ void corner1_step(bool gt, float &x12x, float &x12y) {
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(gt);
+    unsigned long long saved;
+    asm("s_and_saveexec_b64 %0, %3\n\t"
+        "v_add_f32 %1, -1.0, %1\n\t"
+        "s_xor_b64 exec, exec, %0\n\t"
+        "v_add_f32 %2, -1.0, %2\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(saved), "+v"(x12x), "+v"(x12y)
+        : "s"(mask)
+        : "scc");
+}
+
 // noise.snoise(float2), Appendix A.3
 __device__ __forceinline__ float snoise2(float vx, float vy) {
     const float Cx = 0.211324865405187f, Cy = 0.366025403784439f;
@@ -102,6 +132,7 @@ __device__ __forceinline__ float snoise2(float vx, float vy) {
     bool gt = x0x > x0y;
     float i1x = gt ? 1.0f : 0.0f, i1y = gt ? 0.0f : 1.0f;
     float x12x = x0x + Cx, x12y = x0y + Cx, x12z = x0x + Cz, x12w = x0y + Cz;
+    // (not corner1_step: i1 feeds the second permute below as well, so the selects stay and the masked form saves nothing)
     x12x -= i1x;
     x12y -= i1y;
     ix = mod289f(ix);  // plain form: the lattice coordinate itself may exceed 2^24 (the exact-FMA form may not)
@@ -415,8 +446,8 @@ __device__ __forceinline__ float noise_value(float x, float z, const psr_tables 
 //   T1[i]  = 16 * permute(i)                                   (a byte offset into T2)
 //   T2[j]  = {a0, h, 1.79284291400159 - 0.85373472095314*(a0*a0 + h*h), 0} of p = permute(j)
 // and a corner costs one ds_read_b128 and its share of a cell's ds_read2_b32, shift, two shift-adds and select (below)
-// instead of two permutes and the gradient decode (26 fp32 ops + 4 floors).  Per octave-cell 72.5 VALU instructions in
-// the ladder loop of fractal_simplex_tab_kernel<2, false, 0>, 75 in its table loop, 77 with the recurrence, instead of 151.
+// instead of two permutes and the gradient decode (26 fp32 ops + 4 floors).  Per octave-cell 69 VALU instructions in
+// the ladder loop of fractal_simplex_tab_kernel<2, false, 0>, 73 in its table loop, 75 with the recurrence, instead of 151.
 constexpr int NZ_T1_N = 292, NZ_T2_N = 580;
 // The tables hold hashes of lattice coordinates reduced to [0, 289]; fp32 mod289 only guarantees that range
 // for |integer| < 2.3e6 (and the skew of snoise stretches a coordinate by up to 1.73).  Samples beyond this
@@ -451,20 +482,15 @@ __device__ __forceinline__ int corner_base(int ix, int k) {
     return a;
 }
 
-// (returns snoise / 2: see the end).  (ux, uy) are the skewed coordinates v + s of (vx, vy): snoise2_tab below forms them
-// with the reference's operations, the power-of-two octave ladder scales octave 0's (fractal_simplex_tab_kernel).
-// s_t1 is the staged pair form of T1 (stage_t1_pairs<0>).
-__device__ __forceinline__ float snoise2_tab_skewed(float vx, float vy, float ux, float uy, const int *s_t1,
-                                                    const float4 *s_t2) {
+// The simplex cell from its unskewed offset on (returns snoise / 2: see the end): (fx, fy) is the cell's lattice corner,
+// the floors of the skewed coordinates, and (x0x, x0y) the sample's offset from it, v - f + t, formed by the two callers
+// below.  s_t1 is the staged pair form of T1 (stage_t1_pairs<0>).
+__device__ __forceinline__ float snoise2_tab_cell(float x0x, float x0y, float fx, float fy, const int *s_t1,
+                                                  const float4 *s_t2) {
     const float Cx = 0.211324865405187f, Cz = -0.577350269189626f;
-    float fx = floorf(ux), fy = floorf(uy);
-    float t = fx * Cx + fy * Cx;
-    float x0x = vx - fx + t, x0y = vy - fy + t;
     bool gt = x0x > x0y;
-    float i1x = gt ? 1.0f : 0.0f, i1y = gt ? 0.0f : 1.0f;
     float x12x = x0x + Cx, x12y = x0y + Cx, x12z = x0x + Cz, x12w = x0y + Cz;
-    x12x -= i1x;
-    x12y -= i1y;
+    corner1_step(gt, x12x, x12y);  // x12.xy -= i1
     int ixi = (int)mod289i(fx), iyi = (int)mod289i(fy);
     // fp32 mod289 returns 289 (not 0) for some negative multiples of 289 (-8959, -17629, ...): the tables carry
     // that index.  Callers guarantee |v| < NZ_TAB_LIMIT (or NaN, which converts to index 0 and poisons the result
@@ -494,6 +520,24 @@ __device__ __forceinline__ float snoise2_tab_skewed(float vx, float vy, float ux
     // RN(65 n) and RN(1 + v) / 2 == RN(0.5 + v / 2) (where v is small enough for a halving to lose a denormal bit, both
     // forms return 0.5).  The caller adds the 0.5: one multiply and one add instead of two multiplies and an add.
     return 65.0f * (m0 * q0 + m1 * q1 + m2 * q2);
+}
+// (ux, uy) are the skewed coordinates v + s of (vx, vy): snoise2_tab below forms them with the reference's operations.
+__device__ __forceinline__ float snoise2_tab_skewed(float vx, float vy, float ux, float uy, const int *s_t1,
+                                                    const float4 *s_t2) {
+    const float Cx = 0.211324865405187f;
+    float fx = floorf(ux), fy = floorf(uy);
+    float t = fx * Cx + fy * Cx;
+    return snoise2_tab_cell(vx - fx + t, vy - fy + t, fx, fy, s_t1, s_t2);
+}
+// The octave of the power-of-two ladder (fractal_simplex_tab_kernel has the proof): v = f (x, y) with f a power of two and
+// the products exact, (ux, uy) octave 0's skewed coordinates scaled by f.  The unskew's v - floor is ONE fused operation here,
+// RN(f x - fx), where snoise2_tab_skewed rounds twice, RN(RN(f x) - fx): the same bits, because the inner rounding is exact.
+__device__ __forceinline__ float snoise2_tab_ladder(float f, float x, float y, float ux, float uy, const int *s_t1,
+                                                    const float4 *s_t2) {
+    const float Cx = 0.211324865405187f;
+    float fx = floorf(ux), fy = floorf(uy);
+    float t = fx * Cx + fy * Cx;
+    return snoise2_tab_cell(__builtin_fmaf(f, x, -fx) + t, __builtin_fmaf(f, y, -fy) + t, fx, fy, s_t1, s_t2);
 }
 __device__ __forceinline__ float snoise2_tab(float vx, float vy, const int *s_t1, const float4 *s_t2) {
     const float Cy = 0.366025403784439f;
@@ -672,8 +716,15 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
             //     that ulp, > 2^-24 min(|a|, |b|): s0 is 0 or > 2^-26 lo, and Ux, Uz are 0 or > 2^-50 lo.  Times any
             //     f[i] >= g that is > 2^-114: nothing nonzero comes within 2^12 of the subnormal range, in either form.
             // NaN fails every comparison of ladder_row, and a wave with one lane outside these bounds takes the loops below
-            // as a whole: the ballot costs such a wave its speed-up, never a bit.  From the floors on the octave is
-            // snoise2_tab's, instruction for instruction; per pair of cells 7 multiplies open it instead of 12 operations.
+            // as a whole: the ballot costs such a wave its speed-up, never a bit.
+            // The unskew opens with vx - fx, vz - fz, the floors subtracted from vx = RN(f x), vz = RN(f z).  Those products
+            // are exact under the same bounds (f x is x with its exponent shifted: no overflow below 2^20, nothing nonzero
+            // within 2^12 of the subnormal range, a zero keeps its sign), so RN(RN(f x) - fx) = RN(f x - fx) =
+            // fmaf(f, x, -fx): one rounding either way, and the loop forms neither vx nor vz (snoise2_tab_ladder).  The
+            // other loops keep the subtraction: their f is no power of two, f x rounds, and the fused form would round
+            // f x - fx once where the reference rounds twice (tests/test_fractal_ladder_fold.py has counterexamples).
+            // From there on the octave is snoise2_tab's, instruction for instruction; per pair of cells 4 multiplies open
+            // it instead of the skew's 12 operations, and 4 FMAs stand where the unskew's 4 subtractions were.
             const float Cy = 0.366025403784439f;
             float Ux[VEC], Uz[VEC];
             const float zs = zi * Cy;
@@ -688,12 +739,9 @@ __global__ __launch_bounds__(256) void fractal_simplex_tab_kernel(float *__restr
                 f = fn; a = an;
                 const int nx = min(i + 1, NZ_OCT_TAB - 1);
                 fn = oct.f[nx]; an = oct.a[nx];
-                float zV = f * zi;
 #pragma unroll
-                for (int c = 0; c < VEC; c++) {
-                    float xV = f * xi[c];
-                    octave_add<SHAPE>(t[c], w[c], a, rectify_half(snoise2_tab_skewed(xV, zV, f * Ux[c], f * Uz[c], s_t1, s_t2)), rp);
-                }
+                for (int c = 0; c < VEC; c++)
+                    octave_add<SHAPE>(t[c], w[c], a, rectify_half(snoise2_tab_ladder(f, xi[c], zi, f * Ux[c], f * Uz[c], s_t1, s_t2)), rp);
             }
         } else if (p.fmax * reach < NZ_TAB_LIMIT && oct.n > 0) {
             // ... and the host has run the wave-uniform recurrence (nz_octave_table: the same fp32 operations, so the same
