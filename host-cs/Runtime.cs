@@ -115,6 +115,18 @@ namespace xshazwar.noize.hip {
         public IntPtr hardness, upliftMap, proceed, tally;
     }
 
+    // the implicit fluvial step with sediment deposition: NzFluvialImplicitDesc, then the deposition coefficient, the
+    // Gauss-Seidel iterations and the optional flux plane (nz_fluvial_sediment*); IntPtr.Zero = option off
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NzFluvialSedimentDesc {                                                            // nz_fluvial_sediment_desc
+        public float erodibility, uplift, dt, seaLevel;
+        public int maxPasses;
+        public IntPtr hardness, upliftMap, proceed, tally;
+        public float deposition;
+        public int iterations;
+        public IntPtr flux;
+    }
+
     // the hillslope diffusion step's scalars (nz_hillslope_diffusion*)
     [StructLayout(LayoutKind.Sequential)]
     public struct NzHillslopeDesc {                                                                  // nz_hillslope_desc

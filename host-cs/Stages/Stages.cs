@@ -757,10 +757,11 @@ namespace xshazwar.noize.hip {
         public DeviceTile rainMap = null, hardness = null, upliftMap = null;
         public FlowRouting routing = FlowRouting.Steepest;
         public int flowExponent = 1;
-        DeviceTile work;                         // nz_fluvial_implicit_work_floats floats
+        protected DeviceTile work;               // nz_fluvial_implicit_work_floats floats (a deriving stage: its own entry's)
         DeviceTile drainageWork;                 // the drainage entry's work floats; its second int32: the solve's `proceed`
-        DeviceTile area, plane, tally;           // the drainage, the heights' second plane, {steps applied, passes that did work}
-        int resolution, count = 1;
+        protected DeviceTile area;               // the drainage
+        DeviceTile plane, tally;                 // the heights' second plane, {steps applied, passes that did work}
+        protected int resolution, count = 1;
         static readonly IntPtr Zeros = ZeroWords();   // what the tally is set to before a run; lives as long as the process
         static IntPtr ZeroWords() {
             IntPtr p = System.Runtime.InteropServices.Marshal.AllocHGlobal(8);
@@ -768,7 +769,7 @@ namespace xshazwar.noize.hip {
             return p;
         }
         public ImplicitFluvialStage(GpuContext ctx) : base(ctx) {}
-        int Cells => count * resolution * resolution;
+        protected int Cells => count * resolution * resolution;
         public DeviceTile Drainage => area;
         public int? Steps => Counted(0);
         public int? Passes => Counted(1);
@@ -778,9 +779,19 @@ namespace xshazwar.noize.hip {
             jobHandle.Complete();
             return BitConverter.SingleToInt32Bits(tally.ToArray()[k]);
         }
-        DeviceTile Size(DeviceTile t, bool want, int n) {   // a plane of the stage: resized with the payload, gone when not wanted
+        protected DeviceTile Size(DeviceTile t, bool want, int n) {   // a plane of the stage: resized with the payload, gone when not wanted
             if (t != null && (!want || t.Length != n)) { t.Dispose(); t = null; }
             return want && t == null ? ctx.Alloc(n) : t;
+        }
+        // the hook of a stage that derives from this one (SedimentFluvialStage): the size of `work`, and the solve of one
+        // iteration, heights cur -> other, with the desc of the run
+        protected virtual int SolveWorkFloats() => (int) (ulong) Native.nz_fluvial_implicit_work_floats(resolution, count);
+        protected virtual void EnqueueSolve(bool batch, DeviceTile cur, DeviceTile other, ref NzFluvialImplicitDesc solve, out ulong h) {
+            if (batch) {
+                Native.Check(Native.nz_fluvial_implicit_batch(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, count, 0, out h), "nz_fluvial_implicit_batch");
+            } else {
+                Native.Check(Native.nz_fluvial_implicit(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, 0, out h), "nz_fluvial_implicit");
+            }
         }
         public override void Schedule(PipelineWorkItem requirements, GpuJobHandle dependency) {
             if (requirements.data is GeneratorData g) {
@@ -792,7 +803,7 @@ namespace xshazwar.noize.hip {
             foreach (DeviceTile m in new[] { rainMap, hardness, upliftMap })   // before any launch
                 if (m != null && m.Length != Cells) throw new Exception($"ImplicitFluvialStage: a plane of {m.Length} floats does not fit the payload's {Cells}");
             // sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
-            work = Size(work, true, (int) (ulong) Native.nz_fluvial_implicit_work_floats(resolution, count));
+            work = Size(work, true, SolveWorkFloats());
             bool multiple = routing == FlowRouting.Multiple;
             drainageWork = Size(drainageWork, true, (int) (ulong) (multiple ? Native.nz_drainage_mfd_work_floats(resolution, count)
                                                                             : Native.nz_drainage_area_work_floats(resolution, count)));
@@ -824,11 +835,7 @@ namespace xshazwar.noize.hip {
                 } else {
                     Native.Check(Native.nz_drainage_area(ctx.Handle, cur.Ptr, area.Ptr, drainageWork.Ptr, ref drain, resolution, 0, IntPtr.Zero), "nz_drainage_area");
                 }
-                if (batch) {
-                    Native.Check(Native.nz_fluvial_implicit_batch(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, count, 0, out h), "nz_fluvial_implicit_batch");
-                } else {
-                    Native.Check(Native.nz_fluvial_implicit(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref solve, resolution, 0, out h), "nz_fluvial_implicit");
-                }
+                EnqueueSolve(batch, cur, other, ref solve, out h);
                 DeviceTile s = cur; cur = other; other = s;
             }
             if (d.write != null) { d.data = cur; d.write = other; }   // the pair as the run left it: `data` holds the result
@@ -997,6 +1004,48 @@ namespace xshazwar.noize.hip {
             ulong h;
             Native.Check(Native.nz_implicit_fluvial_stripe_finalise(ctx.Handle, heightRows, outRows, ref st, converged, dependency.id, out h), "nz_implicit_fluvial_stripe_finalise");
             return ctx.Wrap(h);
+        }
+    }
+
+    // Implicit stream-power erosion WITH sediment deposition (new-framework feature; the model: nz_fluvial_sediment in
+    // include/noize_hip.h): ImplicitFluvialStage whose solve carries the xi-q deposition term, so valleys aggrade as well as
+    // cut.  Everything but the solve call is inherited: per iteration the drainage call (either routing), the proceed word,
+    // the plane ping-pong, Steps / Passes / Converged and the resize logic.  deposition: G >= 0, dimensionless; 0 is
+    // ImplicitFluvialStage bit for bit.  sedimentIterations: the Gauss-Seidel iterations K of every solve; the iteration
+    // contracts for G up to about 1, slower as G * dt grows -- read Residual.  recordFlux: keep the sediment-flux plane Q of
+    // the last applied iteration in Flux.  maxPasses is the budget of each of the 2K + 1 series of a solve, and Passes counts
+    // them all.  Residual waits for the handle: max |hK - h(K-1)| of the last iteration that ran, null before the first run.
+    public class SedimentFluvialStage : ImplicitFluvialStage {
+        public float deposition = 0.5f;
+        public int sedimentIterations = 4;
+        public bool recordFlux = false;
+        DeviceTile flux;                         // the flux plane, with recordFlux
+        public SedimentFluvialStage(GpuContext ctx) : base(ctx) {}
+        public DeviceTile Flux => flux;
+        public float? Residual {
+            get {
+                if (work == null) return null;
+                jobHandle.Complete();
+                return work.Offset(0, 3).ToArray()[2];   // {passes, converged, residual}
+            }
+        }
+        protected override int SolveWorkFloats() => (int) (ulong) Native.nz_fluvial_sediment_work_floats(resolution, count);
+        protected override void EnqueueSolve(bool batch, DeviceTile cur, DeviceTile other, ref NzFluvialImplicitDesc solve, out ulong h) {
+            flux = Size(flux, recordFlux, Cells);
+            NzFluvialSedimentDesc desc = new NzFluvialSedimentDesc {
+                erodibility = solve.erodibility, uplift = solve.uplift, dt = solve.dt, seaLevel = solve.seaLevel,
+                maxPasses = solve.maxPasses, hardness = solve.hardness, upliftMap = solve.upliftMap, proceed = solve.proceed,
+                tally = solve.tally, deposition = deposition, iterations = sedimentIterations,
+                flux = flux != null ? flux.Ptr : IntPtr.Zero };
+            if (batch) {
+                Native.Check(Native.nz_fluvial_sediment_batch(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref desc, resolution, count, 0, out h), "nz_fluvial_sediment_batch");
+            } else {
+                Native.Check(Native.nz_fluvial_sediment(ctx.Handle, cur.Ptr, area.Ptr, other.Ptr, work.Ptr, ref desc, resolution, 0, out h), "nz_fluvial_sediment");
+            }
+        }
+        public override void OnDestroy() {
+            flux?.Dispose(); flux = null;
+            base.OnDestroy();
         }
     }
 

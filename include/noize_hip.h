@@ -1509,6 +1509,86 @@ int32_t nz_fluvial_implicit_mfd_batch(nz_ctx *ctx, const float *height, const fl
  * was in force. */
 int32_t nz_debug_fluvial_implicit_mfd_sweeps(int32_t sweeps);
 
+/* ---- implicit fluvial erosion with sediment deposition: the xi-q model (new-framework feature) --------------------------
+ * nz_fluvial_implicit is detachment-limited: eroded material leaves the tile, valleys cut and never aggrade.  This entry
+ * adds the deposition term of Yuan, Braun, Guerit, Rouby & Cordonnier (2019), the one fastscape's StreamPowerLaw has: what
+ * the cells upstream gave up comes down the receiver tree as a sediment flux Q, and a cell takes G * Qin / A of it back.
+ * The term sits in the right-hand side of nz_fluvial_implicit's solve, and K Gauss-Seidel iterations bring flux and heights
+ * to agree.
+ *
+ * THE MODEL (tests/fluvial_sediment_ref.py restates it as walks; the kernels are nz_fluvial_sediment.hip):
+ *   Tile, neighbours, outlets, receivers r(c), du, kc, b0 = b, f and invL are exactly nz_fluvial_implicit's; A is the
+ *   caller's drainage plane; G = deposition >= 0, dimensionless; K = iterations >= 0.  Every operation is rounded once to
+ *   float32, no contraction, divisions correctly rounded.  solve(b) is nz_fluvial_implicit's recurrence with right-hand
+ *   side b: a cell without a receiver takes h' = b, otherwise h' = (b + f * h'[q]) / (1 + f).
+ *     h0 = solve(b0)                                   -- nz_fluvial_implicit's result bit for bit
+ *     for k = 1 .. K:
+ *       e[c]   = b0[c] - h(k-1)[c]                     -- what the cell gave up this step, uplift included; +0 on outlets,
+ *                                                         may be negative
+ *       Q[c]   = e[c] + Q[d] over the donors d of c, added one by one onto e[c] in neighbour order 0..7 -- the drainage
+ *                recurrence of nz_drainage_area with a signed per-cell source
+ *       Qin[c] = the same gather of the final Q started from +0 (the flux entering the cell, its own share excluded),
+ *                then Qin < 0 ? +0 : Qin; a NaN passes
+ *       bk[c]  = b0[c] on outlets; elsewhere, pits included, b0[c] + (G * Qin[c]) / A[c] where A[c] > 0 and b0[c] where not
+ *       hk     = solve(bk)
+ *     out = hK;  residual = max over c of |hK[c] - h(K-1)[c]|, taken with d > m so a NaN cell does not enter, +0 when
+ *     K == 0: how far the iteration still was from rest.  flux (optional plane) = the Q of iteration K, +0 when K == 0: the
+ *     sediment-flux map.
+ *   Q is a fixed function of the final values of strictly higher cells and a solve of strictly lower ones, so both fixed
+ *   points are unique and every schedule ends in the same bits.  Every operation of solve is monotone in b and bk >= b0, so
+ *   hK >= h0 cell by cell where neither is NaN.  deposition == 0 or iterations == 0 gives nz_fluvial_implicit's plane bit
+ *   for bit.
+ * THE LIMITS, plainly.  The iteration is a contraction for G up to about 1, slower as G * dt grows: on a filled 97^2 tile
+ *   at dt 100 the residual falls by 3.5 per iteration at G 0.5 and by 1.75 at G 1, and at G 2 with a large dt it stalls
+ *   (DESIGN.md sections 4 and 9) -- read `residual`.  Receivers, f and A are those of the INCOMING heights for the whole
+ *   call, as in nz_fluvial_implicit: deposition may lift a cell above a donor, the next step's receivers see that, and
+ *   nz_fill_depressions (DepressionFillStage) belongs in front as before.  There is no lake trapping: a pit takes the same
+ *   deposit term as any cell.  The multiple-flow solve (nz_fluvial_implicit_mfd) has no sediment form.
+ *
+ * The entry enqueues, without waiting for the device: a begin launch; nz_fluvial_implicit's setup launch and one donor-byte
+ * launch (nz_drainage_area's mask), once per call; solve series 0 (maxPasses launches of nz_fluvial_implicit's pass); per k
+ * a source launch (e, a fresh series), an accumulation series of maxPasses pass launches (nz_drainage_area's gather with
+ * source e, quiet tiles skipped), a deposit launch (Qin at radius 1 from the final Q, bk) and a solve series of maxPasses
+ * launches on bk; and the finalise launch.  A series at rest lets its remaining launches return at the gate, and a series
+ * that did not come to rest stops every launch behind it.  After completion the first three words of `work` hold {passes
+ * that did work over all series, converged 0/1, residual as float bits}.  The result is ALL OR NOTHING: when any of the
+ * 2K + 1 series did not come to rest within maxPasses, or the call was told not to proceed, out = height bit for bit, `flux`
+ * is untouched, converged == 0 and residual == +0.  `proceed` and `tally` are nz_fluvial_implicit's; tally[1] grows by the
+ * passes of all series.
+ *
+ * `work` = nz_fluvial_sediment_work_floats(resolution, count) floats, stage-owned (seven planes and two bytes per cell).
+ * resolution == 0 or count == 0 does nothing and returns NZ_OK; the _batch form runs `count` tiles stored back to back, each
+ * position equal to the single-tile call bit for bit, with status words and residual over the whole batch.  The 16-byte
+ * path runs when every plane is 16-byte aligned and resolution % 4 == 0, the 4-byte path otherwise.  Neither an
+ * _rw pair form nor a row-stripe form exists.
+ * Refused with NZ_ERR_INVALID, the message naming the argument and nothing written: everything nz_fluvial_implicit
+ * refuses; deposition negative or not finite; iterations < 0; flux overlapping out, work, height, drainage, a map, tally or
+ * proceed.
+ * Defaults of the hosts' SedimentFluvialStage: ImplicitFluvialStage's, deposition 0.5, sedimentIterations 4 (the smallest
+ * K whose residual is <= 1 % of max |b0 - h0| on the filled 97^2 test tile at dt 100: DESIGN.md section 4), recordFlux
+ * off. */
+typedef struct nz_fluvial_sediment_desc {
+    float erodibility, uplift, dt, seaLevel;
+    int32_t maxPasses;        /* the budget of each of the 2K + 1 series */
+    const float *hardness;    /* NULL: erodibility everywhere */
+    const float *upliftMap;   /* NULL: uplift everywhere */
+    const int32_t *proceed;   /* device word, NULL: always run; a word of 0: the step is not applied */
+    int32_t *tally;           /* device, 2 words, NULL: off; tally[0] += 1 when the step was applied, tally[1] += passes that did work */
+    float deposition;         /* G >= 0 */
+    int32_t iterations;       /* K >= 0 */
+    float *flux;              /* device plane, NULL: off; the Q of iteration K */
+} nz_fluvial_sediment_desc;
+size_t nz_fluvial_sediment_work_floats(int32_t resolution, int32_t count);
+int32_t nz_fluvial_sediment(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                            const nz_fluvial_sediment_desc *desc, int32_t resolution, nz_handle dep, nz_handle *out_handle);
+int32_t nz_fluvial_sediment_batch(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                  const nz_fluvial_sediment_desc *desc, int32_t resolution, int32_t count, nz_handle dep,
+                                  nz_handle *out_handle);
+/* Test hook, the twin of nz_debug_fluvial_implicit_sweeps with a cap of its own: one cap on the on-chip sweeps per tile of
+ * both kinds of series, solve and accumulation (process-wide; <= 0 restores the default, 16).  Results must not change.
+ * Returns the cap that was in force. */
+int32_t nz_debug_fluvial_sediment_sweeps(int32_t sweeps);
+
 /* ---- the stock stage list as a parameter block --------------------------------------------------------------------
  * NoiseStage -> [KernelFilterStage] -> [FlowMapStage] -> [ErosionKernelJob x n] (README.md:23-32, the metric pipeline) as
  * nz_sharded_create takes it; an iteration count of 0 leaves a stage out.  (Rounds 3 and 4 also offered the list as ONE call

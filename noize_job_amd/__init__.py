@@ -12,7 +12,7 @@ from .pipeline import (BasePipeline, BlurHelper, ConstantOperationType, Constant
                        MeshTileStage, MeshType, NoiseStage, PipelineJoint, PipelineStage, PipelineWorkItem, ReduceData,
                        ReducePipeline, ReduceStage, ShapedNoiseStage, UpsampleStage, Upstream, WarpedNoiseStage, WatershedStage,
                        ReductionType, ResampleFilter, StageGaussianBlur, StageThermalErosion,
-                       StageIO, StageSmoothBlur, StreamOrderStage, ImplicitFluvialStage, HillslopeDiffusionStage, MfdDrainageStage, FlowRouting, MfdFluvialStage)
+                       StageIO, StageSmoothBlur, StreamOrderStage, ImplicitFluvialStage, HillslopeDiffusionStage, MfdDrainageStage, FlowRouting, MfdFluvialStage, SedimentFluvialStage)
 
 from .pipeline_state import (HandleLock, MeshTileReferenceDataStage, PipelineStateManager, ReadGeneratorContextStage,
                              WriteGeneratorContextStage)

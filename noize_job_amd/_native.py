@@ -132,6 +132,13 @@ class FluvialImplicitMfdDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("hardness", "upliftMap", "proceed", "tally")])
 
 
+class FluvialSedimentDesc(C.Structure):
+    """nz_fluvial_sediment_desc (include/noize_hip.h): FluvialImplicitDesc, then the deposition coefficient, the Gauss-Seidel
+    iterations and the optional flux plane (a device address; None = off)."""
+    _fields_ = (FluvialImplicitDesc._fields_ +
+                [("deposition", C.c_float), ("iterations", C.c_int32), ("flux", C.c_void_p)])
+
+
 class HillslopeDesc(C.Structure):
     """nz_hillslope_desc (include/noize_hip.h): the diffusivity, the time step and the number of steps."""
     _fields_ = [("diffusivity", C.c_float), ("dt", C.c_float), ("iterations", C.c_int32)]
@@ -146,6 +153,7 @@ shed_p = C.POINTER(WatershedDesc)
 order_p = C.POINTER(StreamOrderDesc)
 fimp_p = C.POINTER(FluvialImplicitDesc)
 fmfd_p = C.POINTER(FluvialImplicitMfdDesc)
+fsed_p = C.POINTER(FluvialSedimentDesc)
 hill_p = C.POINTER(HillslopeDesc)
 ep_p, tm_p, tp_p = C.POINTER(ErosionParameters), C.POINTER(TileSetMeta), C.POINTER(TerrainParams)
 sd_p = C.POINTER(ShardedDesc)
@@ -290,6 +298,10 @@ SIGNATURES = {
     "nz_fluvial_implicit_mfd": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fmfd_p, _i] + _tail),
     "nz_fluvial_implicit_mfd_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fmfd_p, _i, _i] + _tail),
     "nz_debug_fluvial_implicit_mfd_sweeps": (_i, [_i]),
+    "nz_fluvial_sediment_work_floats": (_sz, [_i, _i]),
+    "nz_fluvial_sediment": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fsed_p, _i] + _tail),
+    "nz_fluvial_sediment_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, dev_ptr, fsed_p, _i, _i] + _tail),
+    "nz_debug_fluvial_sediment_sweeps": (_i, [_i]),
     "nz_hillslope_diffusion_work_floats": (_sz, [_i, _i]),
     "nz_hillslope_diffusion": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, hill_p, _i] + _tail),
     "nz_hillslope_diffusion_batch": (_i, [ctx_p, dev_ptr, dev_ptr, dev_ptr, hill_p, _i, _i] + _tail),

@@ -557,6 +557,27 @@ int32_t nz_launch_fluvial_implicit_mfd_pass(hipStream_t s, const unsigned char *
                                             const float *h_in, float *h_out, int *status, const unsigned char *flags_in,
                                             unsigned char *flags_out, int res, int count, int pass, int sweeps);
 
+// implicit fluvial erosion with sediment deposition (nz_fluvial_sediment.hip); the setup and the solve passes are the
+// implicit launches above, on the status words `solve`.  begin: totals {passes, converged, residual} = 0 and `solve` as the
+// implicit begin.  mask: one donor byte per cell (behind solve[ST_GO]).  source: e = b0 - hprev, the status words `accum` of a
+// fresh accumulation series whose ST_GO is the verdict on `solve`, whose passes join the totals.  gather_pass: pass `pass` of
+// Q, planes q_in -> q_out (pass 0 reads none: it starts from e), as the drainage pass.  deposit: bk (may be e) from the final
+// Q, fresh `solve` words whose ST_GO is the verdict on `accum`.  finalise: the verdict, totals, tally, the residual against
+// hprev (NULL: none), flux = q (NULL: +0) when flux is not NULL, and out = h when the call did not come to rest
+int32_t nz_launch_fluvial_sediment_begin(hipStream_t s, int *totals, int *solve, const int *proceed);
+int32_t nz_launch_fluvial_sediment_mask(hipStream_t s, const float *h, unsigned char *donors, const int *solve, float sea,
+                                        int res, int count);
+int32_t nz_launch_fluvial_sediment_source(hipStream_t s, const float *b0, const float *hprev, float *e, const int *solve,
+                                          int *accum, int *totals, size_t n);
+int32_t nz_launch_fluvial_sediment_gather_pass(hipStream_t s, const unsigned char *donors, const float *e, const float *q_in,
+                                               float *q_out, int *status, const unsigned char *flags_in,
+                                               unsigned char *flags_out, int res, int count, int pass, int sweeps);
+int32_t nz_launch_fluvial_sediment_deposit(hipStream_t s, const unsigned char *donors, const float *q, const float *b0,
+                                           const float *area, const float *h, float *bk, const int *accum, int *solve,
+                                           int *totals, float deposition, float sea, int res, int count);
+int32_t nz_launch_fluvial_sediment_finalise(hipStream_t s, const float *h, float *out, const float *hprev, const float *q,
+                                            float *flux, const int *solve, int *totals, int *tally, size_t n);
+
 // hillslope diffusion (nz_hillslope.hip).  tables: inv[i] and cp[i], i = 1 .. res-2, of r (res floats each; res >= 3).
 // step: one step on `count` tiles of res^2 cells stored back to back, `in` -> `out` (the same pointer: in place; otherwise
 // disjoint), as three launches: the rows' forward sweep, their backward sweep, the columns' two sweeps

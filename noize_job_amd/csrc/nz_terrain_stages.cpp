@@ -1209,6 +1209,112 @@ extern "C" int32_t nz_fluvial_implicit_mfd_batch(nz_ctx *ctx, const float *heigh
 }
 
 // ---------------------------------------------------------------------------------------------
+// implicit fluvial erosion with sediment deposition: the xi-q iteration around the implicit solve (new-framework feature,
+// include/noize_hip.h, nz_fluvial_sediment.hip)
+// ---------------------------------------------------------------------------------------------
+// `work`: the head -- words 0..2 the totals {passes, converged, residual}, words 8.. the solve's status words -- the
+// accumulation's status words, one receiver and one donor byte per cell, the planes b0, f, e (which bk overwrites), two Q
+// planes and two h' planes.  The checks (check_implicit_scalars, check_implicit_planes), the setup launch and every solve
+// pass are fluvial_implicit_impl's.
+namespace {
+struct fluvial_sediment_work {
+    relax_work hd;
+    int *solve, *accum;
+    unsigned char *recv, *donors;
+    float *b0, *f, *eb, *q[2], *h[2];
+};
+fluvial_sediment_work fluvial_sediment_work_of(float *work, const relax_shape &sh) {
+    fluvial_sediment_work k{relax_work(work, sh), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {}, {}};
+    k.solve = k.hd.status ? k.hd.status + 8 : nullptr;
+    k.accum = k.hd.ints(16);
+    k.recv = k.hd.bytes(sh.n);
+    k.donors = k.hd.bytes(sh.n);
+    k.b0 = k.hd.floats(sh.n);
+    k.f = k.hd.floats(sh.n);
+    k.eb = k.hd.floats(sh.n);
+    for (float *&p : k.q) p = k.hd.floats(sh.n);
+    for (float *&p : k.h) p = k.hd.floats(sh.n);
+    return k;
+}
+sweep_cap fluvial_sediment_sweeps;
+}  // namespace
+
+extern "C" size_t nz_fluvial_sediment_work_floats(int32_t resolution, int32_t count) {
+    if (resolution <= 0 || count <= 0) return 0;
+    return fluvial_sediment_work_of(nullptr, tile_shape(resolution, count)).hd.total;
+}
+
+extern "C" int32_t nz_debug_fluvial_sediment_sweeps(int32_t sweeps) { return fluvial_sediment_sweeps.exchange(sweeps); }
+
+static int32_t fluvial_sediment_impl(nz_ctx *ctx, const float *height, const float *drainage, float *outp, float *work,
+                                     const nz_fluvial_sediment_desc *d, int res, int count, nz_handle dep, nz_handle *out) {
+    NZ_BEGIN(ctx, dep);
+    if (res == 0 || count == 0) return nz_ctx_finish(ctx, out);  // an empty payload: nothing to do
+    NZ_TRY(check_batch(res, count));
+    NZ_REQUIRE(d, "desc is NULL");
+    const implicit_args a = implicit_args_of(*d);
+    NZ_TRY(check_implicit_scalars(height, drainage, outp, work, a));
+    NZ_REQUIRE(std::isfinite(d->deposition), "deposition is not finite");
+    NZ_REQUIRE(d->deposition >= 0.0f, "deposition %g < 0", (double)d->deposition);
+    NZ_REQUIRE(d->iterations >= 0, "iterations %d < 0", d->iterations);
+    const relax_shape sh = tile_shape(res, count);
+    const fluvial_sediment_work k = fluvial_sediment_work_of(work, sh);
+    const size_t n = sh.n;
+    NZ_TRY(check_implicit_planes(height, drainage, outp, work, k.hd.total, a, res, count, n));
+    const nz_named_plane others[] = {{"out", outp, n},           {"work", work, k.hd.total},  {"height", height, n},
+                                     {"drainage", drainage, n}, {"hardness", a.hardness, n}, {"upliftMap", a.upliftMap, n}};
+    for (const auto &p : others) NZ_REQUIRE(!nz_planes_overlap(d->flux, n, p.p, p.floats), "flux overlaps %s", p.name);
+    NZ_REQUIRE(!nz_bytes_overlap(a.tally, 8, d->flux, n * sizeof(float)), "flux overlaps tally");
+    NZ_REQUIRE(!nz_bytes_overlap(a.proceed, 4, d->flux, n * sizeof(float)), "flux overlaps proceed");
+    const float G = d->deposition + 0.0f;  // -0 -> +0
+    const int K = d->iterations, sweeps = fluvial_sediment_sweeps.load();
+    int *totals = k.hd.status;
+    hipStream_t s = ctx->stream;
+    NZ_TRY(nz_launch_fluvial_sediment_begin(s, totals, k.solve, d->proceed));
+    NZ_TRY(nz_launch_fluvial_implicit_setup(s, height, drainage, d->hardness, d->upliftMap, k.recv, k.b0, k.f, k.solve,
+                                            d->erodibility, d->uplift, d->dt, d->seaLevel, res, count));
+    if (K > 0) NZ_TRY(nz_launch_fluvial_sediment_mask(s, height, k.donors, k.solve, d->seaLevel, res, count));
+    nz_ctx_handle_rides(ctx, out != nullptr);
+    // solve series j reads the right-hand side b; series K alternates between `out` and h[1], the ones before between h[0]
+    // and h[1]: h[0] keeps h(K-1), and `out` is written by the last series alone
+    auto solve_series = [&](int j, const float *b) -> int32_t {
+        float *planes[2] = {j == K ? outp : k.h[0], k.h[1]};
+        for (int p = 0; p < d->maxPasses; p++)
+            NZ_TRY(nz_launch_fluvial_implicit_pass(s, k.recv, b, k.f, p ? planes[(p - 1) & 1] : nullptr, planes[p & 1], k.solve,
+                                                   k.hd.flags[(p - 1) & 1], k.hd.flags[p & 1], res, count, p, sweeps));
+        return NZ_OK;
+    };
+    NZ_TRY(solve_series(0, k.b0));
+    for (int j = 1; j <= K; j++) {
+        NZ_TRY(nz_launch_fluvial_sediment_source(s, k.b0, k.h[0], k.eb, k.solve, k.accum, totals, n));
+        for (int p = 0; p < d->maxPasses; p++)
+            NZ_TRY(nz_launch_fluvial_sediment_gather_pass(s, k.donors, k.eb, p ? k.q[(p - 1) & 1] : nullptr, k.q[p & 1],
+                                                          k.accum, k.hd.flags[(p - 1) & 1], k.hd.flags[p & 1], res, count, p,
+                                                          sweeps));
+        // a series at rest holds the fixed point in both planes
+        NZ_TRY(nz_launch_fluvial_sediment_deposit(s, k.donors, k.q[0], k.b0, drainage, height, k.eb, k.accum, k.solve, totals, G,
+                                                  d->seaLevel, res, count));
+        NZ_TRY(solve_series(j, k.eb));
+    }
+    nz_ctx_arm_last_launch(ctx);
+    NZ_TRY(nz_launch_fluvial_sediment_finalise(s, height, outp, K ? k.h[0] : nullptr, K ? k.q[0] : nullptr, d->flux, k.solve,
+                                               totals, d->tally, n));
+    return nz_ctx_finish(ctx, out);
+}
+
+extern "C" int32_t nz_fluvial_sediment(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                       const nz_fluvial_sediment_desc *desc, int32_t resolution, nz_handle dep,
+                                       nz_handle *out_handle) {
+    return fluvial_sediment_impl(ctx, height, drainage, out, work, desc, resolution, 1, dep, out_handle);
+}
+
+extern "C" int32_t nz_fluvial_sediment_batch(nz_ctx *ctx, const float *height, const float *drainage, float *out, float *work,
+                                             const nz_fluvial_sediment_desc *desc, int32_t resolution, int32_t count,
+                                             nz_handle dep, nz_handle *out_handle) {
+    return fluvial_sediment_impl(ctx, height, drainage, out, work, desc, resolution, count, dep, out_handle);
+}
+
+// ---------------------------------------------------------------------------------------------
 // hillslope diffusion: one implicit step of any size as two tridiagonal line solves (new-framework feature,
 // include/noize_hip.h, nz_hillslope.hip)
 // ---------------------------------------------------------------------------------------------

@@ -25,6 +25,9 @@
 //                            host_demo_stages.hpp on the planes of <in.f32>: every plane read back goes to <out.bin>, a
 //                            "plane <name> <type> <elements>" line each and a "value <name> <int>" line per scalar on stdout)
 //          host_demo 0 - stage --list   (the scenario names, one per line; needs no device)
+//          host_demo <resolution> <out.bin> sediment <in.f32>   (SedimentFluvialStage through its defaults, every option, a
+//                            WRITE plane, a batch of a single tile's length, an exhausted budget and OnDestroy(), on the
+//                            planes of <in.f32>; resolution = 3 m + 1; output as in the stage mode)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +53,7 @@ int main(int argc, char **argv) {
         return 2;
     }
     if (argc > 4 && std::strcmp(argv[3], "stage") == 0) return stage_demo::main_stage(argc, argv);
+    if (argc > 3 && std::strcmp(argv[3], "sediment") == 0) return stage_demo::main_sediment(argc, argv);
     int res = std::atoi(argv[1]);
     const bool reduce = argc > 3 && std::strcmp(argv[3], "reduce") == 0;
     const bool context = argc > 3 && std::strcmp(argv[3], "context") == 0;

@@ -16,6 +16,7 @@
 
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -892,6 +893,107 @@ inline int main_stage(int argc, char **argv) {
         check(nz_ctx_create(0, &r.ctx), "nz_ctx_create");
         chosen->run(r);
         if (r.at != r.in.size()) throw std::runtime_error("the scenario did not read all of its input");
+        std::fclose(r.out);
+        nz_ctx_destroy(r.ctx);
+    } catch (const std::exception &e) {
+        std::fflush(stdout);
+        std::fprintf(stderr, "host_demo: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
+// ---- host_demo <res> <out.bin> sediment <in.f32>: SedimentFluvialStage, which schedules through ImplicitFluvialStage and so
+// has no scenario of the `stage` table.  <in.f32>: the heights (res^2, behind a depression fill), rainMap, hardness, upliftMap
+// (res^2 each), then for the res - 1 = 3 * m corner of the heights that corner and its nine m^2 blocks, block by block.
+// a: defaults at dt 50, 3 iterations; b: every option -- erodibility .1, uplift .01, dt 20, rain 2, a sea, the three maps, an
+// ample budget, Multiple routing with exponent 2, deposition 1, sedimentIterations 2, recordFlux, 2 iterations; c: the defaults
+// of a with recordFlux on a payload with a WRITE plane; d1, d: the corner, then its nine blocks as a batch of the same length;
+// e: a budget of 2 at 2 iterations; f: OnDestroy().  Planes and values as in the `stage` mode.
+inline void dump_sediment(Run &r, const std::string &s, SedimentFluvialStage &st) {
+    dump_implicit(r, s, st);
+    r.f32_or_null(s + ".flux", st.flux(), st.cells());
+    const float res = st.residual();
+    uint32_t word;
+    std::memcpy(&word, &res, 4);
+    r.value(s + ".residual_bits", (long)word);
+}
+
+inline void sediment(Run &r, int res) {
+    const int m = (res - 1) / 3;
+    const size_t n = (size_t)res * res, nc = (size_t)9 * m * m;
+    const float *h = r.take(n), *maps[3] = {r.take(n), r.take(n), r.take(n)}, *corner = r.take(nc), *blocks = r.take(nc);
+    SedimentFluvialStage st(r.ctx);
+    Driver d({&st});
+    auto through = [&](const std::string &step, const float *host, int rs, int count, bool pair = false) {
+        auto p = payload(r, host, rs, count, pair);
+        if (d.run(p->gd()) != p->gd()) throw std::runtime_error("the stage handed on another payload");
+        r.f32(step + ".height", p->gd()->data->ptr, p->cells());
+        dump_sediment(r, step, st);
+        if (pair) r.value(step + ".swapped", p->gd()->data == p->second.get() && p->gd()->write == p->first.get());
+    };
+    st.dt = 50.f;
+    st.iterations = 3;
+    through("a", h, res, 1);
+    std::unique_ptr<DeviceTile> t[3];
+    for (int k = 0; k < 3; k++) t[k] = r.tile(maps[k], n);
+    SedimentFluvialStage opt(r.ctx);
+    Driver dopt({&opt});
+    opt.iterations = 2;
+    opt.erodibility = .1f;
+    opt.uplift = .01f;
+    opt.dt = 20.f;
+    opt.rain = 2.f;
+    opt.seaLevel = SEA;
+    opt.maxPasses = AMPLE;
+    opt.rainMap = t[0].get();
+    opt.hardness = t[1].get();
+    opt.upliftMap = t[2].get();
+    opt.routing = FlowRouting::Multiple;
+    opt.flowExponent = 2;
+    opt.deposition = 1.f;
+    opt.sedimentIterations = 2;
+    opt.recordFlux = true;
+    {
+        auto p = payload(r, h, res, 1);
+        dopt.run(p->gd());
+        r.f32("b.height", p->gd()->data->ptr, p->cells());
+        dump_sediment(r, "b", opt);
+    }
+    opt.OnDestroy();
+    st.recordFlux = true;
+    through("c", h, res, 1, true);
+    st.recordFlux = false;
+    st.iterations = 1;
+    through("d1", corner, 3 * m, 1);
+    through("d", blocks, m, 9);
+    st.iterations = 2;
+    st.maxPasses = 2;
+    through("e", h, res, 1);
+    st.OnDestroy();
+    dump_sediment(r, "f", st);
+}
+
+// argv: <res> <out.bin> sediment <in.f32>
+inline int main_sediment(int argc, char **argv) {
+    Run r;
+    try {
+        const int res = std::atoi(argv[1]);
+        if (res < 4 || res % 3 != 1) throw std::runtime_error("sediment: the resolution must be 3 m + 1, m >= 1");
+        if (argc < 5) throw std::runtime_error("sediment: no input file given");
+        const size_t floats = (size_t)4 * res * res + (size_t)2 * (res - 1) * (res - 1);
+        FILE *f = std::fopen(argv[4], "rb");
+        if (!f) throw std::runtime_error(std::string("cannot open ") + argv[4]);
+        r.in.resize(floats + 1);
+        const size_t got = std::fread(r.in.data(), sizeof(float), r.in.size(), f);
+        std::fclose(f);
+        if (got != floats) throw std::runtime_error("sediment reads " + std::to_string(floats) + " floats");
+        r.in.resize(floats);
+        r.out = std::fopen(argv[2], "wb");
+        if (!r.out) throw std::runtime_error(std::string("cannot open ") + argv[2]);
+        check(nz_ctx_create(0, &r.ctx), "nz_ctx_create");
+        sediment(r, res);
+        if (r.at != r.in.size()) throw std::runtime_error("the mode did not read all of its input");
         std::fclose(r.out);
         nz_ctx_destroy(r.ctx);
     } catch (const std::exception &e) {

@@ -1199,7 +1199,7 @@ class ImplicitFluvialStage : public PipelineStage {
         for (const DeviceTile *m : {rainMap, hardness, upliftMap})  // before any launch
             if (m && m->Length != cells()) throw std::runtime_error("ImplicitFluvialStage: a plane does not fit the payload");
         // sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
-        size(work, nz_fluvial_implicit_work_floats(resolution, count));
+        size(work, solveWorkFloats());
         const bool multiple = routing == FlowRouting::Multiple;
         size(drainageWork, multiple ? nz_drainage_mfd_work_floats(resolution, count) : nz_drainage_area_work_floats(resolution, count));
         size(area, cells());
@@ -1232,13 +1232,7 @@ class ImplicitFluvialStage : public PipelineStage {
                 check(nz_drainage_area(ctx, cur->ptr, area->ptr, drainageWork->ptr, &drain, resolution, 0, nullptr),
                       "nz_drainage_area");
             }
-            if (b) {
-                check(nz_fluvial_implicit_batch(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, count, 0, &h),
-                      "nz_fluvial_implicit_batch");
-            } else {
-                check(nz_fluvial_implicit(ctx, cur->ptr, area->ptr, other->ptr, work->ptr, &solve, resolution, 0, &h),
-                      "nz_fluvial_implicit");
-            }
+            enqueueSolve(b != nullptr, cur->ptr, other->ptr, solve, &h);
             std::swap(cur, other);
         }
         if (d->write) {  // the pair as the run left it: `data` holds the result
@@ -1257,10 +1251,25 @@ class ImplicitFluvialStage : public PipelineStage {
     size_t workLength() const { return work ? work->Length : 0; }  // the floats of the work planes the stage holds now
     void OnDestroy() override { work.reset(); drainageWork.reset(); area.reset(); plane.reset(); tally.reset(); }
 
-  private:
+  protected:
+    // the hook of a stage that derives from this one (SedimentFluvialStage): the size of `work`, and the solve of one
+    // iteration, heights cur -> other, with the desc of the run
+    virtual size_t solveWorkFloats() const { return nz_fluvial_implicit_work_floats(resolution, count); }
+    virtual void enqueueSolve(bool batch, const float *cur, float *other, const nz_fluvial_implicit_desc &solve, nz_handle *h) {
+        if (batch) {
+            check(nz_fluvial_implicit_batch(ctx, cur, area->ptr, other, work->ptr, &solve, resolution, count, 0, h),
+                  "nz_fluvial_implicit_batch");
+        } else {
+            check(nz_fluvial_implicit(ctx, cur, area->ptr, other, work->ptr, &solve, resolution, 0, h), "nz_fluvial_implicit");
+        }
+    }
     void size(std::unique_ptr<DeviceTile> &t, size_t need) {
         if (!t || t->Length != need) t.reset(new DeviceTile(ctx, need));
     }
+    int resolution = 0, count = 1;
+    std::unique_ptr<DeviceTile> work, drainageWork, area, plane, tally;
+
+  private:
     int counted(int k) const {
         if (!tally) return -1;
         jobHandle.Complete();
@@ -1269,8 +1278,6 @@ class ImplicitFluvialStage : public PipelineStage {
         check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
         return words[k];
     }
-    int resolution = 0, count = 1;
-    std::unique_ptr<DeviceTile> work, drainageWork, area, plane, tally;
 };
 
 class MfdFluvialStage : public PipelineStage {
@@ -1441,6 +1448,54 @@ class ImplicitFluvialStripe {
 
   private:
     nz_ctx *ctx;
+};
+
+// Implicit stream-power erosion WITH sediment deposition (new-framework feature; the model: nz_fluvial_sediment in
+// include/noize_hip.h): ImplicitFluvialStage whose solve carries the xi-q deposition term, so valleys aggrade as well as
+// cut.  Everything but the solve call is inherited: per iteration the drainage call (either routing), the proceed word, the
+// plane ping-pong, steps() / passes() / converged() and the resize logic.  deposition: G >= 0, dimensionless; 0 is
+// ImplicitFluvialStage bit for bit.  sedimentIterations: the Gauss-Seidel iterations K of every solve; the iteration
+// contracts for G up to about 1, slower as G * dt grows -- read residual().  recordFlux: keep the sediment-flux plane Q of the
+// last applied iteration in flux().  maxPasses is the budget of each of the 2K + 1 series of a solve, and passes() counts
+// them all.  residual() waits for the handle: max |hK - h(K-1)| of the last iteration that ran, -1 before the first run.
+class SedimentFluvialStage : public ImplicitFluvialStage {
+  public:
+    using ImplicitFluvialStage::ImplicitFluvialStage;
+    float deposition = .5f;
+    int sedimentIterations = 4;
+    bool recordFlux = false;
+    const float *flux() const { return fluxPlane ? fluxPlane->ptr : nullptr; }  // nullptr without recordFlux
+    float residual() const {
+        if (!work) return -1.f;
+        jobHandle.Complete();
+        float words[3];
+        check(nz_tile_download(ctx, work->ptr, words, 3, 0, nullptr), "nz_tile_download");
+        check(nz_ctx_synchronize(ctx), "nz_ctx_synchronize");
+        return words[2];
+    }
+    void OnDestroy() override {
+        fluxPlane.reset();
+        ImplicitFluvialStage::OnDestroy();
+    }
+
+  protected:
+    size_t solveWorkFloats() const override { return nz_fluvial_sediment_work_floats(resolution, count); }
+    void enqueueSolve(bool batch, const float *cur, float *other, const nz_fluvial_implicit_desc &solve, nz_handle *h) override {
+        if (recordFlux) size(fluxPlane, cells());
+        else fluxPlane.reset();
+        const nz_fluvial_sediment_desc desc{solve.erodibility, solve.uplift, solve.dt, solve.seaLevel, solve.maxPasses,
+                                            solve.hardness, solve.upliftMap, solve.proceed, solve.tally, deposition,
+                                            sedimentIterations, fluxPlane ? fluxPlane->ptr : nullptr};
+        if (batch) {
+            check(nz_fluvial_sediment_batch(ctx, cur, area->ptr, other, work->ptr, &desc, resolution, count, 0, h),
+                  "nz_fluvial_sediment_batch");
+        } else {
+            check(nz_fluvial_sediment(ctx, cur, area->ptr, other, work->ptr, &desc, resolution, 0, h), "nz_fluvial_sediment");
+        }
+    }
+
+  private:
+    std::unique_ptr<DeviceTile> fluxPlane;
 };
 
 class MeshTileStage : public PipelineStage {

@@ -1498,7 +1498,7 @@ class ImplicitFluvialStage(PipelineStage):
             if m is not None and m.Length != n:  # before any launch
                 raise ValueError("ImplicitFluvialStage.%s holds %d floats, the payload %d" % (name, m.Length, n))
         # sized on (resolution, count) like DrainageAreaStage's: the per-tile bytes depend on the number of 64 x 16 tiles
-        self.work = self._size(self.work, True, N.lib.nz_fluvial_implicit_work_floats(self.resolution, self.count))
+        self.work = self._size(self.work, True, self._solve_work_floats())
         multiple = self.routing == FlowRouting.Multiple
         if multiple:
             need = N.lib.nz_drainage_mfd_work_floats(self.resolution, self.count)
@@ -1527,13 +1527,21 @@ class ImplicitFluvialStage(PipelineStage):
         for _ in range(self.iterations):
             self.ctx.call(entry, cur.ptr, self._area.ptr,
                           self.drainageWork.ptr, C.byref(drain), *tail, handle=False)
-            self.jobHandle = self.ctx.call("nz_fluvial_implicit_batch" if batch else "nz_fluvial_implicit", cur.ptr,
-                                           self._area.ptr, other.ptr, self.work.ptr, C.byref(solve), *tail)
+            self.jobHandle = self._enqueue_solve(batch, cur, other, solve, tail)
             cur, other = other, cur
         if d.write is not None:
             d.data, d.write = cur, other  # the pair as the run left it: `data` holds the result
         elif cur is not d.data:           # an odd count ended in the stage's plane
             self.jobHandle = self.ctx.call("nz_flush_write_slice", d.data.ptr, cur.ptr, n)
+
+    # the hook of a stage that derives from this one (SedimentFluvialStage): the size of `work`, and the solve of one iteration
+    def _solve_work_floats(self):
+        return N.lib.nz_fluvial_implicit_work_floats(self.resolution, self.count)
+
+    def _enqueue_solve(self, batch, cur, other, solve, tail):
+        """Enqueue the solve of one iteration, heights `cur` -> `other`, with the FluvialImplicitDesc of the run."""
+        return self.ctx.call("nz_fluvial_implicit_batch" if batch else "nz_fluvial_implicit", cur.ptr,
+                             self._area.ptr, other.ptr, self.work.ptr, C.byref(solve), *tail)
 
     def OnDestroy(self):
         self.DisposeArrays()
@@ -1715,6 +1723,61 @@ class HillslopeDiffusionStage(PipelineStage):
 
     def OnDestroy(self):
         self.DisposeArrays()
+
+
+class SedimentFluvialStage(ImplicitFluvialStage):
+    """Implicit stream-power erosion WITH sediment deposition (new-framework feature; the model is the comment block of
+    nz_fluvial_sediment in include/noize_hip.h): ImplicitFluvialStage whose solve carries the xi-q deposition term, so
+    valleys aggrade as well as cut.  Everything but the solve call is inherited: per iteration the drainage call (either
+    routing), the proceed word, the plane ping-pong, steps / passes / converged and the resize logic.
+
+    deposition: G >= 0, dimensionless; 0 is ImplicitFluvialStage bit for bit.  sedimentIterations: the Gauss-Seidel
+    iterations K of every solve; the iteration contracts for G up to about 1, slower as G * dt grows -- read `residual`.
+    recordFlux: keep the sediment-flux plane Q of the last applied iteration in `flux`.  maxPasses is the budget of each of
+    the 2K + 1 series of a solve, and `passes` counts them all.
+
+    After the handle completes: `residual` is max |hK - h(K-1)| of the last iteration that ran (0.0 when it was not
+    applied), `flux` the stage's own flux plane (None without recordFlux)."""
+
+    def __init__(self, ctx, iterations=1, erodibility=0.05, uplift=0.002, dt=1.0, rain=1.0, seaLevel=ImplicitFluvialStage.SEA_OFF,
+                 maxPasses=None, rainMap=None, hardness=None, upliftMap=None, routing=FlowRouting.Steepest, flowExponent=1,
+                 deposition=0.5, sedimentIterations=4, recordFlux=False):
+        super().__init__(ctx, iterations, erodibility, uplift, dt, rain, seaLevel, maxPasses, rainMap, hardness, upliftMap,
+                         routing, flowExponent)
+        self.deposition = deposition
+        self.sedimentIterations = sedimentIterations
+        self.recordFlux = recordFlux
+        self._flux = None  # the flux plane, with recordFlux
+
+    def DisposeArrays(self):
+        if self._flux is not None and self._flux.IsCreated:
+            self._flux.Dispose()
+        self._flux = None
+        super().DisposeArrays()
+
+    @property
+    def flux(self):
+        """The sediment flux Q of the last applied iteration; None without recordFlux, before the first payload and after
+        OnDestroy."""
+        return self._flux
+
+    @property
+    def residual(self):
+        """max |hK - h(K-1)| of the last iteration that ran; None before the first run."""
+        if self._tally is None:
+            return None
+        self.jobHandle.Complete()
+        return float(self.ctx.wrap(self.work.ptr, 3, dtype=np.int32).ToArray().view(np.float32)[2])
+
+    def _solve_work_floats(self):
+        return N.lib.nz_fluvial_sediment_work_floats(self.resolution, self.count)
+
+    def _enqueue_solve(self, batch, cur, other, solve, tail):
+        self._flux = self._size(self._flux, bool(self.recordFlux), self.count * self.resolution * self.resolution)
+        desc = N.FluvialSedimentDesc(*[getattr(solve, f[0]) for f in N.FluvialImplicitDesc._fields_], self.deposition,
+                                     self.sedimentIterations, self._flux.ptr if self._flux is not None else None)
+        return self.ctx.call("nz_fluvial_sediment_batch" if batch else "nz_fluvial_sediment", cur.ptr, self._area.ptr,
+                             other.ptr, self.work.ptr, C.byref(desc), *tail)
 
 
 class MeshTileStage(PipelineStage):  # Mesh/Stage/MeshTileStage.cs:28-61
