@@ -1,6 +1,6 @@
 // nz_flow_stream.hip -- the whole FlowMapStage (fill, `iterations` x (outflow, water update), velocity, normalise;
 // Geologic/Stage/FlowMapStage.cs:124-195) as ONE row-streaming launch (gfx950).  Built with the max-ILP scheduling
-// strategy (Makefile): a wave here is one long dependent stream and only three share a SIMD.
+// strategy (Makefile): a wave here is one long dependent stream and only two share a SIMD (FS_WPE).
 #include <cstdlib>
 
 #include "nz_internal.hpp"
@@ -28,7 +28,7 @@ __device__ __forceinline__ float wave_next0(float v) {
 // except the wave's private ring of height rows (tot = water + height needs the height again four times, two rows
 // later each time), no barrier, no flag.  Redundant work is the x halo (2n columns per side of 128) and the pipeline
 // fill of a row segment (iteration i starts 2(n - i) + 1 rows above the segment): 108 / 128 x S / (S + 2n) of the
-// executed cell-iterations are stored ones, 0.70 for the 51-row segments that give every SIMD of the chip three waves
+// executed cell-iterations are stored ones, 0.75 for the 78-row segments that give every SIMD of the chip two waves
 // at 4096^2 (0.47 for the tile kernel).  Same per-cell functions, same operand order: bit-identical results.
 // -DNZ_FLOW_PROBE: lane 0 of every wave stamps s_memrealtime (100 MHz) and s_memtime (shader clock) at its start, after
 // the pipeline fill and at its end, plus HW_ID / XCC_ID, into a caller-supplied buffer (tools/probe_flow_stream.py).
@@ -45,8 +45,33 @@ __device__ unsigned long long *nz_flow_probe_buf = nullptr;  // [wave][8]
 #endif
 constexpr int FS_WPE = 2;  // waves per SIMD the four- and five-iteration kernels are register-allocated for: 176 VGPRs, nothing spilled (3: 168 VGPRs and a 25-dword spill; 0.147 against 0.149 ms at 4096^2, round 4)
 constexpr int FS_RING = 16;   // rows of height kept per wave (needs 2n - 1 <= 9)
+// Fair share of a SIMD between its two waves (n >= 4, a one-round launch: nz_launch_flow_stream).  A SIMD arbitrates VALU
+// issue by priority, then by age: at equal priority the older wave runs nearly unimpeded, ends early and leaves the
+// younger one alone on the SIMD, at half the issue rate, for the rest of the launch (4096^2, n = 5: wave slot 0 ends at
+// 0.65 of the span).  So the two take turns: in even slices of the 100 MHz clock, 2^FS_FAIR_SHIFT ticks long, the wave in
+// the even slot of the SIMD runs at s_setprio 1 and the other at 0, in odd slices the other way round -- each is the
+// favoured wave half of the time whatever its age or progress.  A wave reads the clock (one scalar memory read) and sets
+// its priority at the top of a trip of the steady loop, or of a step of the fill and drain loops; it waits for the read
+// there, while its partner issues (setting the priority at the END of the trip, from a reading a trip old, left the
+// slots' mean ends 18.8 us apart and the stage at 0.1305 ms where this form gave 0.1280 in the same visit).
+// Everything here is wave-uniform: s_cmp / s_cbranch_scc around the two s_setprio (tools/kernel_isa.sh).
+// "The wave in the even slot" is bit 0 of HW_ID.wave_id.  Nothing guarantees that the two resident waves of a SIMD sit in
+// slots of opposite parity: in the measured launch, alone on the chip, they are slots 0 and 1 on every SIMD
+// (profiles/r14_flow_fair_timeline.txt), but beside another kernel's waves they may be 0 and 2.  Then both flip together,
+// the arbitration goes back to age and the gain is lost; the results are the same either way.
+// FS_FAIR_SHIFT, flow stage of the 4096^2 step, n = 5: 9: 0.1281 ms, 10: 0.1264, 11: 0.1251, 12: 0.1250 (0.1345 without;
+// a trip takes about 4 us = 2^8.6 ticks).  11 leaves the two slots' mean ends 3.6 us apart, 12 8.9 us.
+// Priorities by the wave's OWN progress (flipped every 3, 6 or 12 steps, no clock, no HW_ID) were measured first: 0.1296,
+// 0.1306 and 0.1313 ms -- the favour alternates, but the lead of the older wave is not bounded and it still ends at 0.77.
+// (profiles/r14_flow_fair_variants.txt has the timelines and bench lines of every variant; HISTORY.md the account.)
+constexpr int FS_FAIR_SHIFT = 11;
+__device__ __forceinline__ void fs_fair_prio() {
+    const unsigned slot = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (0 << 11));  // HW_ID.wave_id, bit 0: which of the SIMD's wave slots
+    if ((((unsigned)(__builtin_amdgcn_s_memrealtime() >> FS_FAIR_SHIFT)) ^ slot) & 1u) __builtin_amdgcn_s_setprio(0);
+    else __builtin_amdgcn_s_setprio(1);
+}
 // NC = columns per lane: 2 (a 128-column strip per wave, 12 registers of state per column and iteration = 120 at n = 5:
-// three waves per SIMD) or 1 (64-column strips: 1.22x the halo columns, half the state per lane -- five waves per SIMD)
+// two waves per SIMD) or 1 (64-column strips: 1.22x the halo columns, half the state per lane -- five waves per SIMD)
 
 // a row of the strip: NC cells per lane
 template <int NC>
@@ -308,8 +333,9 @@ __device__ __forceinline__ fs_row<NC> fs_load_row(const float *__restrict__ h, c
 template <int NST, int NC, bool XEDGE, bool FAST>
 __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *__restrict__ h, float *__restrict__ dst,
                                                  const nz_geom &g, const int lx0, const int s0, const int s1,
-                                                 const float nmin, const float nrange) {
+                                                 const float nmin, const float nrange, const bool fair_arg) {
     constexpr bool VEC = !XEDGE;
+    const bool fair = NST >= 4 && fair_arg;  // compiled out of the kernels that are not built for FS_WPE waves per SIMD
     const float inv_range = FAST ? 1.0f / nrange : 0.0f;
     constexpr int H = 2 * NST, FS_TW = 64 * NC;
     const int lane = threadIdx.x;
@@ -352,6 +378,8 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
     fs_row<NC> hp = fs_load_row<NC, VEC>(h, g, min(t0 + 1, g.zc1), gx);
     ring[((t0 + 1) & (FS_RING - 1)) * 64] = hp;
     int t = t0;
+#define NZ_FS_PRIO() \
+    if (fair) fs_fair_prio()
 #define NZ_FS_STEP(NA, C, T, HP, HN)                                                                              \
     do {                                                                                                          \
         fs_step<NST, NC, NA, C, XEDGE, VEC, FAST>(st, T, HP, HN, ring, b, gx, lane_x0, lane_x1, lane_x1o, g, nmin, nrange, \
@@ -360,6 +388,7 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
 #define NZ_FS_PHASE(K)                                                            \
     if (NST > K) {                                                                \
         for (int q = 0; q < 4 && t < t1; q++, t++) {                              \
+            NZ_FS_PRIO();                                                         \
             const fs_row<NC> hn = fs_load_row<NC, VEC>(h, g, min(t + 2, g.zc1), gx);  \
             NZ_FS_STEP((K < NST ? K : NST), false, t, hp, hn);                    \
             hp = hn;                                                              \
@@ -376,6 +405,7 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
         // z-neighbours: the last stage's row zc0 + 1, the first whose z-neighbours are both real, is reached at t = zc0 + H - 1
         const int tfill = min(t1, max(s0, g.zc0 + 1) + H - 1);
         for (; t < tfill; t++) {
+            NZ_FS_PRIO();
             const fs_row<NC> hn = fs_load_row<NC, VEC>(h, g, min(t + 2, g.zc1), gx);
             NZ_FS_STEP(NST, true, t, hp, hn);
             hp = hn;
@@ -389,6 +419,7 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
     // the windows rotate by renaming, not by moves.
     const int tsteady = min(t1, g.zc1);
     for (; t + 2 < tsteady; t += 3) {
+        NZ_FS_PRIO();
         const fs_row<NC> hn = fs_load_row<NC, VEC>(h, g, t + 2, gx);
         NZ_FS_STEP(NST, false, t, hp, hn);
         const fs_row<NC> hn2 = fs_load_row<NC, VEC>(h, g, min(t + 3, g.zc1), gx);
@@ -399,18 +430,20 @@ __device__ __forceinline__ void flow_stream_body(fs_row<NC> *ring, const float *
     }
     // the last one or two steps of an inner segment; the drain of a segment that ends on the grid's last row
     for (; t < t1; t++) {
+        NZ_FS_PRIO();
         const fs_row<NC> hn = fs_load_row<NC, VEC>(h, g, min(t + 2, g.zc1), gx);
         NZ_FS_STEP(NST, true, t, hp, hn);
         hp = hn;
     }
 #undef NZ_FS_PHASE
 #undef NZ_FS_STEP
+#undef NZ_FS_PRIO
 }
 
 template <int NST, int NC, bool FAST>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NST >= 4 ? FS_WPE : 4)))
 void flow_stream_kernel(const float *__restrict__ h, float *__restrict__ dst, nz_geom g, int S, int nstrips, int Se,
-                        int nseg_edge, float nmin, float nrange, int aligned) {
+                        int nseg_edge, float nmin, float nrange, int aligned, int fair) {
     __shared__ fs_row<NC> s_ring[FS_RING * 64];
     constexpr int FS_TW = 64 * NC, H = 2 * NST, OW = FS_TW - 2 * H;
     // The first blocks are the two border strips (one when the grid is a single strip wide), whose steps carry the border
@@ -439,8 +472,8 @@ void flow_stream_kernel(const float *__restrict__ h, float *__restrict__ dst, nz
     NZ_FPROBE(1, __builtin_amdgcn_s_memtime());
     NZ_FPROBE(6, (unsigned long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)));   // HW_ID
     NZ_FPROBE(7, (unsigned long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11)) | ((unsigned long long)inner << 32));  // XCC_ID
-    if (inner) flow_stream_body<NST, NC, false, FAST>(ring, h + off, dst + off, g, lx0, s0, s1, nmin, nrange);
-    else flow_stream_body<NST, NC, true, FAST>(ring, h + off, dst + off, g, lx0, s0, s1, nmin, nrange);
+    if (inner) flow_stream_body<NST, NC, false, FAST>(ring, h + off, dst + off, g, lx0, s0, s1, nmin, nrange, fair != 0);
+    else flow_stream_body<NST, NC, true, FAST>(ring, h + off, dst + off, g, lx0, s0, s1, nmin, nrange, fair != 0);
     NZ_FPROBE(4, __builtin_amdgcn_s_memrealtime());
     NZ_FPROBE(5, __builtin_amdgcn_s_memtime());
 }
@@ -481,7 +514,14 @@ int32_t nz_launch_flow_stream(hipStream_t s, const float *h, float *dst, const n
     const int aligned = (bits & 7) == 0;
     const dim3 grid((unsigned)nblocks, g.count);
     const bool fast = nz_tls_float_mode >= NZ_FLOAT_RELAXED;
-#define NZ_FSL(N, F) NZ_LAUNCH((flow_stream_kernel<N, 2, F>), grid, dim3(64), 0, s, h, dst, g, S, nstrips, Se, nseg_e, nmin, nrange, aligned)
+    // The two waves of a SIMD take turns at the higher priority (fs_fair_prio) when the launch is one round of resident
+    // waves, the case that was measured.  A launch of several rounds (8192^2, large batches) keeps the arbitration by age:
+    // there a freshly dispatched wave would share the SIMD evenly with a half-finished one, which has been neither reasoned
+    // through nor measured (NZ_FLOW_FAIR=2 runs it).
+    // NZ_FLOW_FAIR: 0 never, 1 that rule (default), 2 whenever the kernel has the code (n >= 4).
+    static const int fair_mode = getenv("NZ_FLOW_FAIR") ? atoi(getenv("NZ_FLOW_FAIR")) : 1;
+    const int fair = n >= 4 && (fair_mode == 2 || (fair_mode == 1 && (long long)nblocks * g.count <= waves));
+#define NZ_FSL(N, F) NZ_LAUNCH((flow_stream_kernel<N, 2, F>), grid, dim3(64), 0, s, h, dst, g, S, nstrips, Se, nseg_e, nmin, nrange, aligned, fair)
 #define NZ_FS(N)                     \
     do {                             \
         if (fast) NZ_FSL(N, true);   \

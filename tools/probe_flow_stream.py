@@ -64,6 +64,10 @@ for k, iv in simd.items():
     cnt.append(len(iv))
 print("SIMDs seen %d; waves per SIMD: mean %.2f min %d max %d; resident waves while busy: mean %.2f; SIMD busy fraction of "
       "the span: mean %.2f min %.2f" % (len(simd), np.mean(cnt), min(cnt), max(cnt), np.mean(conc), np.mean(busy), np.min(busy)))
+# how long a SIMD holds fewer waves than it started with: its first wave's end to its last wave's end, over the span
+tail = [(max(b for _, b in iv) - min(b for _, b in iv)) / end.max() for iv in simd.values() if len(iv) > 1]
+if tail:
+    print("per SIMD (last end - first end) / span: mean %.3f max %.3f" % (np.mean(tail), np.max(tail)))
 hist = collections.Counter(cnt)
 print("waves per SIMD histogram:", dict(sorted(hist.items())))
 slot = p[:, 6] & 0xf
